@@ -2,6 +2,7 @@
 """Benchmark of the Huffman block-codec hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload zipf255|uniform256|const41|uniform255|logtext]
+                    [--dump-outputs DIR]
 
 One "step" = one encode + one decode of the rank's shard (default 1 GiB, 64 KiB blocks) with
 the input already resident in HBM.  The headline workload is `zipf255` (BASELINE.json configs[2]:
@@ -294,6 +295,24 @@ def live_traffic(workload: str, kernels, passthrough=(), timeout: float = 120.0,
         return None
 
 
+DUMP_BYTES_PER_ARRAY = 16 << 20     # --dump-outputs: at most this much of each array (three arrays: 48 MiB in all)
+
+
+def dump_outputs(path: str, arrays) -> None:
+    """--dump-outputs: (name, tensor, dtype) -> path/<name>.npy in float32 or float64 (bytes and offsets are exact in them).
+    An array larger than DUMP_BYTES_PER_ARRAY is cut to a seeded sample of positions that depends on its length alone, so
+    that two runs - or two builds - with the same arguments dump the same positions."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t, dtype in arrays:
+        cap = DUMP_BYTES_PER_ARRAY // np.dtype(dtype).itemsize
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), cap))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(dtype))
+
+
 def launch_ranks(args) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks as a CHILD process (this
     process has not touched a GPU and never will) and relay rank 0's JSON line."""
@@ -406,8 +425,9 @@ class Bench:
         return out
 
     def run(self, workload: str, steps: int, warmup: int, decode: str = None, bytes_per_gpu: int = None,
-            other_decode: bool = True) -> dict:
-        """K timed steps of one workload on every rank; returns rank 0's result record."""
+            other_decode: bool = True, dump_dir: str = None) -> dict:
+        """K timed steps of one workload on every rank; returns rank 0's result record.  With dump_dir, rank 0 writes what
+        the last timed step returned to its caller there (dump_outputs)."""
         from libhuffman_amd.sharding import shard_range
         a, torch, dist, codec = self.a, self.torch, self.dist, self.codec
         world, rank, dev = self.world, self.rank, self.dev
@@ -479,6 +499,10 @@ class Bench:
         elapsed = time.perf_counter() - t0
         raw = codec.decode_result()
         assert raw == n, f"decode produced {raw} of {n} bytes"
+        if dump_dir is not None and rank == 0:
+            # (before the untimed decoders below write `back` again)
+            dump_outputs(dump_dir, [("stream", out[:int(offs[nb].item())], "float32"), ("offsets", offs, "float64"),
+                                    ("decoded", back, "float32")])
         enc_prof, enc_calls = codec.profile("encode")
         dec_prof, dec_calls = codec.profile("decode")
         codec.set_profiling(False)
@@ -915,10 +939,15 @@ def main() -> None:
     ap.add_argument("--no-python-layer", action="store_true", help="skip the huffmanfile (configs[4] shape) figure")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not count the longest kernel's HBM bytes with two rocprofv3 --pmc child passes (the stamp of profiles/traffic.json stays)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline workload's last timed step returned (rank 0's shard) as DIR/stream.npy, "
+                         "DIR/offsets.npy and DIR/decoded.npy; arrays over 16 MiB as a fixed, seeded sample")
     if len(sys.argv) == 4 and sys.argv[1] == "--cpu-all-cores-child":
         cpu_all_cores_child(sys.argv[2], int(sys.argv[3]))
         return
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -966,7 +995,7 @@ def main() -> None:
         if w not in WORKLOADS:
             raise SystemExit(f"unknown secondary workload {w}")
 
-    main_rec = bench.run(args.workload, args.steps, args.warmup)
+    main_rec = bench.run(args.workload, args.steps, args.warmup, dump_dir=args.dump_outputs)
     sec_recs = {w: bench.run(w, args.steps, args.warmup) for w in secondary}
     # the same K steps with the BLOCK INDEX ALONE (no sub-index: what a stream that comes without the
     # encoder's side information costs) - a timed region of its own, so that the driver's record holds both

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Capture known-answer vectors from the UNMODIFIED reference (oracle/_ref/libhuffman_ref.so,
-built from /root/reference/src by `make -C oracle ref`) into tests/golden/vectors.json.
+built from /root/reference/src by `make -C oracle ref`) into tests/golden/vectors.json, and its
+outcomes on the seeded inputs of tests/test_oracle.py's differential tests into
+tests/golden/differential.json.
 
 Runs only in the authoring container (the reference does not exist on the GPU box); the JSON
 it writes is data: inputs (literal bytes or generator parameters) and expected outputs (hex
@@ -15,6 +17,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import test_oracle as T  # noqa: E402
 from libhuffman_amd import datagen  # noqa: E402
 from oracle.oracle import Reference, build  # noqa: E402
 
@@ -107,6 +111,63 @@ def main() -> None:
     path = os.path.join(ROOT, "tests", "golden", "vectors.json")
     with open(path, "w") as f:
         json.dump(vectors, f, indent=1)
+    print("wrote", path, os.path.getsize(path), "bytes")
+    differential(ref)
+
+
+def decode_in_child(ref, stream):
+    """The reference decoder in a forked child: on some corrupt inputs (NULL root) it
+    dereferences NULL, which must not take this script down with it.  (err, output) or None if it crashed."""
+    import pickle
+    rfd, wfd = os.pipe()
+    pid = os.fork()
+    if pid == 0:
+        try:
+            err, out = ref.decode(stream, raw_hint=1 << 17)
+            os.write(wfd, pickle.dumps((int(err), out.tobytes())))
+        finally:
+            os._exit(0)
+    os.close(wfd)
+    chunks = []
+    while True:
+        b = os.read(rfd, 1 << 16)
+        if not b:
+            break
+        chunks.append(b)
+    os.close(rfd)
+    _, status = os.waitpid(pid, 0)
+    if os.WIFSIGNALED(status) or not chunks:
+        return None
+    return pickle.loads(b"".join(chunks))
+
+
+def differential(ref) -> None:
+    """The reference's encode and decode of the inputs of tests/test_oracle.py's differential tests, as digests."""
+    vs, garbage, handmade = {}, {}, {}
+    for seed in range(6):
+        data, bs = T.differential_input(seed)
+        out = ref.encode(data, bs)
+        err, back = ref.decode(out, raw_hint=data.size + 64)
+        vs[seed] = {"input_sha256": sha(data), "blocksize": bs, "encode_len": int(out.size), "encode_sha256": sha(out),
+                    "decode_err": int(err), "decode_sha256": sha(back)}
+    for seed in range(4):
+        rng, data = T.garbage_input(seed)
+        good = ref.encode(data, 1024)
+        muts = []
+        for pos, bit, bad in T.garbage_mutations(rng, good):
+            res = decode_in_child(ref, bad)
+            muts.append([pos, bit, None, None] if res is None else [pos, bit, res[0], sha(res[1])])
+        garbage[seed] = {"input_sha256": sha(data), "encode_sha256": sha(good), "mutations": muts}
+    for seed in range(6):
+        stream, _ = T.handmade_input(seed)
+        res = decode_in_child(ref, stream)
+        handmade[seed] = {"stream_sha256": sha(stream), "decode_err": None if res is None else res[0],
+                          "decode_sha256": None if res is None else sha(res[1])}
+    path = os.path.join(ROOT, "tests", "golden", "differential.json")
+    with open(path, "w") as f:
+        json.dump({"_about": "captured from the unmodified reference by tests/golden/make_goldens.py",
+                   "vs_reference": vs, "garbage": garbage, "handmade": handmade}, f, indent=1)
+        f.write("\n")
     print("wrote", path, os.path.getsize(path), "bytes")
 
 

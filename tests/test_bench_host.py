@@ -106,3 +106,25 @@ def test_the_ranks_of_a_job_agree_at_its_end(tmp_path, case, world, want):
         agreed, seconds = (tmp_path / ("rank%d" % r)).read_text().split()
         assert (agreed == "1") == want, (case, r)
         assert float(seconds) < 30.0
+
+
+def test_dumped_outputs_are_exact_and_the_same_sample_every_time(tmp_path):
+    """bench.dump_outputs (--dump-outputs): bytes as float32 and offsets as float64 hold the values exactly; an array above
+    DUMP_BYTES_PER_ARRAY is cut to sorted positions that are the same in every run; the files stay within 64 MB."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(5)
+    small = torch.from_numpy(rng.integers(0, 256, 1000, dtype=np.uint8))
+    offs = torch.from_numpy(np.cumsum(rng.integers(0, 1 << 40, 300)).astype(np.int64))
+    big = torch.from_numpy(rng.integers(0, 256, bench.DUMP_BYTES_PER_ARRAY // 4 + 12345, dtype=np.uint8))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [("stream", small, "float32"), ("offsets", offs, "float64"), ("decoded", big, "float32")])
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("stream", "offsets", "decoded")}
+    assert got["stream"].dtype == np.float32 and np.array_equal(got["stream"], small.numpy())
+    assert got["offsets"].dtype == np.float64 and np.array_equal(got["offsets"].astype(np.int64), offs.numpy())
+    assert got["decoded"].dtype == np.float32 and got["decoded"].size == bench.DUMP_BYTES_PER_ARRAY // 4
+    idx = np.sort(np.random.default_rng(0).integers(0, big.numel(), got["decoded"].size))
+    assert np.array_equal(got["decoded"], big.numpy()[idx])
+    for n in got:
+        assert np.array_equal(np.load(tmp_path / "b" / (n + ".npy")), got[n])
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 * 10 ** 6

@@ -1010,6 +1010,29 @@ def test_bench_counts_the_longest_kernels_traffic_in_its_own_run(torch_mod):
     assert rf["alg_bytes_per_launch"] <= rf["traffic"] <= 1.3 * rf["alg_bytes_per_launch"], rf
 
 
+def test_bench_dumps_what_its_last_timed_step_returned(torch_mod, oracle, tmp_path):
+    """--dump-outputs at a size below the sampling threshold: the stream and block offsets of the last timed step are the
+    oracle's for the bench's own input (zipf255 from position 0, a short last block), the decoded bytes are that input."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, bs = (2 << 20) + 1000, 65536
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--bytes-per-gpu", str(n),
+                          "--secondary", "none", "--no-cpu-baseline", "--no-live-traffic", "--no-index-free", "--no-python-layer",
+                          "--no-other-decode", "--dump-outputs", str(tmp_path)],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["config"]["bytes_per_gpu"] == n
+    data = datagen.zipf255(n)
+    want, want_offs = oracle.encode(data, bs, with_offsets=True)
+    got = {k: np.load(tmp_path / (k + ".npy")) for k in ("stream", "offsets", "decoded")}
+    assert got["stream"].dtype == np.float32 and np.array_equal(got["stream"], want)
+    assert got["offsets"].dtype == np.float64 and np.array_equal(got["offsets"], want_offs.astype(np.float64))
+    assert got["decoded"].dtype == np.float32 and np.array_equal(got["decoded"], data)
+
+
 @pytest.mark.parametrize("top", [17, 24])
 def test_many_blocks_of_deep_codes(torch_mod, codec, oracle, top):
     """600 blocks whose longest codes have 17..24 bits (the one-code-per-push form of pack_kernel), whole

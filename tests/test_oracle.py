@@ -3,7 +3,8 @@
 1. every known-answer vector of the reference's own tests for the path
    (test/encode_test.c:35, test/decode_test.c:32-74, huffmanfile_test.py:8-34);
 2. streams captured from the unmodified reference (tests/golden/vectors.json);
-3. live differential runs against oracle/_ref/libhuffman_ref.so on seeded inputs.
+3. differential runs on seeded inputs against what oracle/_ref/libhuffman_ref.so returned for them
+   (tests/golden/differential.json).
 """
 import hashlib
 
@@ -75,8 +76,10 @@ def test_null_root_is_an_error_not_a_crash(oracle):
     assert err == 6 and out.size == 0
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_differential_vs_reference(oracle, reference, seed):
+# Inputs of the differential tests, built from their seeds; tests/golden/make_goldens.py runs the same builders through the
+# unmodified reference and stores what it returned in tests/golden/differential.json.
+
+def differential_input(seed):
     rng = np.random.default_rng(seed)
     n = int(rng.integers(1, 40000))
     k = int(rng.integers(1, 256))           # k <= 255 keeps the reference's decoder usable
@@ -86,73 +89,26 @@ def test_differential_vs_reference(oracle, reference, seed):
     bs = int(rng.choice([0, 1, 7, 256, 4096, 65536]))
     if bs == 1:
         data = data[:300]
-    ref_out = reference.encode(data, bs)
-    ora_out = oracle.encode(data, bs)
-    assert np.array_equal(ref_out, ora_out)
-    rerr, rback = reference.decode(ref_out, raw_hint=data.size + 64)
-    oerr, oback, _ = oracle.decode(ora_out, data.size + 8)
-    assert rerr == oerr == 0 and np.array_equal(rback, oback) and np.array_equal(oback, data)
+    return data, bs
 
 
-def _reference_decode_in_child(reference, stream):
-    """Run the reference decoder in a forked child: on some corrupt inputs (NULL root, SURVEY
-    Appendix D) it dereferences NULL, which must not take pytest down with it."""
-    import os
-    import pickle
-    rfd, wfd = os.pipe()
-    pid = os.fork()
-    if pid == 0:
-        try:
-            err, out = reference.decode(stream, raw_hint=1 << 17)
-            os.write(wfd, pickle.dumps((int(err), out.tobytes())))
-        finally:
-            os._exit(0)
-    os.close(wfd)
-    chunks = []
-    while True:
-        b = os.read(rfd, 1 << 16)
-        if not b:
-            break
-        chunks.append(b)
-    os.close(rfd)
-    _, status = os.waitpid(pid, 0)
-    if os.WIFSIGNALED(status) or not chunks:
-        return None
-    return pickle.loads(b"".join(chunks))
-
-
-@pytest.mark.parametrize("seed", range(4))
-def test_differential_decode_of_garbage(oracle, reference, seed):
-    """Random bit flips in a valid stream must fail (or succeed) identically."""
+def garbage_input(seed):
+    """(the generator the mutations are drawn from, the input of the valid stream)"""
     rng = np.random.default_rng(100 + seed)
-    data = rng.integers(0, 40, size=3000, dtype=np.uint8)
-    good = reference.encode(data, 1024)
-    compared = 0
+    return rng, rng.integers(0, 40, size=3000, dtype=np.uint8)
+
+
+def garbage_mutations(rng, good):
+    """60 copies of a valid stream with one bit flipped each: (position, bit, stream)"""
     for _ in range(60):
         bad = good.copy()
         pos = int(rng.integers(0, bad.size))
-        bad[pos] ^= np.uint8(1 << int(rng.integers(0, 8)))
-        oerr, oout, _ = oracle.decode(bad, 1 << 16)
-        if oerr == 1:   # output larger than the test cap (mutated block_len) - not comparable
-            continue
-        res = _reference_decode_in_child(reference, bad)
-        if res is None:
-            # the reference crashed: only the NULL-root case may do that, and the decision
-            # for it is BTREE_CORRUPTED
-            assert oerr == 6
-            continue
-        rerr, rout = res
-        assert rerr == oerr
-        assert rout == oout.tobytes()
-        compared += 1
-    assert compared > 30
+        bit = int(rng.integers(0, 8))
+        bad[pos] ^= np.uint8(1 << bit)
+        yield pos, bit, bad
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_handmade_trees_reference_and_oracle_agree(oracle, reference, seed):
-    """Streams no encoder wrote (tests/handmade_streams.py: trees of any shape, codes of 1 to > 100 bits, with and without
-    the encoder's one-child root): the unmodified reference and the oracle deliver the same bytes - which is what lets the
-    GPU tests of such streams take the oracle's word."""
+def handmade_input(seed):
     import handmade_streams as hm
     rng = np.random.default_rng(400 + seed)
     parts, want = [], []
@@ -161,8 +117,61 @@ def test_handmade_trees_reference_and_oracle_agree(oracle, reference, seed):
                               int(rng.integers(1, 20000)), deep_often=bool(rng.integers(0, 2)), pad_ones=bool(rng.integers(0, 2)))
         parts.append(np.frombuffer(b, dtype=np.uint8))
         want.append(syms)
-    stream, data = np.concatenate(parts), np.concatenate(want)
+    return np.concatenate(parts), np.concatenate(want)
+
+
+@pytest.fixture(scope="module")
+def captured():
+    """What the unmodified reference returned on the inputs above (tests/golden/differential.json)"""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "differential.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_differential_vs_reference(oracle, captured, seed):
+    ref = captured["vs_reference"][str(seed)]
+    data, bs = differential_input(seed)
+    assert (sha(data), bs) == (ref["input_sha256"], ref["blocksize"])
+    ora_out = oracle.encode(data, bs)
+    assert (ora_out.size, sha(ora_out)) == (ref["encode_len"], ref["encode_sha256"])
+    oerr, oback, _ = oracle.decode(ora_out, data.size + 8)
+    assert ref["decode_err"] == oerr == 0 and ref["decode_sha256"] == sha(oback) and np.array_equal(oback, data)
+
+
+@pytest.mark.parametrize("seed", range(4))
+def test_differential_decode_of_garbage(oracle, captured, seed):
+    """Random bit flips in a valid stream must fail (or succeed) identically."""
+    ref = captured["garbage"][str(seed)]
+    rng, data = garbage_input(seed)
+    good = oracle.encode(data, 1024)
+    assert sha(data) == ref["input_sha256"] and sha(good) == ref["encode_sha256"]
+    compared = 0
+    for (pos, bit, bad), (rpos, rbit, rerr, rout_sha) in zip(garbage_mutations(rng, good), ref["mutations"], strict=True):
+        assert (pos, bit) == (rpos, rbit)
+        oerr, oout, _ = oracle.decode(bad, 1 << 16)
+        if oerr == 1:   # output larger than the test cap (mutated block_len) - not comparable
+            continue
+        if rerr is None:
+            # the reference crashed: only the NULL-root case may do that, and the decision
+            # for it is BTREE_CORRUPTED
+            assert oerr == 6
+            continue
+        assert rerr == oerr
+        assert rout_sha == sha(oout)
+        compared += 1
+    assert compared > 30
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_handmade_trees_reference_and_oracle_agree(oracle, captured, seed):
+    """Streams no encoder wrote (tests/handmade_streams.py: trees of any shape, codes of 1 to > 100 bits, with and without
+    the encoder's one-child root): the unmodified reference and the oracle deliver the same bytes - which is what lets the
+    GPU tests of such streams take the oracle's word."""
+    ref = captured["handmade"][str(seed)]
+    stream, data = handmade_input(seed)
+    assert sha(stream) == ref["stream_sha256"]
     oerr, oout, oused = oracle.decode(stream, data.size + 64, 1025)
     assert (oerr, oused) == (0, stream.size) and np.array_equal(oout, data)
-    res = _reference_decode_in_child(reference, stream)
-    assert res is not None and res[0] == 0 and res[1] == data.tobytes()
+    assert ref["decode_err"] == 0 and ref["decode_sha256"] == sha(data)
