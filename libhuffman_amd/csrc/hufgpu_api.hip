@@ -101,6 +101,7 @@ struct hufgpu_ctx {
     const uint64_t *last_offsets;
     uint8_t *last_out;
     uint64_t last_stream_len, last_out_cap, last_nblocks;
+    uint64_t last_failing;        /* hufgpu_decode_result: the first failing block of the last indexed decode (~0: none) */
     int last_max_tree;
 };
 
@@ -618,6 +619,7 @@ extern "C" int hufgpu_decode_result(hufgpu_ctx_t *ctx, uint64_t *raw_len)
     const uint8_t *last_st = ctx->last_st;
     ctx->last_st = NULL;                           /* the caller's buffers are not looked at again after this call */
     const uint64_t failing = ctx->h_result[2];
+    ctx->last_failing = failing;
     if (failing == ~0ull) {                        /* every block decoded */
         if (raw_len) *raw_len = ctx->h_result[1];
         return HUFE_OK;
@@ -1029,10 +1031,10 @@ static int discover_chain(hufgpu_ctx_t *ctx, const uint8_t *st, uint64_t avail, 
 
 /* The block index of a raw stream without decoding it into anything: see include/huffman_gpu.h. */
 #ifdef DFAST_DEBUG
-extern "C" int hufgpu_debug_dfast(unsigned long long *out16, int reset)
+extern "C" int hufgpu_debug_dfast(unsigned long long *out32, int reset)     /* DFAST_DBG_SLOTS counters */
 {
-    if (reset) { unsigned long long z[16] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(hufgpu::g_dfast_dbg), z, sizeof(z)); }
-    return (int)hipMemcpyFromSymbol(out16, HIP_SYMBOL(hufgpu::g_dfast_dbg), 16 * sizeof(unsigned long long));
+    if (reset) { unsigned long long z[DFAST_DBG_SLOTS] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(hufgpu::g_dfast_dbg), z, sizeof(z)); }
+    return (int)hipMemcpyFromSymbol(out32, HIP_SYMBOL(hufgpu::g_dfast_dbg), DFAST_DBG_SLOTS * sizeof(unsigned long long));
 }
 #endif
 
@@ -1204,9 +1206,16 @@ static int decode_stream_general(hufgpu_ctx_t *ctx, const void *d_stream, uint64
             if (m > 0 && in_place != ~0ull) {
                 prefix_raw = in_place;                 /* every candidate was a block: nothing to decode again */
             } else if (m > 0) {
+                ctx->last_failing = ~0ull;
                 err = hufgpu_decode(ctx, st, resume, ctx->d_chain, m, out, out_cap, flags, &prefix_raw, stream);
-                if (err != HUFE_OK) {                  /* cannot happen for probed blocks except for lack of room */
-                    if (err == HUFE_MEMORY) { if (raw_len) *raw_len = prefix_raw; return err; }
+                if (err == HUFE_MEMORY && ctx->last_failing < m) {
+                    /* the block that does not fit (hufgpu_decode_result) and what follows go to the in-order decoder, which
+                     * delivers what fits of it, as src/decoder.c does - not just the whole blocks in front of it */
+                    HIP_OK(ctx, hipMemcpyAsync(&resume, ctx->d_chain + ctx->last_failing, sizeof(resume), hipMemcpyDeviceToHost, s));
+                    HIP_OK(ctx, hipStreamSynchronize(s));
+                    complete = false;
+                    err = HUFE_OK;
+                } else if (err != HUFE_OK) {           /* cannot happen for probed blocks except for lack of room */
                     prefix_raw = 0; resume = 0; complete = false;   /* start over, sequentially */
                 }
             } else {

@@ -96,8 +96,15 @@ struct DfastLds {
     __device__ static __forceinline__ uint16_t *pairs(DecShared<THREADS> &sh) { return reinterpret_cast<uint16_t *>(sh.pay + PAIR_WORD); }
 };
 
+/* Counters of the debug build (-DDFAST_DEBUG; tools/dbg_dfast.py, tests/test_gpu_decode_edges.py).  0-15: this file's lean decoder
+ * (and decode_regs.hpp's rounds, which share 0-3 and 6-15); 16-31: what decode_regs.hpp made of a block - DFAST_DBG_REGS_* */
+#define DFAST_DBG_SLOTS 32
+#define DFAST_DBG_REGS_OUTCOME 16                    /* + 4 x caller (0 indexed kernel, 1 raw-stream probe, 2 in-order chain) + outcome:
+                                                        0 DREG_NO_TABLES, 1 DREG_OK, 2 DREG_FAILED, 3 the LONG instance was run */
+#define DFAST_DBG_REGS_SHRINK 28                     /* + 0, 1, 2: a segment done again with shares of 1/2, 1/4, 1/8 and less of the bits */
+#define DFAST_DBG_REGS_ONE_LENGTH 31                 /* blocks whose shares were cut to whole codewords of one length */
 #ifdef DFAST_DEBUG
-__device__ unsigned long long g_dfast_dbg[16];
+__device__ unsigned long long g_dfast_dbg[DFAST_DBG_SLOTS];
 #define DFAST_DBG(i, v) do { if (threadIdx.x == 0) atomicAdd(&g_dfast_dbg[i], (unsigned long long)(v)); } while (0)
 #define DFAST_DBGW(i, v) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_dfast_dbg[i], (unsigned long long)(v)); } while (0)
 #else
@@ -1181,7 +1188,7 @@ __device__ __forceinline__ void decode_fast_block(DecShared<THREADS> &sh, const 
 #ifndef DFAST_NO_REGS
         if (b.m.leaf < 0 && b.m.block_len >= DREG_MIN_BLOCK)
             regs = decode_payload_regs<THREADS>(sh, b.pay, b.pay_bytes, b.readable, b.m.block_len, a.out + b.obase, nullptr, 0,
-                                                [&]() { return dfast_tables_from_tree<THREADS, true, true>(sh, b.tree, b.m.tree_len) ? (uni32(sh.l2n) != 0u ? 2 : 1) : 0; });
+                                                [&]() { return dfast_tables_from_tree<THREADS, true, true>(sh, b.tree, b.m.tree_len) ? (uni32(sh.l2n) != 0u ? 2 : 1) : 0; }, 0);
         if (regs == 1) return;                          /* (DREG_OK: most blocks of most streams end here) */
 #endif
     }

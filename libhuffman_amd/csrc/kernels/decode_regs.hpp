@@ -497,6 +497,7 @@ __device__ __forceinline__ int decode_payload_regs_as(DecShared<THREADS> &sh, co
              * where codes of one length never fall into step by themselves (1 GiB of uniform bytes: 0.78 ms against 1.06 with
              * shares of 384 bits).  A block that only looks like it loses nothing. */
             if (one_length) {
+                if (!LONG) DFAST_DBG(DFAST_DBG_REGS_ONE_LENGTH, 1);   /* (the LONG instance runs behind the other: the block counted once) */
                 fixlen = Lfix;
                 cap = Lfix * (uint32_t)(((float)cap + 0.5f) * __builtin_amdgcn_rcpf((float)Lfix));
             }
@@ -644,6 +645,7 @@ __device__ __forceinline__ int decode_payload_regs_as(DecShared<THREADS> &sh, co
             DFAST_DBG(9, 1);
             if ((cap >> shrink) <= 64u) { ok = false; break; }         /* (shares of 64 bits hold what a lane can take: this is not a payload of this tree - the exact decoder says what it is) */
             shrink++;
+            DFAST_DBG(DFAST_DBG_REGS_SHRINK + (shrink < 3u ? shrink - 1u : 2u), 1);
             continue;
         }
         if (guessed) DFAST_DBG(12, 1);
@@ -753,13 +755,19 @@ __device__ __forceinline__ int decode_payload_regs_as(DecShared<THREADS> &sh, co
 /* A block's payload: by the pass that does not ask for codes beyond the table, and - when the table build says the block has some -
  * by the one that does (two instances of everything above: one pass with the question in it was 3 % slower on blocks that have
  * none, two passes chosen from inside the round loop 30 % - the sixteen registers came out of the choice as copies).
- * build_tables() -> 0: declined, 1: the table stands, 2: and the block has codes beyond it. */
+ * build_tables() -> 0: declined, 1: the table stands, 2: and the block has codes beyond it.  `caller` only names the caller to the
+ * debug build's counters (DFAST_DBG_REGS_OUTCOME: 0 the indexed kernel, 1 the raw-stream probe, 2 the in-order chain). */
 template <int THREADS, class BuildTables>
 __device__ __forceinline__ int decode_payload_regs(DecShared<THREADS> &sh, const uint8_t *pay, uint64_t pay_bytes, uint64_t readable, uint64_t block_len,
-                                                   uint8_t *gout, uint64_t *end_bits, uint64_t hint_bytes, BuildTables build_tables)
+                                                   uint8_t *gout, uint64_t *end_bits, uint64_t hint_bytes, BuildTables build_tables, int caller)
 {
     int r = decode_payload_regs_as<THREADS, false>(sh, pay, pay_bytes, readable, block_len, gout, end_bits, hint_bytes, build_tables);
-    if (r == DREG_LONG) r = decode_payload_regs_as<THREADS, true>(sh, pay, pay_bytes, readable, block_len, gout, end_bits, hint_bytes, []() { return 2; });
+    if (r == DREG_LONG) {
+        DFAST_DBG(DFAST_DBG_REGS_OUTCOME + 4 * caller + 3, 1);
+        r = decode_payload_regs_as<THREADS, true>(sh, pay, pay_bytes, readable, block_len, gout, end_bits, hint_bytes, []() { return 2; });
+    }
+    DFAST_DBG(DFAST_DBG_REGS_OUTCOME + 4 * caller + r, 1);
+    (void)caller;
     return r;
 }
 
@@ -809,7 +817,7 @@ __global__ __launch_bounds__(THREADS) void decode_chain_lean_kernel(const uint8_
              *  declines them: decode_fast.hpp's lean decoder walks such codes, with the tables of the tree's walk) */
             const int lean = block_len < DREG_MIN_BLOCK ? DREG_NO_TABLES :
                 decode_payload_regs<THREADS>(sh, stream + rd, avail - rd, avail - rd, block_len, out + wr, &end_bits, hint,
-                                             [&]() { return dfast_tables_from_tree<THREADS, true, true>(sh, tree, tl) ? (uni32(sh.l2n) != 0u ? 2 : 1) : 0; });
+                                             [&]() { return dfast_tables_from_tree<THREADS, true, true>(sh, tree, tl) ? (uni32(sh.l2n) != 0u ? 2 : 1) : 0; }, 2);
             bool done = lean == DREG_OK;
             if (lean == DREG_NO_TABLES) {
                 int leaf = -1;

@@ -33,7 +33,7 @@ for wl in [a for a in sys.argv[1:] if a != "--raw"] or ["zipf255", "uniform256"]
         data = torch.empty(n, dtype=torch.uint8, device="cuda"); c.fill(data, wl)
     out, offs, length = c.encode(data, bs)
     back = torch.empty(n, dtype=torch.uint8, device="cuda"); nb = c.block_count(n, bs)
-    arr = (C.c_ulonglong * 16)()
+    arr = (C.c_ulonglong * 32)()
     c.lib.hufgpu_debug_dfast(arr, 1)
     if raw: c.decode_stream(out, length, length, back, relaxed=True)
     else: c.decode(out, length, offs, nb, back, relaxed=True)
