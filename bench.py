@@ -2,14 +2,20 @@
 """Benchmark of the Huffman block-codec hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload zipf255|uniform256|const41|uniform255|logtext]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one encode + one decode of the rank's shard (default 1 GiB, 64 KiB blocks) with
 the input already resident in HBM.  The headline workload is `zipf255` (BASELINE.json configs[2]:
 text-like bytes, every block a full 255-symbol tree; the unmodified reference can decode it, so it
-is the workload the CPU baseline is timed on); `uniform256` (configs[3], per-GPU share) and
-`const41` (configs[1], the degenerate one-symbol tree) run in the same process with the same K/W
-and are reported under "secondary" of the same JSON line.
+is the workload the CPU baseline is timed on).
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps of the
+headline workload (per-kernel HIP events on every PROFILE_EVERY-th of them), checks the round trip,
+writes --dump-outputs and prints the line.  With --full the same process then measures everything else:
+`uniform256` (configs[3], per-GPU share) and `const41` (configs[1], the degenerate one-symbol tree)
+with the same K/W under "secondary", the same step with the block index alone, the other decoders,
+the copy / read / fill ceilings, the size all-gather on its own and `root_placement` (more than one
+rank), the Python layer and the C API by input size, live counter passes and the CPU baseline.
 
 N > 1: one rank per GPU.  Either the driver starts the ranks (torch.distributed.run sets
 WORLD_SIZE), or `python bench.py --gpus N` alone starts them itself - as a child process, before
@@ -17,14 +23,14 @@ this process touches a GPU - and relays rank 0's line.  Blocks are independent, 
 a contiguous range of blocks of the one logical input (weak scaling: bytes per GPU are fixed) and
 the timed step needs ONE exchange: the all-gather of the per-rank compressed sizes that places each
 rank's stream in the job's stream (RCCL, 8 bytes per rank).  Beside that resident-data figure
-(`value`), "root_placement" times the form north_star words: the input scattered from rank 0 over
+(`value`), "root_placement" (--full) times the form north_star words: the input scattered from rank 0 over
 xGMI, encoded, the compressed shards gathered on rank 0, scattered again, decoded, and the output
 gathered on rank 0.
 
 Prints ONE JSON line on rank 0.  `value` = uncompressed bytes of the whole job per second of
 (encode + decode), in GiB/s.  `roofline` is the dominant kernel's algorithmic HBM bytes over
-its HIP-event-measured duration inside the timed region; `cpu_baseline` is the unmodified
-reference library (oracle/_ref) timed on this box's host CPU on a bounded sample.
+its HIP-event-measured duration inside the timed region; `cpu_baseline` (--full) is the unmodified
+reference library (oracle/_ref) timed on the host CPU on a bounded sample.
 """
 from __future__ import annotations
 
@@ -509,20 +515,22 @@ class Bench:
 
         per_rank_ms, allgather_ms = None, None
         if self.use_dist:
-            # every rank's own clock over the K steps (the value uses the slowest), and what the step's one collective -
-            # the all-gather of the compressed sizes - costs on its own (K of them back to back, after the timed region)
+            # every rank's own clock over the K steps (the value uses the slowest), and (--full) what the step's one
+            # collective - the all-gather of the compressed sizes - costs on its own (K of them back to back, after the
+            # timed region)
             mine = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             every = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(world)]
             dist.all_gather(every, mine)
             per_rank_ms = [round(float(t.item()) / steps * 1e3, 4) for t in every]
             elapsed = max(float(t.item()) for t in every)
-            torch.cuda.synchronize()
-            dist.barrier()
-            t1 = time.perf_counter()
-            for _ in range(steps):
-                dist.all_gather_into_tensor(sizes[0], snaps[0])
-            torch.cuda.synchronize()
-            allgather_ms = round((time.perf_counter() - t1) / steps * 1e3, 4)
+            if a.full:
+                torch.cuda.synchronize()
+                dist.barrier()
+                t1 = time.perf_counter()
+                for _ in range(steps):
+                    dist.all_gather_into_tensor(sizes[0], snaps[0])
+                torch.cuda.synchronize()
+                allgather_ms = round((time.perf_counter() - t1) / steps * 1e3, 4)
 
         comp_len = int(offs[nb].item())
         bit_exact = None
@@ -536,7 +544,7 @@ class Bench:
         # the other decoder on the same stream, outside the timed region: what a stream without the
         # encoder's sub-index costs (and the other way round)
         other_ms = None
-        if rank == 0 and use_sub and other_decode and not a.no_other_decode:
+        if rank == 0 and use_sub and other_decode and a.full and not a.no_other_decode:
             codec.set_profiling(True)
             for _ in range(3):
                 codec.decode(out, out.numel(), offs, nb, back, relaxed=relaxed, sync=False)
@@ -548,7 +556,7 @@ class Bench:
         # ... and with no index at all (what huf_decode() gets: block discovery + probes), wall clock
         # of the call, outside the timed region; reported with the index-free record only
         raw_ms = None
-        if rank == 0 and not use_sub and not a.no_other_decode:
+        if rank == 0 and not use_sub and a.full and not a.no_other_decode:
             codec.decode_stream(out, comp_len, comp_len, back, relaxed=relaxed)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -625,6 +633,7 @@ class Bench:
             }
             if per_rank_ms is not None:
                 rec["per_rank_ms_per_step"] = per_rank_ms
+            if allgather_ms is not None:
                 rec["size_allgather_ms"] = allgather_ms
             if raw_ms is not None:
                 rec["raw_stream_decode"] = {"ms": round(raw_ms, 4), "GiBps": round(n / GIB / (raw_ms / 1e3), 1),
@@ -924,14 +933,14 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="zipf255", choices=sorted(WORKLOADS))
     ap.add_argument("--secondary", default=None,
-                    help="comma-separated workloads reported under 'secondary' (default: uniform256,const41 "
+                    help="with --full: comma-separated workloads reported under 'secondary' (default: uniform256,const41 "
                          "beside zipf255; 'none' = only the headline workload)")
     ap.add_argument("--decode", default="sub", choices=["sub", "selfsync"],
                     help="sub = with the encoder's sub-index (verified on the device); selfsync = block index only")
     ap.add_argument("--bytes-per-gpu", type=int, default=1 << 30)
     ap.add_argument("--blocksize", type=int, default=None, help="default 64 KiB (1 MiB for logtext)")
     ap.add_argument("--placement", default="auto", choices=["auto", "resident", "root"],
-                    help="root = also time the scatter/gather form (default when more than one rank runs)")
+                    help="with --full, root = also time the scatter/gather form (default when more than one rank runs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-other-decode", action="store_true")
@@ -942,12 +951,20 @@ def main() -> None:
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the headline workload's last timed step returned (rank 0's shard) as DIR/stream.npy, "
                          "DIR/offsets.npy and DIR/decoded.npy; arrays over 16 MiB as a fixed, seeded sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, measure everything else in the same process: secondary workloads, the "
+                         "index-alone step, the other decoders, ceilings, root placement, the host API figures, live counter "
+                         "passes, the CPU baseline (the --no-* options and --secondary leave parts out)")
     if len(sys.argv) == 4 and sys.argv[1] == "--cpu-all-cores-child":
         cpu_all_cores_child(sys.argv[2], int(sys.argv[3]))
         return
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full and args.secondary not in (None, "none"):
+        ap.error("--secondary needs --full: a plain run times the headline workload alone")
+    if not args.full and args.placement == "root":
+        ap.error("--placement root needs --full: a plain run times the headline workload alone")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -987,7 +1004,9 @@ def main() -> None:
 
     codec = GpuCodec(local_rank)
     bench = Bench(args, torch, dist, codec, rank, world, local_rank, use_dist, ctl_group=end_group)
-    if args.secondary is None:
+    if not args.full:
+        secondary = []
+    elif args.secondary is None:
         secondary = DEFAULT_SECONDARY.get(args.workload, [])
     else:
         secondary = [w for w in args.secondary.split(",") if w and w != "none"]
@@ -999,7 +1018,7 @@ def main() -> None:
     sec_recs = {w: bench.run(w, args.steps, args.warmup) for w in secondary}
     # the same K steps with the BLOCK INDEX ALONE (no sub-index: what a stream that comes without the
     # encoder's side information costs) - a timed region of its own, so that the driver's record holds both
-    if args.decode == "sub" and not args.no_index_free:
+    if args.full and args.decode == "sub" and not args.no_index_free:
         sec_recs[args.workload + "_index_free"] = bench.run(args.workload, args.steps, args.warmup, decode="selfsync",
                                                            other_decode=False)
     # BASELINE.json configs[3] is 16 GiB of uniform bytes over 8 GPUs: at world 8 that is 2 GiB per rank
@@ -1009,13 +1028,13 @@ def main() -> None:
         if rank == 0:
             sec_recs["uniform256_16GiB"]["config"]["workload"] = \
                 "configs[3]: 16 GiB uniform-random bytes (uniform256 seed 1), blocksize=64KiB, sharded across 8 MI355X"
-    ceil = bench.ceilings(1 << 30) if rank == 0 else None
+    ceil = bench.ceilings(1 << 30) if rank == 0 and args.full else None
     copy_gbs = ceil["copy"][0] if ceil else None
     # The scatter/gather form is an extra figure.  Every movement in it is waited for with a deadline
     # (BENCH_LEG_TIMEOUT), so a rank that fails alone shows as an exception here, not as a hang: the line is
     # then printed without the figure and the ranks leave without the final barrier.
     root_rec, root_ok = None, True
-    if use_dist and args.placement in ("auto", "root"):
+    if args.full and use_dist and args.placement in ("auto", "root"):
         try:
             root_rec = bench.root_placement(args.workload, max(2, min(args.steps, 5)))
         except Exception as e:                      # the extra figure never takes the headline down with it
@@ -1025,7 +1044,7 @@ def main() -> None:
         input size.  With more than one rank they run AFTER the other ranks have left, over every GPU of the node
         (HUF_GPU_DEVICES=all: one huffmanfile call dealt out over the sessions - configs[4]'s stated route)."""
         py, capi = None, None
-        if args.no_python_layer:
+        if not args.full or args.no_python_layer:
             return py, capi
         try:
             n_py = 1 << 30
@@ -1073,16 +1092,17 @@ def main() -> None:
             "data": "synthetic",
         }
         result.update({k: v for k, v in main_rec.items() if k not in ("value", "ms_per_step")})
-        result["secondary"] = {
-            w: {"value": r["value"], "ms_per_step": r["ms_per_step"], "workload": r["config"]["workload"],
-                "ratio": r["config"]["ratio"], "bit_exact_roundtrip": r["config"]["bit_exact_roundtrip"],
-                "roofline": {"kernel": r["roofline"]["kernel"], "frac": r["roofline"]["frac"],
-                             "achieved": r["roofline"]["achieved"], "traffic": r["roofline"]["traffic"],
-                             "traffic_source": (STAMP_SOURCE if r["roofline"]["traffic"] is not None else None),
-                             "pipeline_frac": r["roofline"]["pipeline_frac"]},
-                "kernels": {k: v["avg_ms"] for k, v in r["kernels"].items()},
-                **({"raw_stream_decode": r["raw_stream_decode"]} if "raw_stream_decode" in r else {})}
-            for w, r in sec_recs.items()}
+        if args.full:
+            result["secondary"] = {
+                w: {"value": r["value"], "ms_per_step": r["ms_per_step"], "workload": r["config"]["workload"],
+                    "ratio": r["config"]["ratio"], "bit_exact_roundtrip": r["config"]["bit_exact_roundtrip"],
+                    "roofline": {"kernel": r["roofline"]["kernel"], "frac": r["roofline"]["frac"],
+                                 "achieved": r["roofline"]["achieved"], "traffic": r["roofline"]["traffic"],
+                                 "traffic_source": (STAMP_SOURCE if r["roofline"]["traffic"] is not None else None),
+                                 "pipeline_frac": r["roofline"]["pipeline_frac"]},
+                    "kernels": {k: v["avg_ms"] for k, v in r["kernels"].items()},
+                    **({"raw_stream_decode": r["raw_stream_decode"]} if "raw_stream_decode" in r else {})}
+                for w, r in sec_recs.items()}
         # the reference's OWN boundary (src/decoder.c:201-287 takes the stream and nothing else): encode + the decode of a
         # stream that comes with no index at all, against the same 8 TB/s
         idx_rec = sec_recs.get(args.workload + "_index_free")
@@ -1103,7 +1123,7 @@ def main() -> None:
         if capi_rec is not None:
             result["secondary"]["c_api_memstream"] = capi_rec
         result["roofline"]["traffic_source"] = STAMP_SOURCE if result["roofline"].get("traffic") is not None else None
-        if world == 1 and not args.no_live_traffic:
+        if args.full and world == 1 and not args.no_live_traffic:
             same = ["--bytes-per-gpu", str(args.bytes_per_gpu), "--decode", args.decode]
             if args.blocksize is not None:
                 same += ["--blocksize", str(args.blocksize)]
@@ -1150,18 +1170,19 @@ def main() -> None:
                     idx = result["secondary"][args.workload + "_index_free"]["roofline"]
                     if idx.get("kernel") == "decode_fast_kernel":          # the live count in the record it belongs to, not the stamp
                         idx["traffic"], idx["traffic_source"] = li["decode_fast_kernel"], live_src
-        result["roofline"]["copy_ceiling_GBps"] = round(copy_gbs, 1)
-        result["roofline"]["read_ceiling_GBps"] = round(ceil["read"][0], 1)
-        result["roofline"]["write_ceiling_GBps"] = round(ceil["fill"][0], 1)
-        result["roofline"]["torch_copy_GBps"] = round(ceil["torch_copy"][0], 1)
-        result["roofline"]["ceiling_source"] = ("hufgpu_calib_bandwidth: hand-written 16-byte-per-lane copy / read / fill kernels "
-                                                "(kernels/fill.hpp), best of %d shapes each over 1 GiB: variants %d / %d / %d"
-                                                % (bench.codec.CALIB_VARIANTS, ceil["copy"][1], ceil["read"][1], ceil["fill"][1]))
-        result["roofline"]["frac_of_copy_ceiling"] = round(result["roofline"]["achieved"] / copy_gbs, 4)
+        if ceil is not None:
+            result["roofline"]["copy_ceiling_GBps"] = round(copy_gbs, 1)
+            result["roofline"]["read_ceiling_GBps"] = round(ceil["read"][0], 1)
+            result["roofline"]["write_ceiling_GBps"] = round(ceil["fill"][0], 1)
+            result["roofline"]["torch_copy_GBps"] = round(ceil["torch_copy"][0], 1)
+            result["roofline"]["ceiling_source"] = ("hufgpu_calib_bandwidth: hand-written 16-byte-per-lane copy / read / fill kernels "
+                                                    "(kernels/fill.hpp), best of %d shapes each over 1 GiB: variants %d / %d / %d"
+                                                    % (bench.codec.CALIB_VARIANTS, ceil["copy"][1], ceil["read"][1], ceil["fill"][1]))
+            result["roofline"]["frac_of_copy_ceiling"] = round(result["roofline"]["achieved"] / copy_gbs, 4)
         if world > 1:
-            result["multi_gpu_note"] = ("ranks are block-sharded; value = all ranks' bytes over the slowest rank's time; "
-                                        "cpu_baseline is rank 0's host")
-        if not args.no_cpu_baseline:
+            result["multi_gpu_note"] = ("ranks are block-sharded; value = all ranks' bytes over the slowest rank's time"
+                                        + ("; cpu_baseline is rank 0's host" if args.full else ""))
+        if args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args.workload, bs)
             try:                                         # the reference on the sizes of secondary.c_api_memstream (bounded: up to 64 MiB)
                 import ctypes

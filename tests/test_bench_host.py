@@ -3,7 +3,7 @@
 The figure is counted in the run itself (two child passes under `rocprofv3 --pmc`, bench.live_traffic) and falls
 back to the table of profiles/traffic.json, which is only believed when it was collected for exactly the kernel
 sources of the tree (bench.measured_traffic).  The GPU side of it: tests/test_gpu_parity.py
-(test_bench_counts_the_longest_kernels_traffic_in_its_own_run)."""
+(test_full_bench_counts_the_longest_kernels_traffic_in_its_own_run)."""
 import json
 import os
 import stat
@@ -85,6 +85,16 @@ def test_counter_passes_are_read_per_launch_of_the_named_kernel(clean_env, tmp_p
     got = bench.live_traffic("zipf255", ["decode_sub_kernel", "pack_kernel", "no_such_kernel"], ["--bytes-per-gpu", str(1 << 28)])
     assert got == {"decode_sub_kernel": 1000 * 1024 * 2 + 500 * 1024, "pack_kernel": 99999 * 1024 * 3}
     assert bench.live_traffic("zipf255", ["no_such_kernel"]) is None
+
+
+@pytest.mark.parametrize("extra", [["--secondary", "const41"], ["--placement", "root"]])
+def test_figures_beside_the_headline_are_asked_for_with_full(extra):
+    """a plain run times the headline workload alone: asking it for another figure is an error before any GPU work, not a
+    line that quietly lacks the figure"""
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1"] + extra,
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert out.returncode == 2 and "needs --full" in out.stderr and not out.stdout, out.stderr[-2000:]
 
 
 @pytest.mark.parametrize("case,world,want", [("all_good", 3, True), ("one_fails", 3, False), ("one_missing", 2, False)])

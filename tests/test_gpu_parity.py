@@ -944,7 +944,7 @@ def test_full_size_stream_equals_oracle_stream(torch_mod, codec, oracle, kind, b
     assert int(offs_h[nb]) == length
 
 
-def test_bench_runs_over_rccl_with_one_rank(torch_mod):
+def test_full_bench_runs_over_rccl_with_one_rank(torch_mod):
     """bench.py's distributed path on this one GPU: nccl init, the size all-gather inside the timed
     step, the root-placement legs (variable-size all-to-alls).  N > 1 runs only on the driver's
     8-GPU node; this pins everything but the second rank."""
@@ -954,7 +954,7 @@ def test_bench_runs_over_rccl_with_one_rank(torch_mod):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29577")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",
-                          "--bytes-per-gpu", str(64 << 20), "--secondary", "const41", "--no-cpu-baseline", "--no-live-traffic"],
+                          "--bytes-per-gpu", str(64 << 20), "--secondary", "const41", "--no-cpu-baseline", "--no-live-traffic", "--full"],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -968,7 +968,7 @@ def test_bench_runs_over_rccl_with_one_rank(torch_mod):
     assert set(rp["legs_ms_rank0"]) >= {"scatter_in", "encode", "gather_stream", "scatter_stream", "decode", "gather_out"}
 
 
-def test_bench_configs3_share_over_rccl_with_one_rank(torch_mod):
+def test_full_bench_configs3_share_over_rccl_with_one_rank(torch_mod):
     """BASELINE configs[3] is 16 GiB of uniform bytes over 8 GPUs = 2 GiB per rank: that share - its allocations (2 GiB
     in, 2.3 GiB of stream bound, the sub-index, 2 GiB out), 32 768 blocks of k = 256 in relaxed-tree mode - over RCCL with
     the one rank this box has, per-rank times and the size all-gather's cost in the record."""
@@ -979,7 +979,7 @@ def test_bench_configs3_share_over_rccl_with_one_rank(torch_mod):
     env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29579")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "uniform256",
                           "--bytes-per-gpu", str(2 << 30), "--secondary", "none", "--no-cpu-baseline", "--no-live-traffic",
-                          "--no-index-free", "--no-python-layer", "--no-other-decode", "--placement", "resident"],
+                          "--no-index-free", "--no-python-layer", "--no-other-decode", "--placement", "resident", "--full"],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -988,8 +988,8 @@ def test_bench_configs3_share_over_rccl_with_one_rank(torch_mod):
     assert len(d["per_rank_ms_per_step"]) == 1 and d["size_allgather_ms"] >= 0
 
 
-def test_bench_counts_the_longest_kernels_traffic_in_its_own_run(torch_mod):
-    """roofline.traffic of the default bench line is counted in the run itself (two rocprofv3 --pmc child passes of
+def test_full_bench_counts_the_longest_kernels_traffic_in_its_own_run(torch_mod):
+    """roofline.traffic of the full bench line is counted in the run itself (two rocprofv3 --pmc child passes of
     the same command), not taken from a table: between the algorithmic bytes and 1.3 times them for the kernels the
     step is made of."""
     import json
@@ -1000,7 +1000,7 @@ def test_bench_counts_the_longest_kernels_traffic_in_its_own_run(torch_mod):
         pytest.skip("no rocprofv3 here")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--secondary", "none",
-                          "--no-cpu-baseline", "--no-index-free", "--no-python-layer", "--no-other-decode"],
+                          "--no-cpu-baseline", "--no-index-free", "--no-python-layer", "--no-other-decode", "--full"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -1031,6 +1031,27 @@ def test_bench_dumps_what_its_last_timed_step_returned(torch_mod, oracle, tmp_pa
     assert got["stream"].dtype == np.float32 and np.array_equal(got["stream"], want)
     assert got["offsets"].dtype == np.float64 and np.array_equal(got["offsets"], want_offs.astype(np.float64))
     assert got["decoded"].dtype == np.float32 and np.array_equal(got["decoded"], data)
+
+
+def test_a_plain_bench_run_times_the_headline_alone(torch_mod):
+    """Without --full the line carries the headline figure and what its timed steps measured (per-kernel HIP events, the
+    round trip) and nothing that takes work of its own: no secondary workloads, other decoders, ceilings, counter passes
+    or CPU baseline."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1",
+                          "--bytes-per-gpu", str(64 << 20)],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["metric"] == "encode+decode GiB/s (uncompressed) on 64KiB blocks" and d["unit"] == "GiB/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "u8" and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["config"]["bytes_per_gpu"] == 64 << 20
+    assert d["config"]["bit_exact_roundtrip"] is True and {"pack", "decode"} <= set(d["kernels"])
+    assert not {"secondary", "cpu_baseline", "kernel_traffic", "kernel_valu", "root_placement"} & set(d), sorted(d)
+    assert "decode_selfsync" not in d["kernels"] and "copy_ceiling_GBps" not in d["roofline"]
 
 
 @pytest.mark.parametrize("top", [17, 24])

@@ -6,7 +6,7 @@
 # 2. HBM traffic per kernel launch from the TCC counters, separate --pmc passes (FETCH_SIZE doubled:
 #    the gfx950 correction of MI355X_MICROARCH.md) -> traffic.json, stamped with the kernel sources' digest
 # 3. SQ counters of every kernel on zipf255 (two --pmc passes) -> <tag>_pmc_zipf255.txt
-# 4. the default bench command with no profiler attached -> <tag>_final_bench.json
+# 4. the full bench command with no profiler attached -> <tag>_final_bench.json
 TAG=${1:-r02}
 shift
 WLS=${@:-zipf255 uniform256 const41}
@@ -29,7 +29,7 @@ rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/rd_index -o rd -- python3
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/wr_index -o wr -- python3 $ROOT/bench.py --steps 3 --warmup 1 --workload zipf255 --decode selfsync $COMMON --no-verify > $OUT/wr_index.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $OUT/sq1 -o p1 -- python3 $ROOT/bench.py --steps 3 --warmup 1 --workload zipf255 $COMMON --no-verify > $OUT/sq1.log 2>&1
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_WAIT_ANY --output-format csv -d $OUT/sq2 -o p2 -- python3 $ROOT/bench.py --steps 3 --warmup 1 --workload zipf255 $COMMON --no-verify > $OUT/sq2.log 2>&1
-python3 $ROOT/bench.py > $OUT/${TAG}_final_bench.json 2> $OUT/final.err
+python3 $ROOT/bench.py --full > $OUT/${TAG}_final_bench.json 2> $OUT/final.err
 cd $ROOT
 python3 - <<PY
 import csv, glob, collections, json, sys
