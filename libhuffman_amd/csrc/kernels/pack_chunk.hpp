@@ -288,7 +288,9 @@ __device__ __forceinline__ void pack_segment(const uint8_t *__restrict__ src, ui
                 base += (uintptr_t)(moved >> 3);
                 tile_org -= moved;
                 bitpos = end_bits - moved;
-                own_lo = own_hi;
+                /* never back: a part that ends inside the word of the chunk's first byte (a chunk of a few symbols)
+                 * stored nothing, and that word's bytes in front of own_lo are the previous chunk's */
+                own_lo = dmax<uintptr_t>(own_lo, own_hi);
                 __syncthreads();
             }
         }

@@ -258,9 +258,11 @@ def test_encode_deep_codes(torch_mod, codec, oracle):
 
 
 def test_blocks_of_4_mib_and_more(torch_mod, codec, oracle):
-    """Blocks >= 4 MiB take the unfused kernels (hist256 -> tree with 64-bit keys -> scan_sizes ->
-    pack): several such blocks, a one-symbol block among them, a ragged tail; and the block sizes
-    just below the switch and around the 16-bit counter limit of the fused kernel (128 KiB)."""
+    """Blocks >= 4 MiB are counted in 256 KiB chunks, get trees with 64-bit keys (tree_kernel), the
+    index from scan_sizes and are packed chunk by chunk (pack_chunk_kernel): several such blocks, a
+    one-symbol block among them, a ragged tail.  4 MiB - 1 takes the same chunks with the 32-bit
+    tree_wave_kernel; 128 KiB and 128 KiB + 1 take hist_lanes -> tree_wave -> the full pack_kernel
+    (the fused kernel serves only blocks below 32 KiB)."""
     torch = torch_mod
     for bs in ((5 << 20) + 3, 4 << 20, (4 << 20) - 1, 131072, 131073):
         nblk = 3 if bs >= (4 << 20) - 1 else 5
