@@ -124,6 +124,59 @@ int hufgpu_decode_sub(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_l
                       uint64_t *raw_len, void *stream);
 
 /*
+ * BATCHES: many independent inputs in one launch sequence.  A call per input costs tens of microseconds of host API
+ * whatever the input holds; a batch encodes (decodes) every block of every input with the launches of one call.
+ * The inputs lie back to back in one device buffer: item i starts at the sum of the lengths in front of it, at any
+ * byte alignment.  Item lengths are a HOST array (the grid sizes depend on them); an item of length 0 has no blocks
+ * and an empty stream (src/encoder.c:288).  Blocks are independent and every header stores its own block_len, so
+ * the items' streams back to back are ONE valid stream: hufgpu_decode() of the whole of it gives the inputs back to
+ * back.  Host arrays may be reused as soon as a call returns.  There is no CPU path: the two batch calls need a
+ * context; hufgpu_batch_geometry() is plain arithmetic and works without a GPU.
+ *
+ *   hufgpu_batch_geometry : for nitems lengths and a blocksize as in hufgpu_encode() (0 = every item is one block):
+ *                           *nblocks = the sum of hufgpu_block_count(len_i, blocksize), *row_blocksize = the longest
+ *                           block, min(blocksize or infinity, max len_i), *out_bound = the sum of
+ *                           hufgpu_encode_bound(len_i, blocksize), *sub_index_bytes = the size of a batch sub-index:
+ *                           nblocks rows laid out like hufgpu_sub_index_bytes(), each sized for row_blocksize symbols.
+ *                           Outputs may be NULL; item_lens may be NULL only for nitems = 0.
+ *   hufgpu_encode_batch   : item i's stream d_out[o[i], o[i+1]) is byte for byte what hufgpu_encode() writes for that
+ *                           item alone with the same blocksize.  d_block_offsets (optional, nblocks + 1 words): the
+ *                           concatenation of the items' own block indexes, each shifted to its absolute place in d_out
+ *                           (the last word = the batch's length).  d_item_offsets (optional, nitems + 1 words) and
+ *                           item_offsets (optional HOST array, nitems + 1): o[].  With item_offsets the call
+ *                           synchronises; without it, it only enqueues (two such calls back to back on one context are
+ *                           safe: the tables are staged per call).  d_sub_index (optional, 8-byte aligned,
+ *                           sub_index_bytes): block b's row holds the entries hufgpu_encode_sub() writes for that block
+ *                           when its item is encoded alone - the rows are laid out by (nblocks, row_blocksize) instead
+ *                           of (n, blocksize).  Blocks of HUFGPU_BATCH_CHUNKED_FROM (2 MiB) and more (row_blocksize >= it)
+ *                           are encoded item by item, one synchronisation per item, with the same output; such a
+ *                           batch takes no sub-index: a non-NULL d_sub_index returns HUF_ERROR_INVALID_ARGUMENT.
+ *   hufgpu_decode_batch   : item i = blocks [item_blocks[i], item_blocks[i+1]) of the stream (item_blocks[0] = 0, host,
+ *                           non-decreasing), its slot = d_out[out_offsets[i], out_offsets[i+1]) (host, non-decreasing).
+ *                           item_errs[i], item_raw_lens[i] and the bytes of the slot are what
+ *                             hufgpu_decode(ctx, d_stream, stream_len, d_block_offsets + item_blocks[i],
+ *                                           item_blocks[i+1] - item_blocks[i], d_out + out_offsets[i],
+ *                                           out_offsets[i+1] - out_offsets[i], flags, &raw, ...)
+ *                           returns: the reference's partial delivery from a failing block, HUF_ERROR_MEMORY_ALLOCATION
+ *                           for a slot that is too small.  A damaged or oversized item never moves, shortens or corrupts
+ *                           another item's output, and bytes of d_out outside the decoded bytes of every slot are never
+ *                           written.  d_sub_index / row_blocksize (optional): from the batch encode; the results are
+ *                           those of the same call without them for ANY content of the buffer (as hufgpu_decode_sub()).
+ *                           Synchronous.  Returns HUF_ERROR_SUCCESS when every item decoded, else the error of the
+ *                           first failing item in item order.  Argument errors return before anything is enqueued.
+ */
+#define HUFGPU_BATCH_CHUNKED_FROM ((uint64_t)1 << 21)   /* = HUF_CHUNKED_FROM: row_blocksize from here on goes item by item, no sub-index */
+int hufgpu_batch_geometry(uint64_t nitems, const uint64_t *item_lens, uint64_t blocksize, uint64_t *nblocks,
+                          uint64_t *row_blocksize, uint64_t *out_bound, uint64_t *sub_index_bytes);
+int hufgpu_encode_batch(hufgpu_ctx_t *ctx, const void *d_in, uint64_t nitems, const uint64_t *item_lens,
+                        uint64_t blocksize, void *d_out, uint64_t out_cap, uint64_t *d_block_offsets,
+                        uint64_t *d_item_offsets, void *d_sub_index, uint64_t *item_offsets, void *stream);
+int hufgpu_decode_batch(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                        uint64_t nitems, const uint64_t *item_blocks, const uint64_t *out_offsets,
+                        const void *d_sub_index, uint64_t row_blocksize, void *d_out, uint32_t flags,
+                        int32_t *item_errs, uint64_t *item_raw_lens, void *stream);
+
+/*
  * One logical input over the GPUs of a node: RCCL scatter / gather of block buffers.
  * Blocks are independent (src/encoder.c:288-374 resets all state between blocks), so rank r of G owns a contiguous range
  * of ceil(nblocks / G) blocks (hufgpu_shard_range) and the codec needs no collective; the data starts and ends on ONE

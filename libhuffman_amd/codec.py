@@ -28,6 +28,49 @@ class HuffmanGpuError(RuntimeError):
         super().__init__(msg)
 
 
+class EncodedBatch:
+    """What GpuCodec.encode_batch returns: the stream of many items back to back and where everything lies in it.
+
+    stream        : uint8 device view of the whole stream (the items' streams back to back - one valid stream)
+    offsets       : int64 device tensor, nblocks + 1 block header offsets in `stream` (the last = its length)
+    item_blocks   : host list, nitems + 1: item i = blocks [item_blocks[i], item_blocks[i + 1])
+    item_offsets  : host list, nitems + 1: item i = stream[item_offsets[i]:item_offsets[i + 1]]
+    item_lens     : host list of the items' raw lengths, or None when not known (batch_from_streams without them)
+    blocksize, row_blocksize, sub_index (int64 device tensor or None: the batch sub-index)
+    """
+
+    def __init__(self, stream, offsets, item_blocks, item_offsets, item_lens, blocksize, row_blocksize, sub_index=None):
+        self.stream = stream
+        self.offsets = offsets
+        self.item_blocks = list(item_blocks)
+        self.item_offsets = list(item_offsets)
+        self.item_lens = None if item_lens is None else list(item_lens)
+        self.blocksize = blocksize
+        self.row_blocksize = row_blocksize
+        self.sub_index = sub_index
+
+    @property
+    def nitems(self) -> int:
+        return len(self.item_blocks) - 1
+
+    @property
+    def nblocks(self) -> int:
+        return self.item_blocks[-1]
+
+    @property
+    def stream_len(self) -> int:
+        return self.item_offsets[-1]
+
+    def item_stream(self, i: int) -> torch.Tensor:
+        """View of item i's stream: what GpuCodec.encode writes for the item alone."""
+        return self.stream[self.item_offsets[i]: self.item_offsets[i + 1]]
+
+
+def _u64_array(values):
+    values = [int(v) for v in values]
+    return (C.c_uint64 * max(1, len(values)))(*values)
+
+
 class GpuCodec:
     """One codec context per device. Not thread-safe (like the reference's objects)."""
 
@@ -141,6 +184,89 @@ class GpuCodec:
         finally:
             self._pending_decode = None
         return int(raw.value)
+
+    # -- batches: many independent inputs in one launch sequence -----------------------------
+    def batch_geometry(self, item_lens, blocksize: int):
+        """(nblocks, row_blocksize, out_bound, sub_index_bytes) of a batch (hufgpu_batch_geometry)."""
+        lens = _u64_array(item_lens)
+        nb, rbs, bound, subb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.hufgpu_batch_geometry(len(item_lens), lens, blocksize, C.byref(nb), C.byref(rbs),
+                                                   C.byref(bound), C.byref(subb)), "batch geometry failed")
+        return int(nb.value), int(rbs.value), int(bound.value), int(subb.value)
+
+    def encode_batch(self, data: torch.Tensor, item_lens, blocksize: int, sub_index: bool = False) -> EncodedBatch:
+        """Encode the items that lie back to back in `data` (item i = the item_lens[i] bytes behind the ones before it),
+        each as hufgpu_encode would encode it alone, in one launch sequence.  Synchronises."""
+        assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
+        item_lens = [int(x) for x in item_lens]
+        if sum(item_lens) != data.numel():
+            raise ValueError(f"the item lengths add up to {sum(item_lens)} bytes, the data holds {data.numel()}")
+        nb, rbs, bound, subb = self.batch_geometry(item_lens, blocksize)
+        out = torch.empty(max(1, bound), dtype=torch.uint8, device=self.tdev)
+        offsets = torch.empty(nb + 1, dtype=torch.int64, device=self.tdev)
+        sub = torch.empty(max(1, (subb + 7) // 8), dtype=torch.int64, device=self.tdev) if sub_index else None
+        item_offs = (C.c_uint64 * (len(item_lens) + 1))()
+        err = self.lib.hufgpu_encode_batch(self._ctx, data.data_ptr() if data.numel() else None, len(item_lens),
+                                           _u64_array(item_lens), blocksize, out.data_ptr(), out.numel(),
+                                           offsets.data_ptr(), None, sub.data_ptr() if sub is not None else None,
+                                           item_offs, self._stream())
+        self._check(err, "Failed to encode the batch")
+        item_blocks = [0]
+        for n in item_lens:
+            item_blocks.append(item_blocks[-1] + self.block_count(n, blocksize))
+        item_offsets = list(item_offs)
+        return EncodedBatch(out[: item_offsets[-1]], offsets, item_blocks, item_offsets, item_lens, blocksize, rbs, sub)
+
+    def decode_batch(self, batch: EncodedBatch, out: torch.Tensor | None = None, out_offsets=None, relaxed: bool = False):
+        """Decode every item of `batch` into its slot out[out_offsets[i]:out_offsets[i + 1]] (default: the item lengths
+        back to back).  Returns (out, errs, raw_lens): per item the error and the bytes delivered that hufgpu_decode of
+        the item alone into its slot returns - per-item errors are returned, not raised."""
+        n = batch.nitems
+        if out_offsets is None:
+            if batch.item_lens is None:
+                raise ValueError("the batch does not know its item lengths: pass out_offsets")
+            out_offsets = [0]
+            for x in batch.item_lens:
+                out_offsets.append(out_offsets[-1] + x)
+        out_offsets = [int(x) for x in out_offsets]
+        assert len(out_offsets) == n + 1
+        if out is None:
+            out = torch.empty(max(1, out_offsets[-1]), dtype=torch.uint8, device=self.tdev)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.numel() >= out_offsets[-1]
+        errs = (C.c_int32 * max(1, n))()
+        raws = (C.c_uint64 * max(1, n))()
+        flags = _native.RELAXED_TREE if relaxed else _native.STRICT_TREE
+        sub = batch.sub_index
+        err = self.lib.hufgpu_decode_batch(self._ctx, batch.stream.data_ptr() if batch.stream.numel() else None,
+                                           batch.stream_len, batch.offsets.data_ptr(), n, _u64_array(batch.item_blocks),
+                                           _u64_array(out_offsets), sub.data_ptr() if sub is not None else None,
+                                           batch.row_blocksize if sub is not None else 0, out.data_ptr(), flags,
+                                           errs, raws, self._stream())
+        if err == _native.HUF_ERROR_INVALID_ARGUMENT or err == _native.HUF_ERROR_FATAL:
+            self._check(err, "Failed to decode the batch")
+        return out, [int(errs[i]) for i in range(n)], [int(raws[i]) for i in range(n)]
+
+    def batch_from_streams(self, items) -> EncodedBatch:
+        """A batch for decode_batch from streams encoded one by one: items = [(stream, offsets) or
+        (stream, offsets, raw_len), ...], stream = a uint8 device tensor of exactly the stream's bytes, offsets = its
+        block index (nblocks + 1 int64, as encode returns it).  The streams are copied back to back and the indexes
+        shifted to match.  Without raw lengths decode_batch needs out_offsets."""
+        streams, offs, item_blocks, item_offsets, lens = [], [], [0], [0], []
+        for it in items:
+            stream, offsets = it[0], it[1]
+            lens.append(int(it[2]) if len(it) > 2 else None)
+            assert stream.dtype == torch.uint8
+            o = offsets.to(device=self.tdev, dtype=torch.int64)
+            if o.numel() == 0:
+                o = torch.zeros(1, dtype=torch.int64, device=self.tdev)
+            offs.append(o[:-1] + item_offsets[-1])
+            streams.append(stream.to(self.tdev).reshape(-1))
+            item_blocks.append(item_blocks[-1] + o.numel() - 1)
+            item_offsets.append(item_offsets[-1] + stream.numel())
+        offs.append(torch.tensor([item_offsets[-1]], dtype=torch.int64, device=self.tdev))
+        stream = torch.cat(streams) if streams else torch.empty(0, dtype=torch.uint8, device=self.tdev)
+        known = all(x is not None for x in lens)
+        return EncodedBatch(stream, torch.cat(offs), item_blocks, item_offsets, lens if known else None, None, 0)
 
     CALIB_VARIANTS = 8
 

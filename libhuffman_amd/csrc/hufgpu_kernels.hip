@@ -35,3 +35,4 @@
 #include "kernels/spec_index.hpp"
 #include "kernels/discover.hpp"
 #include "kernels/fill.hpp"
+#include "kernels/batch.hpp"

@@ -32,29 +32,32 @@ namespace hufgpu {
  * last array, which lies behind the 7 KiB TreeLds: 8 KiB per workgroup = 20 resident groups per
  * CU instead of 13, and the latency-bound tree waves are what the kernel waits for on
  * multi-symbol data (uniform bytes 0.68 -> 0.60 ms, Zipf 0.77 -> 0.71 ms per GiB). */
+/* LDS layout of the fused kernel (the kernels declare it; hist_tree_block works in it) */
 template <int THREADS, bool PACKED>
-__global__ __launch_bounds__(THREADS) void hist_tree_kernel(const uint8_t *__restrict__ in, uint64_t n,
-                                                            uint64_t blocksize, hufcode_t *__restrict__ codetab,
-                                                            int16_t *__restrict__ treebuf,
-                                                            HufBlockMeta *__restrict__ meta, TwoLevel sizes)
-{
-    constexpr int WAVES = THREADS / 64;
-    constexpr int COPIES = WAVES * (PACKED ? HTP_ARRAYS : HT_COPIES);   /* 256-word arrays */
-    constexpr size_t HBYTES = (size_t)COPIES * HUF_NSYM * sizeof(uint32_t);
-    constexpr size_t TBYTES = HUF_NSYM * sizeof(uint32_t);
+struct HistTreeLds {
+    static constexpr int WAVES = THREADS / 64;
+    static constexpr int COPIES = WAVES * (PACKED ? HTP_ARRAYS : HT_COPIES);   /* 256-word arrays */
+    static constexpr size_t HBYTES = (size_t)COPIES * HUF_NSYM * sizeof(uint32_t);
+    static constexpr size_t TBYTES = HUF_NSYM * sizeof(uint32_t);
     /* totals: the last histogram array when that lies behind the tree's area (summed in place:
      * a thread reads and writes only its own bin there), else right behind the tree's area */
-    constexpr size_t TOT_OFF = (HBYTES >= sizeof(TreeLds) + TBYTES) ? HBYTES - TBYTES : sizeof(TreeLds);
-    constexpr size_t UBYTES = (HBYTES > TOT_OFF + TBYTES) ? HBYTES : TOT_OFF + TBYTES;
+    static constexpr size_t TOT_OFF = (HBYTES >= sizeof(TreeLds) + TBYTES) ? HBYTES - TBYTES : sizeof(TreeLds);
+    static constexpr size_t UBYTES = (HBYTES > TOT_OFF + TBYTES) ? HBYTES : TOT_OFF + TBYTES;
     static_assert(TOT_OFF >= sizeof(TreeLds) && TOT_OFF % 16 == 0, "totals must survive the tree's initialisation");
-    __shared__ __attribute__((aligned(16))) uint8_t s_union[UBYTES];
-    __shared__ uint32_t s_side[2 * THREADS];   /* a lane's counts of its wave's two most frequent bytes (see below) */
+};
+
+/* The body of hist_tree_kernel for block blk = the `len` bytes at `p` (also hist_tree_batch_kernel's, batch.hpp).
+ * s_union: HistTreeLds::UBYTES, s_side: 2 * THREADS words. */
+template <int THREADS, bool PACKED>
+__device__ __forceinline__ void hist_tree_block(const uint8_t *__restrict__ p, uint64_t len, uint64_t blk,
+                                                hufcode_t *__restrict__ codetab, int16_t *__restrict__ treebuf,
+                                                HufBlockMeta *__restrict__ meta, const TwoLevel &sizes,
+                                                uint8_t *s_union, uint32_t *s_side)
+{
+    constexpr int COPIES = HistTreeLds<THREADS, PACKED>::COPIES;
+    constexpr size_t TOT_OFF = HistTreeLds<THREADS, PACKED>::TOT_OFF;
     uint32_t *s_hist = reinterpret_cast<uint32_t *>(s_union);
     uint32_t *s_tot = reinterpret_cast<uint32_t *>(s_union + TOT_OFF);
-
-    const uint64_t blk = blockIdx.x;
-    const uint64_t base = blk * blocksize;
-    const uint64_t len = dmin<uint64_t>(blocksize, n - base);
     const int tid = (int)threadIdx.x;
 
     for (int i = tid; i < COPIES * HUF_NSYM; i += THREADS) s_hist[i] = 0;
@@ -78,7 +81,6 @@ __global__ __launch_bounds__(THREADS) void hist_tree_kernel(const uint8_t *__res
         mine = s_hist + ((tid >> 6) * HT_COPIES + arr) * HUF_NSYM;
     }
     auto rotated = [rot4](uint4 v) { return make_uint4(v.x ^ rot4, v.y ^ rot4, v.z ^ rot4, v.w ^ rot4); };
-    const uint8_t *p = in + base;
     const uint64_t head = dmin<uint64_t>(len, (16u - (uint32_t)((uintptr_t)p & 15u)) & 15u);
     if ((uint64_t)tid < head) atomicAdd(&mine[p[tid] ^ rot], one);
     const uint4 *q = reinterpret_cast<const uint4 *>(p + head);
@@ -165,6 +167,20 @@ __global__ __launch_bounds__(THREADS) void hist_tree_kernel(const uint8_t *__res
     const uint64_t bytes = tree_fast_wave(rate, *reinterpret_cast<TreeLds *>(s_union), blk, codetab, treebuf, meta);
     /* stream offsets (the reference's running file position): summed here, see two_level_arrive */
     two_level_arrive(sizes, blk, gridDim.x, bytes);
+}
+
+template <int THREADS, bool PACKED>
+__global__ __launch_bounds__(THREADS) void hist_tree_kernel(const uint8_t *__restrict__ in, uint64_t n,
+                                                            uint64_t blocksize, hufcode_t *__restrict__ codetab,
+                                                            int16_t *__restrict__ treebuf,
+                                                            HufBlockMeta *__restrict__ meta, TwoLevel sizes)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_union[HistTreeLds<THREADS, PACKED>::UBYTES];
+    __shared__ uint32_t s_side[2 * THREADS];   /* a lane's counts of its wave's two most frequent bytes (see hist_tree_block) */
+    const uint64_t blk = blockIdx.x;
+    const uint64_t base = blk * blocksize;
+    const uint64_t len = dmin<uint64_t>(blocksize, n - base);
+    hist_tree_block<THREADS, PACKED>(in + base, len, blk, codetab, treebuf, meta, sizes, s_union, s_side);
 }
 
 }  // namespace hufgpu

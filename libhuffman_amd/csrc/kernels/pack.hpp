@@ -621,6 +621,56 @@ __device__ __forceinline__ void pack_block_multi(const uint8_t *__restrict__ src
 
 #undef PACK_REQUEST
 
+/* The body of pack_kernel for block blk = the `len` bytes at `src` (also pack_batch_kernel's, batch.hpp): the writer
+ * by the block's longest code, the index entry, the sub-index rows.  s_*: the kernel's LDS (see pack_kernel). */
+template <int THREADS, bool SHORT>
+__device__ __forceinline__ void pack_block_any(const uint8_t *__restrict__ src, uint64_t len, uint64_t blk,
+                                               const hufcode_t *__restrict__ codetab,
+                                               const int16_t *__restrict__ treebuf,
+                                               const HufBlockMeta *__restrict__ meta,
+                                               uint64_t *__restrict__ offsets, const TwoLevel &sizes,
+                                               uint8_t *__restrict__ out, const HufSubIndex &sub,
+                                               hufcode_t *s_code, uint32_t *s_part, uint32_t *s_tail, uint32_t *s_stage)
+{
+    const HufBlockMeta m = meta[blk];
+    const hufcode_t *codes = codetab + blk * HUF_NSYM;
+    const int16_t *tb = treebuf + blk * HUF_TREE_STRIDE;
+    uint64_t o0, o1;
+    if (sizes.local) {                   /* sizes were summed by hist_tree_kernel: publish the index entry */
+        o0 = sizes.gprefix[blk / SCAN_GROUP] + sizes.local[blk];
+        o1 = o0 + encoded_block_bytes(m);
+        if (threadIdx.x == 0) offsets[blk] = o0;
+    } else {
+        o0 = offsets[blk];
+        o1 = offsets[blk + 1];
+    }
+    uint64_t *sub_tiles = sub.tile_bits ? sub.tile_bits + blk * sub.tpb : nullptr;
+    uint16_t *sub_groups = sub.tile_bits ? sub.group_bits + blk * sub.gpb : nullptr;
+    if (sub.tile_bits && m.tree_len != 5)
+        for (int i = (int)threadIdx.x; i < HUF_NSYM; i += THREADS) sub.lens[blk * HUF_NSYM + i] = (uint8_t)(codes[i] & 0xffu);
+#if !defined(PACK_ACC64)   /* (-DPACK_ACC64 = round 2's kernel, tests/test_isa_check.py) */
+    if (m.max_len <= 10)                 /* three codes per push */
+        pack_block_multi<THREADS, 3>(src, len, codes, tb, m.tree_len, out, o0, o1,
+                                     reinterpret_cast<uint2 *>(s_code), s_part, s_tail, s_stage, sub_tiles, sub_groups);
+    else if (m.max_len <= 15)            /* two codes per push (at most 30 bits) */
+        pack_block_multi<THREADS, 2>(src, len, codes, tb, m.tree_len, out, o0, o1,
+                                     reinterpret_cast<uint2 *>(s_code), s_part, s_tail, s_stage, sub_tiles, sub_groups);
+#else
+    if (m.max_len <= 10)
+        pack_block<THREADS, uint32_t, 3>(src, len, codes, tb, m.tree_len, out, o0, o1,
+                                         reinterpret_cast<uint32_t *>(s_code), s_part, s_tail, s_stage, sub_tiles, sub_groups);
+    else if (m.max_len <= 15)
+        pack_block<THREADS, uint32_t, 2>(src, len, codes, tb, m.tree_len, out, o0, o1,
+                                            reinterpret_cast<uint32_t *>(s_code), s_part, s_tail, s_stage, sub_tiles, sub_groups);
+#endif
+    else if (SHORT || m.max_len <= 24)
+        pack_block<THREADS, uint32_t>(src, len, codes, tb, m.tree_len, out, o0, o1,
+                                      reinterpret_cast<uint32_t *>(s_code), s_part, s_tail, s_stage, sub_tiles, sub_groups);
+    else if constexpr (!SHORT)
+        pack_block<THREADS, hufcode_t>(src, len, codes, tb, m.tree_len, out, o0, o1,
+                                       s_code, s_part, s_tail, s_stage, sub_tiles, sub_groups);
+}
+
 /* SHORT = true: the host guarantees that no code of this launch is longer than 24 bits (any
  * Huffman merge order on n <= 121392 symbols gives depth <= 23, plus the wrap-root bit; the
  * deepest tree needs Fibonacci weights), so only the 32-bit code path is compiled - fewer
@@ -655,43 +705,8 @@ __global__ __launch_bounds__(THREADS, SHORT ? PACK_WAVES_PER_SIMD : 4) void pack
     const uint64_t blk = blockIdx.x;
     const uint64_t base = blk * blocksize;
     const uint64_t len = dmin<uint64_t>(blocksize, n - base);
-    const HufBlockMeta m = meta[blk];
-    const hufcode_t *codes = codetab + blk * HUF_NSYM;
-    const int16_t *tb = treebuf + blk * HUF_TREE_STRIDE;
-    uint64_t o0, o1;
-    if (sizes.local) {                   /* sizes were summed by hist_tree_kernel: publish the index entry */
-        o0 = sizes.gprefix[blk / SCAN_GROUP] + sizes.local[blk];
-        o1 = o0 + encoded_block_bytes(m);
-        if (threadIdx.x == 0) offsets[blk] = o0;
-    } else {
-        o0 = offsets[blk];
-        o1 = offsets[blk + 1];
-    }
-    uint64_t *sub_tiles = sub.tile_bits ? sub.tile_bits + blk * sub.tpb : nullptr;
-    uint16_t *sub_groups = sub.tile_bits ? sub.group_bits + blk * sub.gpb : nullptr;
-    if (sub.tile_bits && m.tree_len != 5)
-        for (int i = (int)threadIdx.x; i < HUF_NSYM; i += THREADS) sub.lens[blk * HUF_NSYM + i] = (uint8_t)(codes[i] & 0xffu);
-#if !defined(PACK_ACC64)   /* (-DPACK_ACC64 = round 2's kernel, tests/test_isa_check.py) */
-    if (m.max_len <= 10)                 /* three codes per push */
-        pack_block_multi<THREADS, 3>(in + base, len, codes, tb, m.tree_len, out, o0, o1,
-                                     reinterpret_cast<uint2 *>(s_code), s_part, s_tail, s_stage, sub_tiles, sub_groups);
-    else if (m.max_len <= 15)            /* two codes per push (at most 30 bits) */
-        pack_block_multi<THREADS, 2>(in + base, len, codes, tb, m.tree_len, out, o0, o1,
-                                     reinterpret_cast<uint2 *>(s_code), s_part, s_tail, s_stage, sub_tiles, sub_groups);
-#else
-    if (m.max_len <= 10)
-        pack_block<THREADS, uint32_t, 3>(in + base, len, codes, tb, m.tree_len, out, o0, o1,
-                                         reinterpret_cast<uint32_t *>(s_code), s_part, s_tail, s_stage, sub_tiles, sub_groups);
-    else if (m.max_len <= 15)
-        pack_block<THREADS, uint32_t, 2>(in + base, len, codes, tb, m.tree_len, out, o0, o1,
-                                            reinterpret_cast<uint32_t *>(s_code), s_part, s_tail, s_stage, sub_tiles, sub_groups);
-#endif
-    else if (SHORT || m.max_len <= 24)
-        pack_block<THREADS, uint32_t>(in + base, len, codes, tb, m.tree_len, out, o0, o1,
-                                      reinterpret_cast<uint32_t *>(s_code), s_part, s_tail, s_stage, sub_tiles, sub_groups);
-    else if constexpr (!SHORT)
-        pack_block<THREADS, hufcode_t>(in + base, len, codes, tb, m.tree_len, out, o0, o1,
-                                       s_code, s_part, s_tail, s_stage, sub_tiles, sub_groups);
+    pack_block_any<THREADS, SHORT>(in + base, len, blk, codetab, treebuf, meta, offsets, sizes, out, sub,
+                                   s_code, s_part, s_tail, s_stage);
 }
 
 }  // namespace hufgpu
