@@ -177,6 +177,54 @@ int hufgpu_decode_batch(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream
                         int32_t *item_errs, uint64_t *item_raw_lens, void *stream);
 
 /*
+ * RANGES: bytes [lo, hi) of the original data out of one indexed stream, many ranges in one launch sequence.  A call costs
+ * tens of microseconds whatever it carries; fetching ten thousand records out of a compressed column is one call.
+ * Raw positions are positions in what hufgpu_decode() of the whole stream delivers: block b covers [P[b], P[b+1]), P = the
+ * exclusive sums of the block_len header fields.  No blocksize is assumed, so an index from hufgpu_block_index(), the
+ * stream of a batch (short last blocks per item) and a hand-made stream all work; a range's first and last block are
+ * found on the device by binary search in P.  Blocks are independent, positions inside a block are not: the blocks at
+ * a range's edges are decoded WHOLE (a start inside a block cannot be verified without decoding what lies in front of
+ * it), so with the reference's blocksize = 0 - one block - a range costs a full decode.  There is no CPU path.
+ *
+ *   range i         : [range_lo[i], range_hi[i]), lo <= hi (host arrays).  Ranges may overlap, repeat and come in any
+ *                     order.  Its slot is d_out[out_offsets[i], out_offsets[i+1]) (host, nranges + 1, non-decreasing).
+ *                     A range that reaches past the end of the data is cut there: range_raw_lens[i] says so, with
+ *                     HUF_ERROR_SUCCESS (a read at the end of a file).  A slot shorter than the cut range gives that
+ *                     range HUF_ERROR_MEMORY_ALLOCATION and nothing is written into it.
+ *   what is decoded : only blocks that a range touches.  Damage in the PAYLOAD of an untouched block is never seen.  A
+ *                     HEADER that does not parse (what hufgpu_decode() reports for the block before it looks at the
+ *                     payload) hides the positions of everything behind it: a range that ends in front of the first
+ *                     such block is served, every other range fails with that header's error and delivers the bytes
+ *                     it has in front of that block.
+ *   per range       : range_errs[i] = the error of the first failing touched block in stream order, range_raw_lens[i]
+ *                     = the range's bytes in front of that block plus, for HUF_ERROR_READ_WRITE / _BTREE_CORRUPTED,
+ *                     the part of what src/decoder.c:69-91 delivers of the failing block (decoded once more, in
+ *                     order, its record as the whole input) that lies inside the range.  A failing range never moves,
+ *                     shortens or corrupts another range's slot.  Nothing outside the first (cut length) bytes of
+ *                     the slots is ever written; inside a FAILING range's slot, what lies behind the delivered bytes
+ *                     is unspecified (as behind *raw_len of hufgpu_decode()).
+ *   routing         : a block that lies wholly inside exactly one range and is touched by no other is decoded straight
+ *                     into that slot.  Every other touched block - a cut edge, a block several ranges share - is
+ *                     decoded once into a scratch area of the context (staged blocks x the longest of them; when it
+ *                     cannot grow the call returns HUF_ERROR_MEMORY_ALLOCATION) and its pieces are copied to the slots.
+ *   d_sub_index     : optional, with (raw_size, blocksize) as in hufgpu_decode_sub() (they must give nblocks blocks):
+ *                     the touched blocks are decoded with the encoder's sub-index, verified as ever - the results are
+ *                     those of the same call without it for ANY content of the buffer.  NULL: raw_size and blocksize
+ *                     are not looked at.
+ * Synchronous.  Returns HUF_ERROR_SUCCESS or the error of the first failing range in range order.  Argument errors
+ * (lo > hi, decreasing out_offsets, NULL host arrays, a misaligned or mis-sized sub-index, no context) return
+ * HUF_ERROR_INVALID_ARGUMENT before anything is enqueued; nranges = 0 is success.  hufgpu_decode_counters() after the
+ * call counts the blocks of this call that went to the exact decoder.
+ */
+int hufgpu_decode_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                         const uint64_t *d_block_offsets, uint64_t nblocks,
+                         uint64_t nranges, const uint64_t *range_lo, const uint64_t *range_hi,
+                         const uint64_t *out_offsets,
+                         const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                         void *d_out, uint32_t flags,
+                         int32_t *range_errs, uint64_t *range_raw_lens, void *stream);
+
+/*
  * One logical input over the GPUs of a node: RCCL scatter / gather of block buffers.
  * Blocks are independent (src/encoder.c:288-374 resets all state between blocks), so rank r of G owns a contiguous range
  * of ceil(nblocks / G) blocks (hufgpu_shard_range) and the codec needs no collective; the data starts and ends on ONE
@@ -246,7 +294,7 @@ int hufgpu_decode_small(hufgpu_ctx_t *ctx, const void *h_in_pinned, uint64_t ava
                         void *d_in, void *d_out, uint64_t out_cap, void *h_out_pinned, uint64_t h_out_cap,
                         uint64_t *raw_len, uint64_t *consumed);
 
-/* Of the last enqueued hufgpu_decode() / hufgpu_decode_sub(): blocks that went through a slower decoder -
+/* Of the last enqueued hufgpu_decode() / hufgpu_decode_sub(), or the last hufgpu_decode_ranges(): blocks that went through a slower decoder -
  * counters[0] = decoded again by the exact in-order-equivalent decoder (a damaged block, an unusual tree, a stale
  * sub-index), counters[1] = 0 (reserved: it counted the blocks round 4's one-pass decoder handed on).
  * Results never depend on these; they say what a slow decode was slow for.  Synchronises the stream. */

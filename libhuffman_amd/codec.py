@@ -268,6 +268,49 @@ class GpuCodec:
         known = all(x is not None for x in lens)
         return EncodedBatch(stream, torch.cat(offs), item_blocks, item_offsets, lens if known else None, None, 0)
 
+    # -- ranges: bytes [lo, hi) of the original data out of one indexed stream --------------------
+    def decode_ranges(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, ranges,
+                      out: torch.Tensor | None = None, out_offsets=None, relaxed: bool = False,
+                      sub_index: torch.Tensor | None = None, raw_size: int = 0, blocksize: int = 0):
+        """Decode the byte ranges `ranges` = [(lo, hi), ...] of the original data, range i into its slot
+        out[out_offsets[i]:out_offsets[i + 1]] (default: the range lengths back to back), in one launch sequence
+        (hufgpu_decode_ranges).  Only the blocks a range touches are decoded.  Returns (out, errs, raw_lens): per range
+        the error and the bytes delivered - per-range errors are returned, not raised."""
+        ranges = [(int(lo), int(hi)) for lo, hi in ranges]
+        n = len(ranges)
+        if out_offsets is None:
+            out_offsets = [0]
+            for lo, hi in ranges:
+                out_offsets.append(out_offsets[-1] + max(0, hi - lo))
+        out_offsets = [int(x) for x in out_offsets]
+        assert len(out_offsets) == n + 1
+        if out is None:
+            out = torch.empty(max(1, out_offsets[-1]), dtype=torch.uint8, device=self.tdev)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.numel() >= out_offsets[-1]
+        errs = (C.c_int32 * max(1, n))()
+        raws = (C.c_uint64 * max(1, n))()
+        flags = _native.RELAXED_TREE if relaxed else _native.STRICT_TREE
+        err = self.lib.hufgpu_decode_ranges(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
+                                            offsets.data_ptr(), nblocks, n, _u64_array(lo for lo, _ in ranges),
+                                            _u64_array(hi for _, hi in ranges), _u64_array(out_offsets),
+                                            sub_index.data_ptr() if sub_index is not None else None,
+                                            raw_size if sub_index is not None else 0,
+                                            blocksize if sub_index is not None else 0, out.data_ptr(), flags,
+                                            errs, raws, self._stream())
+        if err == _native.HUF_ERROR_INVALID_ARGUMENT or err == _native.HUF_ERROR_FATAL:
+            self._check(err, "Failed to decode the ranges")
+        return out, [int(errs[i]) for i in range(n)], [int(raws[i]) for i in range(n)]
+
+    def decode_range(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, lo: int, hi: int,
+                     relaxed: bool = False, sub_index: torch.Tensor | None = None, raw_size: int = 0,
+                     blocksize: int = 0) -> torch.Tensor:
+        """The bytes [lo, hi) of the original data (cut at its end) as a new tensor.  Raises HuffmanGpuError, with the
+        bytes delivered in front of the failure in `.raw`, when a block of the range does not decode."""
+        out, errs, raws = self.decode_ranges(stream, stream_len, offsets, nblocks, [(lo, hi)], relaxed=relaxed,
+                                             sub_index=sub_index, raw_size=raw_size, blocksize=blocksize)
+        self._check(errs[0], "Failed to decode the range", raw=raws[0])
+        return out[: raws[0]]
+
     CALIB_VARIANTS = 8
 
     def calib_bandwidth(self, kind: str, variant: int, a: torch.Tensor | None, b: torch.Tensor | None, nbytes: int):

@@ -36,3 +36,4 @@
 #include "kernels/discover.hpp"
 #include "kernels/fill.hpp"
 #include "kernels/batch.hpp"
+#include "kernels/ranges.hpp"
