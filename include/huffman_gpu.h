@@ -225,6 +225,49 @@ int hufgpu_decode_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t strea
                          int32_t *range_errs, uint64_t *range_raw_lens, void *stream);
 
 /*
+ * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from
+ * another rank, or encoded here by a caller that did not keep the 7 % of side data.  hufgpu_encode_sub() writes the
+ * sub-index as a by-product of packing; these three rebuild exactly that - the same entries, entry for entry
+ * (kernels/sub_build.hpp) - from the stream, its block index and the decoded bytes, so that hufgpu_decode_sub() and
+ * hufgpu_decode_ranges(..., d_sub_index, ...) decode the stream at their fast rate from then on.
+ *
+ * (raw_size, blocksize) are those of the encode that wrote the stream, exactly as hufgpu_decode_sub() takes them: they
+ * fix the block count and the layout.  d_sub_index: hufgpu_sub_index_bytes(raw_size, blocksize) bytes of device memory,
+ * 8-byte aligned; what the encoder never writes there (one-symbol blocks, padding, entries behind a short last block)
+ * these calls never write either.  flags: HUFGPU_RELAXED_TREE as for hufgpu_decode().
+ *
+ * A block is UNBUILT when its header or tree does not parse under `flags`, its header's length is not the layout's, a
+ * byte of its data has no code in its tree, or its code lengths do not add up to the payload the index gives it (and,
+ * for the two calls that decode, when it did not decode).  *unbuilt counts such blocks; their rows hold whatever they
+ * held, or stale entries.  That costs time, never correctness: the decoders verify every entry they use and decode an
+ * unverifiable block the slow way.  Trees of any shape are taken - every byte value on at most one leaf, codes of 1 to
+ * 255 bits; a block with codes over 32 bits gets its entries like any other (hufgpu_decode_sub sends it to the exact
+ * decoder by design).
+ *
+ * Argument errors - no context, a NULL stream or index, a missing or misaligned sub-index - return
+ * HUF_ERROR_INVALID_ARGUMENT before anything is enqueued; raw_size = 0 is success.
+ *
+ * hufgpu_sub_index_from_raw: the caller holds the decoded data (raw_size bytes at d_raw, any alignment; nothing behind
+ *   them is read).  One launch sequence; with unbuilt = NULL it only enqueues.
+ * hufgpu_decode_build_sub: hufgpu_decode() - its results, errors and delivered bytes, unchanged, raw_len = NULL enqueues
+ *   and hufgpu_decode_result() reports as usual - and the sub-index from the output it has just written.  After a
+ *   decode error the rows of the blocks that did not decode are unbuilt and counted.
+ * hufgpu_build_sub_index: no output buffer is wanted - the blocks are decoded into a scratch area of the context (128 MiB
+ *   of whole blocks at a time, at least one block; HUF_ERROR_MEMORY_ALLOCATION when it cannot be had) and indexed from
+ *   there.  Synchronous.  A pending hufgpu_decode() of the context is forgotten.
+ */
+int hufgpu_sub_index_from_raw(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                              const uint64_t *d_block_offsets, const void *d_raw, uint64_t raw_size,
+                              uint64_t blocksize, void *d_sub_index, uint32_t flags, uint64_t *unbuilt, void *stream);
+int hufgpu_decode_build_sub(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                            const uint64_t *d_block_offsets, uint64_t raw_size, uint64_t blocksize,
+                            void *d_out, uint64_t out_cap, void *d_sub_index, uint32_t flags,
+                            uint64_t *raw_len, uint64_t *unbuilt, void *stream);
+int hufgpu_build_sub_index(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                           const uint64_t *d_block_offsets, uint64_t raw_size, uint64_t blocksize,
+                           void *d_sub_index, uint32_t flags, uint64_t *unbuilt, void *stream);
+
+/*
  * One logical input over the GPUs of a node: RCCL scatter / gather of block buffers.
  * Blocks are independent (src/encoder.c:288-374 resets all state between blocks), so rank r of G owns a contiguous range
  * of ceil(nblocks / G) blocks (hufgpu_shard_range) and the codec needs no collective; the data starts and ends on ONE

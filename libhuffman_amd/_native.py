@@ -70,7 +70,8 @@ hufgpu_get_profile hufgpu_sub_index_bytes hufgpu_encode_sub hufgpu_decode_sub
 hufgpu_decode_stream_complete hufgpu_block_index hufgpu_decode_counters hufgpu_calib_bandwidth hufgpu_encode_small hufgpu_decode_small huf_gpu_set_relaxed_tree huf_gpu_memwrap huf_gpu_memwrap_out huf_gpu_decode_blocks huf_gpu_sessions huf_gpu_fanouts huf_gpu_copy_out
 hufgpu_ctx_device hufgpu_shard_unique_id hufgpu_shard_create hufgpu_shard_destroy hufgpu_shard_info hufgpu_shard_last_error
 hufgpu_shard_range hufgpu_shard_plan_decode hufgpu_encode_sharded hufgpu_decode_sharded hufgpu_shard_set_timeout
-hufgpu_batch_geometry hufgpu_encode_batch hufgpu_decode_batch hufgpu_decode_ranges""".split()
+hufgpu_batch_geometry hufgpu_encode_batch hufgpu_decode_batch hufgpu_decode_ranges
+hufgpu_sub_index_from_raw hufgpu_decode_build_sub hufgpu_build_sub_index""".split()
 
 
 def so_path() -> str:
@@ -165,6 +166,9 @@ def load() -> C.CDLL:
     L.hufgpu_decode_ranges.restype = C.c_int
     L.hufgpu_decode_ranges.argtypes = [vp, vp, u64, vp, u64, u64, P64, P64, P64, vp, u64, u64, vp, C.c_uint32,
                                        C.POINTER(C.c_int32), P64, vp]
+    L.hufgpu_sub_index_from_raw.argtypes = [vp, vp, u64, vp, vp, u64, u64, vp, C.c_uint32, P64, vp]
+    L.hufgpu_decode_build_sub.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, vp, C.c_uint32, P64, P64, vp]
+    L.hufgpu_build_sub_index.argtypes = [vp, vp, u64, vp, u64, u64, vp, C.c_uint32, P64, vp]
     _LIB = L
     return L
 

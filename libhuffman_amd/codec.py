@@ -311,6 +311,47 @@ class GpuCodec:
         self._check(errs[0], "Failed to decode the range", raw=raws[0])
         return out[: raws[0]]
 
+    # -- the sub-index of a stream that came without one -------------------------------------------
+    def build_sub_index(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, raw_size: int, blocksize: int,
+                        raw: torch.Tensor | None = None, sub_index: torch.Tensor | None = None, relaxed: bool = False):
+        """The sub-index hufgpu_encode_sub would have written for `stream` (raw_size bytes encoded in blocks of
+        `blocksize`), rebuilt from the stream and its block index: from the decoded data when the caller holds it
+        (`raw`: hufgpu_sub_index_from_raw), else by decoding slabs of blocks into scratch memory
+        (hufgpu_build_sub_index).  Returns (sub_index, unbuilt): the tensor for decode(..., sub_index=) and
+        decode_ranges(..., sub_index=), and the blocks whose rows could not be built (they decode the slow way)."""
+        if sub_index is None:
+            sub_index = self.new_sub_index(raw_size, blocksize)
+        assert sub_index.numel() * sub_index.element_size() >= self.sub_index_bytes(raw_size, blocksize)
+        unbuilt = C.c_uint64(0)
+        flags = _native.RELAXED_TREE if relaxed else _native.STRICT_TREE
+        sp = stream.data_ptr() if stream.numel() else None
+        if raw is not None:
+            assert raw.dtype == torch.uint8 and raw.is_cuda and raw.is_contiguous() and raw.numel() >= raw_size
+            err = self.lib.hufgpu_sub_index_from_raw(self._ctx, sp, stream_len, offsets.data_ptr(), raw.data_ptr(), raw_size,
+                                                     blocksize, sub_index.data_ptr(), flags, C.byref(unbuilt), self._stream())
+        else:
+            err = self.lib.hufgpu_build_sub_index(self._ctx, sp, stream_len, offsets.data_ptr(), raw_size, blocksize,
+                                                  sub_index.data_ptr(), flags, C.byref(unbuilt), self._stream())
+            self._pending_decode = None
+        self._check(err, "Failed to build the sub-index")
+        return sub_index, int(unbuilt.value)
+
+    def decode_build_sub(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, out: torch.Tensor, raw_size: int,
+                         blocksize: int, sub_index: torch.Tensor | None = None, relaxed: bool = False):
+        """decode() - same result, same HuffmanGpuError with the delivered bytes in `.raw` - that also builds the
+        stream's sub-index from the output it writes (hufgpu_decode_build_sub).  Returns (raw_len, sub_index, unbuilt)."""
+        if sub_index is None:
+            sub_index = self.new_sub_index(raw_size, blocksize)
+        assert sub_index.numel() * sub_index.element_size() >= self.sub_index_bytes(raw_size, blocksize)
+        raw, unbuilt = C.c_uint64(0), C.c_uint64(0)
+        flags = _native.RELAXED_TREE if relaxed else _native.STRICT_TREE
+        err = self.lib.hufgpu_decode_build_sub(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
+                                               offsets.data_ptr(), raw_size, blocksize, out.data_ptr(), out.numel(),
+                                               sub_index.data_ptr(), flags, C.byref(raw), C.byref(unbuilt), self._stream())
+        self._pending_decode = None
+        self._check(err, "Failed to decode the data", raw=int(raw.value))
+        return int(raw.value), sub_index, int(unbuilt.value)
+
     CALIB_VARIANTS = 8
 
     def calib_bandwidth(self, kind: str, variant: int, a: torch.Tensor | None, b: torch.Tensor | None, nbytes: int):

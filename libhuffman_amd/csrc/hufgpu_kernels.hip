@@ -11,6 +11,8 @@
  *   decode:  decode_prepare_kernel -> decode_kernel (block index known)
  *            decode_prepare_kernel -> decode_sub_kernel -> decode_fix_kernel (block index and the
  *            encoder's sub-index known), or decode_chain_kernel (raw stream, blocks in order)
+ *   sub-index of a stream that came without one: sub_lens_kernel -> sub_groups_kernel (-> sub_chunk_scan_kernel ->
+ *            sub_tile_add_kernel for blocks of 2 MiB and more)
  *
  * Wave size is 64 throughout (hard-coded, gfx950 only).  All arithmetic is integer.
  */
@@ -37,3 +39,4 @@
 #include "kernels/fill.hpp"
 #include "kernels/batch.hpp"
 #include "kernels/ranges.hpp"
+#include "kernels/sub_build.hpp"
