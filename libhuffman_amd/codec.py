@@ -311,6 +311,60 @@ class GpuCodec:
         self._check(errs[0], "Failed to decode the range", raw=raws[0])
         return out[: raws[0]]
 
+    # -- overwrite: bytes [lo, hi) of the original data replaced in one indexed stream ---------------
+    def update_ranges(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, ranges,
+                      data: torch.Tensor, src_offsets=None, sub_index: torch.Tensor | None = None, raw_size: int = 0,
+                      blocksize: int = 0, out: torch.Tensor | None = None, want_sub_index: bool = False,
+                      relaxed: bool = False):
+        """Overwrite the byte ranges `ranges` = [(lo, hi), ...] of the original data with the bytes of `data`, range i
+        from data[src_offsets[i]:] (default: the ranges' bytes back to back), out of place (hufgpu_update_ranges).  Only
+        the blocks a range touches are encoded again.  `sub_index` is the OLD stream's (optional); `want_sub_index`
+        asks for the new stream's and needs (raw_size, blocksize).  Without `out` the output is sized from `blocksize`,
+        which must then be the length of the stream's longest block.  Returns (new stream view, its length, new offsets,
+        new sub-index or None, blocks re-encoded).  Raises HuffmanGpuError."""
+        ranges = [(int(lo), int(hi)) for lo, hi in ranges]
+        n = len(ranges)
+        assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
+        if src_offsets is not None:
+            src_offsets = [int(x) for x in src_offsets]
+            assert len(src_offsets) == n
+        if out is None:
+            # include/huffman_gpu.h: the old length + every touched block at its encode_bound always fits.  The block
+            # lengths are not known here, so both are bounded from above: a touched block holds a byte of a range (at
+            # most `grow` of them, and nblocks), and the touched blocks hold the ranges' bytes plus, per range, what two
+            # cut blocks of at most `blocksize` bytes hold besides.
+            if not blocksize:
+                raise ValueError("update_ranges sizes its output from `blocksize` (the longest block): pass it, or pass `out`")
+            grow = sum(max(0, hi - lo) for lo, hi in ranges)
+            touched = min(nblocks, grow)
+            per_block = self.encode_bound(1, 0)                        # header, the longest tree, padding
+            held = grow + 2 * n * blocksize
+            out = torch.empty(stream_len + touched * per_block + (9 * held + 7) // 8 + 64, dtype=torch.uint8, device=self.tdev)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous()
+        new_offsets = torch.empty(nblocks + 1, dtype=torch.int64, device=self.tdev)
+        new_sub = self.new_sub_index(raw_size, blocksize) if want_sub_index else None
+        out_len, count = C.c_uint64(0), C.c_uint64(0)
+        flags = _native.RELAXED_TREE if relaxed else _native.STRICT_TREE
+        with_layout = sub_index is not None or want_sub_index
+        err = self.lib.hufgpu_update_ranges(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
+                                            offsets.data_ptr(), nblocks, n, _u64_array(lo for lo, _ in ranges),
+                                            _u64_array(hi for _, hi in ranges),
+                                            _u64_array(src_offsets) if src_offsets is not None else None,
+                                            data.data_ptr() if data.numel() else None,
+                                            sub_index.data_ptr() if sub_index is not None else None,
+                                            raw_size if with_layout else 0, blocksize if with_layout else 0,
+                                            out.data_ptr(), out.numel(), new_offsets.data_ptr(),
+                                            new_sub.data_ptr() if new_sub is not None else None, flags,
+                                            C.byref(out_len), C.byref(count), self._stream())
+        self._pending_decode = None
+        self._check(err, "Failed to update the ranges")
+        return out[: out_len.value], int(out_len.value), new_offsets, new_sub, int(count.value)
+
+    def update_range(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, lo: int,
+                     data: torch.Tensor, **kwargs):
+        """update_ranges for the one range [lo, lo + data.numel())."""
+        return self.update_ranges(stream, stream_len, offsets, nblocks, [(lo, lo + data.numel())], data, **kwargs)
+
     # -- the sub-index of a stream that came without one -------------------------------------------
     def build_sub_index(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, raw_size: int, blocksize: int,
                         raw: torch.Tensor | None = None, sub_index: torch.Tensor | None = None, relaxed: bool = False):

@@ -13,6 +13,8 @@
  *            encoder's sub-index known), or decode_chain_kernel (raw stream, blocks in order)
  *   sub-index of a stream that came without one: sub_lens_kernel -> sub_groups_kernel (-> sub_chunk_scan_kernel ->
  *            sub_tile_add_kernel for blocks of 2 MiB and more)
+ *   overwrite of byte ranges: decode_prepare_kernel -> drange_plan / drange_mark -> upd_class -> the indexed decoders on
+ *            the staged blocks -> upd_overlay -> hist_*_pairs -> upd_index -> pack_pairs, update_copy_kernel
  *
  * Wave size is 64 throughout (hard-coded, gfx950 only).  All arithmetic is integer.
  */
@@ -40,3 +42,4 @@
 #include "kernels/batch.hpp"
 #include "kernels/ranges.hpp"
 #include "kernels/sub_build.hpp"
+#include "kernels/update.hpp"

@@ -622,9 +622,11 @@ __device__ __forceinline__ void pack_block_multi(const uint8_t *__restrict__ src
 #undef PACK_REQUEST
 
 /* The body of pack_kernel for block blk = the `len` bytes at `src` (also pack_batch_kernel's, batch.hpp): the writer
- * by the block's longest code, the index entry, the sub-index rows.  s_*: the kernel's LDS (see pack_kernel). */
+ * by the block's longest code, the index entry, the sub-index rows.  s_*: the kernel's LDS (see pack_kernel).
+ * `row` is where the block's code table, tree and meta lie, `blk` its number in the stream (index entry, sub-index
+ * rows): the same number everywhere but in pack_pairs_kernel (update.hpp), whose rows are a compact list of blocks. */
 template <int THREADS, bool SHORT>
-__device__ __forceinline__ void pack_block_any(const uint8_t *__restrict__ src, uint64_t len, uint64_t blk,
+__device__ __forceinline__ void pack_block_any(const uint8_t *__restrict__ src, uint64_t len, uint64_t row, uint64_t blk,
                                                const hufcode_t *__restrict__ codetab,
                                                const int16_t *__restrict__ treebuf,
                                                const HufBlockMeta *__restrict__ meta,
@@ -632,9 +634,9 @@ __device__ __forceinline__ void pack_block_any(const uint8_t *__restrict__ src, 
                                                uint8_t *__restrict__ out, const HufSubIndex &sub,
                                                hufcode_t *s_code, uint32_t *s_part, uint32_t *s_tail, uint32_t *s_stage)
 {
-    const HufBlockMeta m = meta[blk];
-    const hufcode_t *codes = codetab + blk * HUF_NSYM;
-    const int16_t *tb = treebuf + blk * HUF_TREE_STRIDE;
+    const HufBlockMeta m = meta[row];
+    const hufcode_t *codes = codetab + row * HUF_NSYM;
+    const int16_t *tb = treebuf + row * HUF_TREE_STRIDE;
     uint64_t o0, o1;
     if (sizes.local) {                   /* sizes were summed by hist_tree_kernel: publish the index entry */
         o0 = sizes.gprefix[blk / SCAN_GROUP] + sizes.local[blk];
@@ -669,6 +671,18 @@ __device__ __forceinline__ void pack_block_any(const uint8_t *__restrict__ src, 
     else if constexpr (!SHORT)
         pack_block<THREADS, hufcode_t>(src, len, codes, tb, m.tree_len, out, o0, o1,
                                        s_code, s_part, s_tail, s_stage, sub_tiles, sub_groups);
+}
+
+template <int THREADS, bool SHORT>
+__device__ __forceinline__ void pack_block_any(const uint8_t *__restrict__ src, uint64_t len, uint64_t blk,
+                                               const hufcode_t *__restrict__ codetab,
+                                               const int16_t *__restrict__ treebuf,
+                                               const HufBlockMeta *__restrict__ meta,
+                                               uint64_t *__restrict__ offsets, const TwoLevel &sizes,
+                                               uint8_t *__restrict__ out, const HufSubIndex &sub,
+                                               hufcode_t *s_code, uint32_t *s_part, uint32_t *s_tail, uint32_t *s_stage)
+{
+    pack_block_any<THREADS, SHORT>(src, len, blk, blk, codetab, treebuf, meta, offsets, sizes, out, sub, s_code, s_part, s_tail, s_stage);
 }
 
 /* SHORT = true: the host guarantees that no code of this launch is longer than 24 bits (any
