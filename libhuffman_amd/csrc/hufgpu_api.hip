@@ -1153,6 +1153,13 @@ extern "C" int hufgpu_debug_dfast(unsigned long long *out32, int reset)     /* D
     return (int)hipMemcpyFromSymbol(out32, HIP_SYMBOL(hufgpu::g_dfast_dbg), DFAST_DBG_SLOTS * sizeof(unsigned long long));
 }
 #endif
+#ifdef TREE_DEBUG
+extern "C" int hufgpu_debug_tree(unsigned long long *out, int reset)        /* TREE_DBG_SLOTS counters (kernels/tree.hpp) */
+{
+    if (reset) { unsigned long long z[TREE_DBG_SLOTS] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(hufgpu::g_tree_dbg), z, sizeof(z)); }
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(hufgpu::g_tree_dbg), TREE_DBG_SLOTS * sizeof(unsigned long long));
+}
+#endif
 
 extern "C" int hufgpu_block_index(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t avail, uint64_t length, uint32_t flags,
                                   const uint64_t **d_index, uint64_t *nblocks, uint64_t *consumed, void *stream)

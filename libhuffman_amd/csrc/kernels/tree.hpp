@@ -331,6 +331,33 @@ __device__ __forceinline__ uint64_t tree_state(uint32_t anc, uint32_t depth, uin
 #define TREE_ROUND_MIN 16u        /* items below a + b that make a sorted round cheaper than their single merges */
 #endif
 
+/* Counters of the debug build (-DTREE_DEBUG; tests/test_gpu_tree_cases.py): which way tree_fast_wave went, counted by
+ * lane 0 of the tree's wave (every condition counted is uniform).  "+ ri": by the register count R, ri = R >> 1 = 0, 1, 2
+ * for R = 1, 2, 4; "+ (R >> 2)": for R = 2, 4.  tests/tree_rounds_ref.py names the slots in this order. */
+#define TREE_DBG_SLOTS 36
+#define TREE_DBG_BLOCKS 0               /* + ri: blocks by R on entry (not the one-symbol ones) */
+#define TREE_DBG_ONE_SYMBOL 3           /* the one-symbol shortcut */
+#define TREE_DBG_ROUND_SORTED 4         /* + ri: sorted rounds that sorted */
+#define TREE_DBG_ROUND_IN_ORDER 7       /* + ri: sorted rounds that found the keys in order */
+#define TREE_DBG_SINGLE 10              /* + ri: single merges */
+#define TREE_DBG_R_4_2 13               /* a round changed R: 4 -> 2, */
+#define TREE_DBG_R_2_1 14               /*   2 -> 1, */
+#define TREE_DBG_R_4_1 15               /*   4 -> 1 */
+#define TREE_DBG_NODES_IN_ORDER 16      /* + (R >> 2), R the new one: the round's nodes found in order, */
+#define TREE_DBG_NODES_SORTED1 18       /*   sorted in one register, */
+#define TREE_DBG_NODES_SORTED2 20       /*   sorted in two, */
+#define TREE_DBG_NODES_CHANCE 22        /*   not looked at (new R = 1) */
+#define TREE_DBG_CHECK_PASS 23          /* + ri of the new R: the order check behind the merge passed, */
+#define TREE_DBG_CHECK_FAIL 26          /*   failed */
+#define TREE_DBG_WRAP_ROOT 29           /* the left-only wrap root */
+#define TREE_DBG_PATH_ROUNDS 30         /* + rounds - 1: path-doubling rounds a block took (1..6) */
+#ifdef TREE_DEBUG
+__device__ unsigned long long g_tree_dbg[TREE_DBG_SLOTS];
+#define TREE_DBG(i, v) do { if (lane_id() == 0) atomicAdd(&g_tree_dbg[i], (unsigned long long)(v)); } while (0)
+#else
+#define TREE_DBG(i, v) do { } while (0)
+#endif
+
 /* Executed by ONE wavefront; rate[j] = count of byte (lane + 64 j) in the block.  Returns the
  * encoded size of the block in bytes (every lane). */
 __device__ __forceinline__ uint64_t tree_fast_wave(const uint32_t (&rate)[4], TreeLds &L, uint64_t blk,
@@ -365,6 +392,7 @@ __device__ __forceinline__ uint64_t tree_fast_wave(const uint32_t (&rate)[4], Tr
             mm.max_len = 1;
             mm.payload_bits = cnt;
             if (lane == 0) meta[blk] = mm;
+            TREE_DBG(TREE_DBG_ONE_SYMBOL, 1);
             return encoded_block_bytes(mm);
         }
     }
@@ -404,6 +432,7 @@ __device__ __forceinline__ uint64_t tree_fast_wave(const uint32_t (&rate)[4], Tr
             TREE_WAVE_SYNC();
         }
     }
+    TREE_DBG(TREE_DBG_BLOCKS + (R >> 1), 1);
 
     int node = HUF_NSYM;
     int root = -1;
@@ -438,6 +467,7 @@ __device__ __forceinline__ uint64_t tree_fast_wave(const uint32_t (&rate)[4], Tr
             }
             root = node;
             node++;
+            TREE_DBG(TREE_DBG_WRAP_ROOT, 1);
             break;
         }
         /* Every item whose rate is below a + b precedes every node still to be made (a node's rate
@@ -455,6 +485,7 @@ __device__ __forceinline__ uint64_t tree_fast_wave(const uint32_t (&rate)[4], Tr
             const uint32_t round_min = R == 4u ? TREE_ROUND_MIN : (R == 2u ? TREE_ROUND_MIN / 2u : TREE_ROUND_MIN / 4u);
             if (sel >= round_min) {
                 const uint32_t pairs = sel >> 1;
+                TREE_DBG((sorted ? TREE_DBG_ROUND_IN_ORDER : TREE_DBG_ROUND_SORTED) + (R >> 1), 1);
                 if (R == 4u) {
                     if (!sorted) wave_sort_r<4>(k);
 #pragma unroll
@@ -540,6 +571,9 @@ __device__ __forceinline__ uint64_t tree_fast_wave(const uint32_t (&rate)[4], Tr
                                 TREE_WAVE_SYNC();
                                 if ((uint32_t)lane < pairs) s_scratch[unp + (uint32_t)lane] = nd[0];
                                 TREE_WAVE_SYNC();
+                                TREE_DBG(TREE_DBG_NODES_SORTED1 + (nr >> 2), 1);
+                            } else {
+                                TREE_DBG(TREE_DBG_NODES_IN_ORDER + (nr >> 2), 1);
                             }
                         } else {
                             nd[0] = p0 < pairs ? s_scratch[unp + p0] : KMAX;
@@ -549,8 +583,12 @@ __device__ __forceinline__ uint64_t tree_fast_wave(const uint32_t (&rate)[4], Tr
                             if (p0 < pairs) s_scratch[unp + p0] = nd[0];
                             if (p1 < pairs) s_scratch[unp + p1] = nd[1];
                             TREE_WAVE_SYNC();
+                            TREE_DBG(TREE_DBG_NODES_SORTED2 + (nr >> 2), 1);
                         }
+                    } else {
+                        TREE_DBG(TREE_DBG_NODES_CHANCE, 1);
                     }
+                    if (nr != R) TREE_DBG(R == 2u ? TREE_DBG_R_2_1 : (nr == 2u ? TREE_DBG_R_4_2 : TREE_DBG_R_4_1), 1);
                     R = nr;
 #pragma unroll
                     for (uint32_t r = 0; r < 4; r++) {
@@ -573,6 +611,7 @@ __device__ __forceinline__ uint64_t tree_fast_wave(const uint32_t (&rate)[4], Tr
                         in_order = k[0] <= nf;
                     }
                     sorted = __ballot(!in_order) == 0ull;
+                    TREE_DBG((sorted ? TREE_DBG_CHECK_PASS : TREE_DBG_CHECK_FAIL) + (R >> 1), 1);
                 }
                 continue;
             }
@@ -582,6 +621,7 @@ __device__ __forceinline__ uint64_t tree_fast_wave(const uint32_t (&rate)[4], Tr
 #pragma unroll
         for (int j = 0; j < 4; j++) k[j] = (k[j] == a) ? nk : ((t[j] == b) ? KMAX : t[j]);
         sorted = false;                                            /* (the new key stands where the smaller of the two stood) */
+        TREE_DBG(TREE_DBG_SINGLE + (R >> 1), 1);
         if (lane == 0) {
             const uint32_t lx = s_lcnt[i1];                        /* tree.c:390-404 */
             s_state[i1] = tree_state((uint32_t)node, 1u, 1u, 0u);
@@ -624,7 +664,10 @@ __device__ __forceinline__ uint64_t tree_fast_wave(const uint32_t (&rate)[4], Tr
                 pending = pending || (u0 & 0x3ffu) != TREE_ANC_ROOT;
             }
         }
-        if (!__any(pending)) break;
+        if (!__any(pending)) {
+            TREE_DBG(TREE_DBG_PATH_ROUNDS + round, 1);
+            break;
+        }
     }
 
     /* The serialized tree goes straight to HBM: a node at preorder position p writes its index there, a leaf
