@@ -329,6 +329,77 @@ int hufgpu_update_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t strea
                          uint32_t flags, uint64_t *out_len, uint64_t *blocks_reencoded, void *stream);
 
 /*
+ * APPEND and TRUNCATE: an indexed stream made longer or shorter IN PLACE.  Every record in front of the last block
+ * stays where it is, so the cost follows the appended bytes, not the stream.
+ *
+ * hufgpu_append: let D be the raw_size bytes the stream decodes to; the stream was written by hufgpu_encode(D, blocksize)
+ * (blocksize as passed there, not 0).  Let A be the src_len bytes at d_src, at any alignment.  After the call
+ * d_stream[0, *out_len) is hufgpu_encode(D ++ A, blocksize) byte for byte, and d_block_offsets[0 .. nb_new] its block
+ * index, nb_new = hufgpu_block_count(raw_size + src_len, blocksize) - the caller's index buffer has room for nb_new + 1
+ * entries.
+ *
+ *   what is touched : with t = raw_size % blocksize and nb_keep = nb_old - (t > 0), the records of blocks [0, nb_keep)
+ *                     and the index entries [0, nb_keep] are not written, and apart from the last block's header, which
+ *                     is always read, not read either: payload damage in them is carried over unseen, as in
+ *                     hufgpu_update_ranges().  With t > 0 the last block is decoded once into the context's scratch area
+ *                     (the one hufgpu_decode_ranges() uses; HUF_ERROR_MEMORY_ALLOCATION when it cannot grow) by the
+ *                     indexed decoders, the first min(src_len, blocksize - t) bytes of A are placed behind it and the
+ *                     joined block is encoded from there; every further block is encoded straight from A.  The new
+ *                     records land at old_index[nb_keep] onwards.  With t = 0 or raw_size = 0 nothing is decoded.
+ *   canonical check : the last block's header must parse (else: what hufgpu_decode() reports for it) and show a
+ *                     block_len of t (blocksize when t = 0), else HUF_ERROR_INVALID_ARGUMENT: a batch's stream, a wrong
+ *                     raw_size, a stream that already has a short block in the middle.  A tail that does not decode
+ *                     returns hufgpu_decode()'s error for it.
+ *   all or nothing  : on any error - a new length over stream_cap (HUF_ERROR_MEMORY_ALLOCATION), a tail that does not
+ *                     decode, a bad header, an argument error - d_stream[0, stream_len) and d_block_offsets[0 .. nb_old]
+ *                     are unchanged byte for byte and *out_len = 0.  Nothing behind stream_cap or behind index entry
+ *                     nb_new is ever written, and on success nothing in [*out_len, stream_cap) either.
+ *                     stream_len + hufgpu_encode_bound(t + src_len, blocksize) always suffices as stream_cap.
+ *   d_sub_index     : optional, the OLD stream's (hufgpu_sub_index_bytes(raw_size, blocksize) bytes): speeds up the decode
+ *                     of the tail, verified as ever - any content gives the same result.
+ *   d_out_sub_index : optional, hufgpu_sub_index_bytes(raw_size + src_len, blocksize) bytes, 8-byte aligned, blocksize
+ *                     below HUFGPU_BATCH_CHUNKED_FROM.  The three arrays of a sub-index are each sized by the block count,
+ *                     so a longer stream has another layout: the sub-index cannot grow in place and is written out of
+ *                     place.  It receives the rows of the new blocks; with d_sub_index as well, the rows of blocks
+ *                     [0, nb_keep) are copied from the old layout to the new one, so the buffer then holds the sub-index
+ *                     of the new stream wherever hufgpu_encode_sub() writes one.  Whole rows are copied, since these
+ *                     blocks' headers are not read: the padding of a row and the row of a one-symbol block, which the
+ *                     encoder never writes and no decoder reads, carry whatever the old buffer held.  That copy moves 7 % of
+ *                     the raw size and is the only part of the call that grows with the stream.  WITHOUT d_sub_index
+ *                     only the new rows are written.
+ * Synchronous: waits once, for (error, *out_len).  Argument errors - blocksize = 0, stream_len > stream_cap, a NULL
+ * stream or index with raw_size > 0 or src_len > 0, a NULL d_src with src_len > 0, a d_stream that is not 4-byte aligned, a
+ * misaligned sub-index, d_src, d_sub_index or d_out_sub_index overlapping d_stream[0, stream_cap), the index or one
+ * another, no context - return HUF_ERROR_INVALID_ARGUMENT before anything is enqueued.  src_len = 0 is success, writes
+ * nothing, needs no context and gives *out_len = stream_len.  Blocks of HUFGPU_BATCH_CHUNKED_FROM bytes and more take a slow route through
+ * the chunked encoder (same output, same guarantee, several waits, scratch for the new records as well); a d_out_sub_index
+ * returns HUF_ERROR_INVALID_ARGUMENT there.  A pending hufgpu_decode() of the context is forgotten.  There is no CPU path.
+ */
+int hufgpu_append(hufgpu_ctx_t *ctx, void *d_stream, uint64_t stream_len, uint64_t stream_cap,
+                  uint64_t *d_block_offsets, uint64_t raw_size, uint64_t blocksize,
+                  const void *d_src, uint64_t src_len,
+                  const void *d_sub_index, void *d_out_sub_index,
+                  uint32_t flags, uint64_t *out_len, void *stream);
+
+/*
+ * hufgpu_truncate: the stream of hufgpu_append() cut to its first new_raw_size bytes: afterwards d_stream[0, *out_len) is
+ * hufgpu_encode(D[0, new_raw_size), blocksize) and d_block_offsets[0 .. hufgpu_block_count(new_raw_size, blocksize)] its
+ * index, in place, with the guarantees and the argument checks of hufgpu_append() (stream_cap = stream_len: a cut never
+ * makes a stream longer).  new_raw_size > raw_size returns HUF_ERROR_INVALID_ARGUMENT; new_raw_size = raw_size changes
+ * nothing.  A cut on a block border decodes nothing and writes nothing: *out_len is the device index entry at that border
+ * (one wait).  A cut inside block k decodes block k into the scratch area and encodes its first new_raw_size - k * blocksize
+ * bytes at old_index[k]; index entry k + 1 is written, the entries behind it are left as they are.  The canonical check
+ * applies to the header of block k: its block_len must be blocksize, or raw_size % blocksize for the last block.
+ * d_out_sub_index is laid out for (new_raw_size, blocksize): row k is written by the encoder, rows [0, k) are copied when
+ * d_sub_index is given.
+ */
+int hufgpu_truncate(hufgpu_ctx_t *ctx, void *d_stream, uint64_t stream_len,
+                    uint64_t *d_block_offsets, uint64_t raw_size, uint64_t blocksize,
+                    uint64_t new_raw_size,
+                    const void *d_sub_index, void *d_out_sub_index,
+                    uint32_t flags, uint64_t *out_len, void *stream);
+
+/*
  * One logical input over the GPUs of a node: RCCL scatter / gather of block buffers.
  * Blocks are independent (src/encoder.c:288-374 resets all state between blocks), so rank r of G owns a contiguous range
  * of ceil(nblocks / G) blocks (hufgpu_shard_range) and the codec needs no collective; the data starts and ends on ONE

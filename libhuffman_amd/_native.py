@@ -71,7 +71,8 @@ hufgpu_decode_stream_complete hufgpu_block_index hufgpu_decode_counters hufgpu_c
 hufgpu_ctx_device hufgpu_shard_unique_id hufgpu_shard_create hufgpu_shard_destroy hufgpu_shard_info hufgpu_shard_last_error
 hufgpu_shard_range hufgpu_shard_plan_decode hufgpu_encode_sharded hufgpu_decode_sharded hufgpu_shard_set_timeout
 hufgpu_batch_geometry hufgpu_encode_batch hufgpu_decode_batch hufgpu_decode_ranges
-hufgpu_sub_index_from_raw hufgpu_decode_build_sub hufgpu_build_sub_index hufgpu_update_ranges""".split()
+hufgpu_sub_index_from_raw hufgpu_decode_build_sub hufgpu_build_sub_index hufgpu_update_ranges
+hufgpu_append hufgpu_truncate""".split()
 
 
 def so_path() -> str:
@@ -172,6 +173,10 @@ def load() -> C.CDLL:
     L.hufgpu_update_ranges.restype = C.c_int
     L.hufgpu_update_ranges.argtypes = [vp, vp, u64, vp, u64, u64, P64, P64, P64, vp, vp, u64, u64, vp, u64, vp, vp, C.c_uint32,
                                        P64, P64, vp]
+    L.hufgpu_append.restype = C.c_int
+    L.hufgpu_append.argtypes = [vp, vp, u64, u64, vp, u64, u64, vp, u64, vp, vp, C.c_uint32, P64, vp]
+    L.hufgpu_truncate.restype = C.c_int
+    L.hufgpu_truncate.argtypes = [vp, vp, u64, vp, u64, u64, u64, vp, vp, C.c_uint32, P64, vp]
     _LIB = L
     return L
 

@@ -365,6 +365,66 @@ class GpuCodec:
         """update_ranges for the one range [lo, lo + data.numel())."""
         return self.update_ranges(stream, stream_len, offsets, nblocks, [(lo, lo + data.numel())], data, **kwargs)
 
+    # -- append and truncate: an indexed stream made longer or shorter in place ----------------------
+    def append(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, raw_size: int, blocksize: int,
+               data: torch.Tensor, sub_index: torch.Tensor | None = None, new_sub_index: bool = False,
+               relaxed: bool = False):
+        """Append the bytes of `data` to the stream of `raw_size` bytes encoded in blocks of `blocksize`
+        (hufgpu_append): afterwards stream and offsets are what encode() writes for the old data plus `data`.  Works in
+        place on `stream` and `offsets` when they are large enough (the old length plus encode_bound of the tail block
+        and the new bytes; one entry per block and one more); otherwise tensors of that size are allocated and the
+        old content copied.  `sub_index` is the OLD stream's (optional); `new_sub_index` asks for the new stream's.
+        Returns (stream, offsets, new length, new raw size[, new sub-index]).  Raises HuffmanGpuError, and then the
+        stream and its index are unchanged."""
+        assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
+        assert stream.dtype == torch.uint8 and stream.is_cuda and stream.is_contiguous()
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous()
+        n = data.numel()
+        new_raw = raw_size + n
+        nb_old, nb_new = self.block_count(raw_size, blocksize), self.block_count(new_raw, blocksize)
+        tail = raw_size % blocksize if blocksize else 0
+        if n and stream.numel() < stream_len + self.encode_bound(tail + n, blocksize):
+            grown = torch.empty(stream_len + self.encode_bound(tail + n, blocksize), dtype=torch.uint8, device=self.tdev)
+            grown[:stream_len] = stream[:stream_len]
+            stream = grown
+        if offsets.numel() < nb_new + 1:
+            grown = torch.empty(nb_new + 1, dtype=torch.int64, device=self.tdev)
+            grown[: nb_old + 1] = offsets[: nb_old + 1]
+            offsets = grown
+        new_sub = self.new_sub_index(new_raw, blocksize) if new_sub_index else None
+        out_len = C.c_uint64(0)
+        flags = _native.RELAXED_TREE if relaxed else _native.STRICT_TREE
+        err = self.lib.hufgpu_append(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len, stream.numel(),
+                                     offsets.data_ptr(), raw_size, blocksize, data.data_ptr() if n else None, n,
+                                     sub_index.data_ptr() if sub_index is not None else None,
+                                     new_sub.data_ptr() if new_sub is not None else None, flags, C.byref(out_len),
+                                     self._stream())
+        self._pending_decode = None
+        self._check(err, "Failed to append to the stream")
+        res = (stream, offsets, int(out_len.value), new_raw)
+        return res + (new_sub,) if new_sub_index else res
+
+    def truncate(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, raw_size: int, blocksize: int,
+                 new_raw_size: int, sub_index: torch.Tensor | None = None, new_sub_index: bool = False,
+                 relaxed: bool = False):
+        """Cut the stream of `raw_size` bytes encoded in blocks of `blocksize` to its first `new_raw_size` bytes, in
+        place (hufgpu_truncate): afterwards stream and offsets are what encode() writes for them.  Returns what
+        append() returns."""
+        assert stream.dtype == torch.uint8 and stream.is_cuda and stream.is_contiguous()
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous()
+        new_sub = self.new_sub_index(new_raw_size, blocksize) if new_sub_index else None
+        out_len = C.c_uint64(0)
+        flags = _native.RELAXED_TREE if relaxed else _native.STRICT_TREE
+        err = self.lib.hufgpu_truncate(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
+                                       offsets.data_ptr(), raw_size, blocksize, new_raw_size,
+                                       sub_index.data_ptr() if sub_index is not None else None,
+                                       new_sub.data_ptr() if new_sub is not None else None, flags, C.byref(out_len),
+                                       self._stream())
+        self._pending_decode = None
+        self._check(err, "Failed to truncate the stream")
+        res = (stream, offsets, int(out_len.value), new_raw_size)
+        return res + (new_sub,) if new_sub_index else res
+
     # -- the sub-index of a stream that came without one -------------------------------------------
     def build_sub_index(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, raw_size: int, blocksize: int,
                         raw: torch.Tensor | None = None, sub_index: torch.Tensor | None = None, relaxed: bool = False):

@@ -15,6 +15,8 @@
  *            sub_tile_add_kernel for blocks of 2 MiB and more)
  *   overwrite of byte ranges: decode_prepare_kernel -> drange_plan / drange_mark -> upd_class -> the indexed decoders on
  *            the staged blocks -> upd_overlay -> hist_*_pairs -> upd_index -> pack_pairs, update_copy_kernel
+ *   append / truncate in place: decode_prepare_kernel on the one block that is opened again -> app_plan -> the indexed
+ *            decoders on it -> app_join -> hist_*_pairs -> app_index -> pack_pairs -> app_commit (-> app_sub_rows)
  *
  * Wave size is 64 throughout (hard-coded, gfx950 only).  All arithmetic is integer.
  */
@@ -43,3 +45,4 @@
 #include "kernels/ranges.hpp"
 #include "kernels/sub_build.hpp"
 #include "kernels/update.hpp"
+#include "kernels/append.hpp"
