@@ -42,6 +42,9 @@ typedef struct hufgpu_ctx hufgpu_ctx_t;
 #define HUFGPU_RELAXED_TREE 1u  /* accept the 1025-entry tree the encoder itself emits for blocks
                                    with all 256 byte values */
 
+#define HUFGPU_RANGES_TILES 4u  /* hufgpu_decode_ranges only (every other entry point ignores it): the caller states that
+                                 * d_sub_index is the sub-index of this very stream; cut blocks are then decoded by the
+                                 * sub-index tile, not whole - see TILES at hufgpu_decode_ranges */
 #define HUFGPU_SEQUENTIAL   2u  /* hufgpu_decode_stream only: skip the parallel block discovery and take the
                                    blocks strictly in order (diagnostics; results are identical) */
 
@@ -211,6 +214,38 @@ int hufgpu_decode_batch(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream
  *                     the touched blocks are decoded with the encoder's sub-index, verified as ever - the results are
  *                     those of the same call without it for ANY content of the buffer.  NULL: raw_size and blocksize
  *                     are not looked at.
+ *
+ * TILES (flags & HUFGPU_RANGES_TILES, with d_sub_index; without a sub-index the flag does nothing): the sub-index holds
+ * the payload bit every tile of 2 048 symbols starts at, so a range can be decoded from the first tile that holds one of
+ * its bytes - the cost of a range follows the range, not the block, and a stream of ONE block (blocksize = 0) has random
+ * access.  That a tile's recorded start is where the in-order decoder arrives cannot be verified without decoding what
+ * lies in front of it (Huffman codes resynchronise: a false start can pass every later check), so the promise "for ANY
+ * content of the buffer" above cannot hold for a partial decode.  It stays as it is for every call without the flag.  By
+ * setting the flag the caller states that d_sub_index is the sub-index of THIS stream: from hufgpu_encode_sub(), a batch
+ * encode, hufgpu_update_ranges(), hufgpu_append() / hufgpu_truncate(), or one of the three builders below.  Then:
+ *   1. With the stream's own sub-index, every range's bytes, error and delivered count are those of the same call
+ *      without the flag, as long as the payload in front of the range's first touched tile, inside that tile's block,
+ *      is as the encoder wrote it.
+ *   2. Damage in the payload of UNTOUCHED tiles of a touched block goes unnoticed, just as damage in untouched blocks
+ *      does without the flag; the touched tiles' bytes are delivered with success.
+ *   3. Damage inside a touched tile, or in the header or tree of a touched block, gives what the call without the flag
+ *      gives: every group of 32 symbols of a touched tile is decoded from its true start - to what the in-order decoder
+ *      sees there - and must take exactly its recorded bits; the claimed code lengths are checked against the stream's
+ *      tree.  When a check fails, the call is served again by the whole-block route, which produces the reference's
+ *      error and partial delivery.
+ *   4. With any OTHER content of d_sub_index: no memory fault, no byte outside the first (cut length) bytes of the slots
+ *      is written, every walk stays inside the tree and the payload, the call returns.  Bytes inside a slot MAY BE WRONG
+ *      WITH HUF_ERROR_SUCCESS - but only if every check happens to hold: the tile start inside the payload, the start
+ *      plus the sum of the tile's 64 bit counts equal to the next tile's recorded start, every group of the tile
+ *      exactly its bits, the code lengths those of the tree.
+ *   5. Without the flag, or without d_sub_index, nothing changes.
+ * Which blocks go by tiles: a touched block that is not decoded straight into a slot, whose block_len is the layout's
+ * min(blocksize, raw_size - b * blocksize), whose tree has more than one leaf and over which all ranges together make no
+ * more (range, tile) pairs than the block has tiles - the tile route never decodes more symbols than the whole block
+ * holds.  Every other block is routed as without the flag.  Tile-routed blocks use no scratch area.  A call in which no
+ * check fails waits as often as the call without the flag; one in which a check fails is run a second time without it.
+ * hufgpu_ranges_counters() says which way the blocks went.
+ *
  * Synchronous.  Returns HUF_ERROR_SUCCESS or the error of the first failing range in range order.  Argument errors
  * (lo > hi, decreasing out_offsets, NULL host arrays, a misaligned or mis-sized sub-index, no context) return
  * HUF_ERROR_INVALID_ARGUMENT before anything is enqueued; nranges = 0 is success.  hufgpu_decode_counters() after the
@@ -474,6 +509,13 @@ int hufgpu_decode_small(hufgpu_ctx_t *ctx, const void *h_in_pinned, uint64_t ava
  * sub-index), counters[1] = 0 (reserved: it counted the blocks round 4's one-pass decoder handed on).
  * Results never depend on these; they say what a slow decode was slow for.  Synchronises the stream. */
 int hufgpu_decode_counters(hufgpu_ctx_t *ctx, uint32_t *counters);
+
+/* How the last hufgpu_decode_ranges() routed its blocks: counters[0] = blocks decoded direct (straight into a slot),
+ * [1] = blocks decoded whole into the scratch area, fail-overs of the tile route included, [2] = blocks served by tiles
+ * (HUFGPU_RANGES_TILES), [3] = (range, tile) items decoded, [4] = blocks that failed a tile check and were decoded again,
+ * [5..7] = 0.  When [4] is not 0 the call was served again by the whole-block route: [0] and [1] are then that run's and
+ * [2] is 0.  Results never depend on these.  HUF_ERROR_INVALID_ARGUMENT for a NULL context or array; touches no GPU. */
+int hufgpu_ranges_counters(hufgpu_ctx_t *ctx, uint64_t counters[8]);
 
 /* Synchronise and report the outcome of the last enqueued hufgpu_decode() / hufgpu_decode_sub().
  * LIFETIME: d_stream, d_block_offsets and d_out of the enqueued call must stay valid until this returns - when a block

@@ -36,6 +36,8 @@ HUF_ERROR_BTREE_CORRUPTED = 6
 
 STRICT_TREE = 0
 RELAXED_TREE = 1
+SEQUENTIAL = 2                  # hufgpu_decode_stream only
+RANGES_TILES = 4                # hufgpu_decode_ranges only: cut blocks by the sub-index tile (include/huffman_gpu.h, TILES)
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t))
@@ -72,7 +74,7 @@ hufgpu_ctx_device hufgpu_shard_unique_id hufgpu_shard_create hufgpu_shard_destro
 hufgpu_shard_range hufgpu_shard_plan_decode hufgpu_encode_sharded hufgpu_decode_sharded hufgpu_shard_set_timeout
 hufgpu_batch_geometry hufgpu_encode_batch hufgpu_decode_batch hufgpu_decode_ranges
 hufgpu_sub_index_from_raw hufgpu_decode_build_sub hufgpu_build_sub_index hufgpu_update_ranges
-hufgpu_append hufgpu_truncate""".split()
+hufgpu_append hufgpu_truncate hufgpu_ranges_counters""".split()
 
 
 def so_path() -> str:
@@ -167,6 +169,8 @@ def load() -> C.CDLL:
     L.hufgpu_decode_ranges.restype = C.c_int
     L.hufgpu_decode_ranges.argtypes = [vp, vp, u64, vp, u64, u64, P64, P64, P64, vp, u64, u64, vp, C.c_uint32,
                                        C.POINTER(C.c_int32), P64, vp]
+    L.hufgpu_ranges_counters.restype = C.c_int
+    L.hufgpu_ranges_counters.argtypes = [vp, P64]
     L.hufgpu_sub_index_from_raw.argtypes = [vp, vp, u64, vp, vp, u64, u64, vp, C.c_uint32, P64, vp]
     L.hufgpu_decode_build_sub.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, vp, C.c_uint32, P64, P64, vp]
     L.hufgpu_build_sub_index.argtypes = [vp, vp, u64, vp, u64, u64, vp, C.c_uint32, P64, vp]

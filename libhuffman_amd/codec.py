@@ -271,11 +271,14 @@ class GpuCodec:
     # -- ranges: bytes [lo, hi) of the original data out of one indexed stream --------------------
     def decode_ranges(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, ranges,
                       out: torch.Tensor | None = None, out_offsets=None, relaxed: bool = False,
-                      sub_index: torch.Tensor | None = None, raw_size: int = 0, blocksize: int = 0):
+                      sub_index: torch.Tensor | None = None, raw_size: int = 0, blocksize: int = 0, tiles: bool = False):
         """Decode the byte ranges `ranges` = [(lo, hi), ...] of the original data, range i into its slot
         out[out_offsets[i]:out_offsets[i + 1]] (default: the range lengths back to back), in one launch sequence
         (hufgpu_decode_ranges).  Only the blocks a range touches are decoded.  Returns (out, errs, raw_lens): per range
-        the error and the bytes delivered - per-range errors are returned, not raised."""
+        the error and the bytes delivered - per-range errors are returned, not raised.
+        tiles=True (HUFGPU_RANGES_TILES): `sub_index` is vouched to be this stream's own, and of a cut block only the
+        sub-index tiles that hold bytes of a range are decoded (the contract: include/huffman_gpu.h, TILES).  Without
+        `sub_index` it does nothing."""
         ranges = [(int(lo), int(hi)) for lo, hi in ranges]
         n = len(ranges)
         if out_offsets is None:
@@ -289,7 +292,7 @@ class GpuCodec:
         assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.numel() >= out_offsets[-1]
         errs = (C.c_int32 * max(1, n))()
         raws = (C.c_uint64 * max(1, n))()
-        flags = _native.RELAXED_TREE if relaxed else _native.STRICT_TREE
+        flags = (_native.RELAXED_TREE if relaxed else _native.STRICT_TREE) | (_native.RANGES_TILES if tiles else 0)
         err = self.lib.hufgpu_decode_ranges(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
                                             offsets.data_ptr(), nblocks, n, _u64_array(lo for lo, _ in ranges),
                                             _u64_array(hi for _, hi in ranges), _u64_array(out_offsets),
@@ -303,13 +306,20 @@ class GpuCodec:
 
     def decode_range(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, lo: int, hi: int,
                      relaxed: bool = False, sub_index: torch.Tensor | None = None, raw_size: int = 0,
-                     blocksize: int = 0) -> torch.Tensor:
+                     blocksize: int = 0, tiles: bool = False) -> torch.Tensor:
         """The bytes [lo, hi) of the original data (cut at its end) as a new tensor.  Raises HuffmanGpuError, with the
         bytes delivered in front of the failure in `.raw`, when a block of the range does not decode."""
         out, errs, raws = self.decode_ranges(stream, stream_len, offsets, nblocks, [(lo, hi)], relaxed=relaxed,
-                                             sub_index=sub_index, raw_size=raw_size, blocksize=blocksize)
+                                             sub_index=sub_index, raw_size=raw_size, blocksize=blocksize, tiles=tiles)
         self._check(errs[0], "Failed to decode the range", raw=raws[0])
         return out[: raws[0]]
+
+    def ranges_counters(self):
+        """How the last decode_ranges routed its blocks (hufgpu_ranges_counters): (direct, staged whole, served by
+        tiles, (range, tile) items decoded, failed a tile check and decoded again, 0, 0, 0)."""
+        c = (C.c_uint64 * 8)()
+        self._check(self.lib.hufgpu_ranges_counters(self._ctx, c), "counter readout failed")
+        return tuple(int(x) for x in c)
 
     # -- overwrite: bytes [lo, hi) of the original data replaced in one indexed stream ---------------
     def update_ranges(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, ranges,

@@ -124,6 +124,8 @@ struct hufgpu_ctx {
     uint64_t *d_rrel, *d_rplan;
     uint32_t *d_rflag;
     unsigned long long *d_rcounters;
+    unsigned long long *d_rtpairs;            /* the tile route's (range, tile) pairs per block (kernels/range_tiles.hpp) */
+    uint64_t rcounters[8];                    /* hufgpu_ranges_counters(): of the last hufgpu_decode_ranges */
     uint8_t *d_rscratch;
     uint64_t rscratch_bytes;
 
@@ -301,8 +303,8 @@ static void free_batch_ws(hufgpu_ctx *c)
 
 static void free_range_ws(hufgpu_ctx *c)
 {
-    (void)hipFree(c->d_rcover); (void)hipFree(c->d_rrel); (void)hipFree(c->d_rplan); (void)hipFree(c->d_rflag);
-    c->d_rcover = NULL; c->d_rrel = c->d_rplan = NULL; c->d_rflag = NULL;
+    (void)hipFree(c->d_rcover); (void)hipFree(c->d_rrel); (void)hipFree(c->d_rplan); (void)hipFree(c->d_rflag); (void)hipFree(c->d_rtpairs);
+    c->d_rcover = NULL; c->d_rrel = c->d_rplan = NULL; c->d_rflag = NULL; c->d_rtpairs = NULL;
     c->rws_blocks = c->rws_ranges = 0;
 }
 
@@ -800,6 +802,14 @@ extern "C" int hufgpu_decode_counters(hufgpu_ctx_t *ctx, uint32_t *counters)
     HIP_OK(ctx, hipSetDevice(ctx->device));
     if (ctx->last_stream || ctx->decode_pending) HIP_OK(ctx, hipStreamSynchronize(ctx->last_stream));
     HIP_OK(ctx, hipMemcpy(counters, ctx->d_fix_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return HUFE_OK;
+}
+
+/* How the last hufgpu_decode_ranges routed its blocks (include/huffman_gpu.h): host values, no GPU is touched. */
+extern "C" int hufgpu_ranges_counters(hufgpu_ctx_t *ctx, uint64_t counters[8])
+{
+    if (!ctx || !counters) return HUFE_ARGUMENT;
+    memcpy(counters, ctx->rcounters, sizeof(ctx->rcounters));
     return HUFE_OK;
 }
 
@@ -1806,7 +1816,7 @@ extern "C" int hufgpu_decode_batch(hufgpu_ctx_t *ctx, const void *d_stream, uint
 
 static int ensure_range_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t nranges)
 {
-    if (!c->d_rcounters) HIP_OK(c, hipMalloc((void **)&c->d_rcounters, 4 * sizeof(unsigned long long)));
+    if (!c->d_rcounters) HIP_OK(c, hipMalloc((void **)&c->d_rcounters, 8 * sizeof(unsigned long long)));
     if (nblocks <= c->rws_blocks && nranges <= c->rws_ranges) return HUFE_OK;
     HIP_OK(c, hipDeviceSynchronize());
     const uint64_t nbc = (nblocks > c->rws_blocks ? nblocks + nblocks / 8 : c->rws_blocks) + 16;
@@ -1814,6 +1824,7 @@ static int ensure_range_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t nranges)
     free_range_ws(c);
     HIP_OK(c, hipMalloc((void **)&c->d_rcover, nbc * sizeof(unsigned long long)));
     HIP_OK(c, hipMalloc((void **)&c->d_rrel, nbc * sizeof(uint64_t)));
+    HIP_OK(c, hipMalloc((void **)&c->d_rtpairs, nbc * sizeof(unsigned long long)));
     HIP_OK(c, hipMalloc((void **)&c->d_rplan, 4 * nrc * sizeof(uint64_t)));
     HIP_OK(c, hipMalloc((void **)&c->d_rflag, nrc * sizeof(uint32_t)));
     c->rws_blocks = nbc;
@@ -1866,7 +1877,10 @@ extern "C" int hufgpu_decode_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uin
     for (uint64_t i = 0; i < nranges; i++) { range_errs[i] = HUFE_OK; range_raw_lens[i] = 0; }
     ctx->decode_pending = 0;
     ctx->last_st = NULL;
+    memset(ctx->rcounters, 0, sizeof(ctx->rcounters));
     if (nb == 0 || stream_len == 0) return HUFE_OK;     /* no data (src/decoder.c:218): every range lies behind its end */
+    /* the tile route (kernels/range_tiles.hpp): the caller vouches for the sub-index */
+    const bool tiles = (flags & HUFGPU_RANGES_TILES) != 0u && d_sub_index != NULL;
 
     HIP_OK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = pick_stream(ctx, stream);
@@ -1917,6 +1931,11 @@ extern "C" int hufgpu_decode_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uin
     ra.range_fail = ctx->d_item_fail;
     ra.range_res = ctx->d_item_res;
     ra.dout = (uint8_t *)d_out;
+    if (tiles) {
+        ra.tpairs = ctx->d_rtpairs;
+        ra.raw_size = raw_size;
+        ra.blocksize = blocksize;
+    }
     drange_plan_kernel<<<dim3(grid256((nb + 1 > nranges ? nb + 1 : nranges))), dim3(256), 0, s>>>(ra);
     /* a few long ranges: several workgroups a range walk its blocks; many ranges are parallel enough as they are */
     const unsigned mark_y = nranges >= 64 ? 1u : (unsigned)(nb / 2048 < 1 ? 1 : (nb / 2048 > 16 ? 16 : nb / 2048));
@@ -1924,9 +1943,14 @@ extern "C" int hufgpu_decode_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uin
     drange_class_kernel<<<dim3(grid256(nb)), dim3(256), 0, s>>>(ra);
     HIP_OK(ctx, hipGetLastError());
     /* how many blocks are staged and how long the longest of them is decides the scratch area: the one wait in front of the decoders */
-    HIP_OK(ctx, hipMemcpyAsync(ctx->h_result + 8, ctx->d_rcounters, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(ctx, hipMemcpyAsync(ctx->h_result + 8, ctx->d_rcounters, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIP_OK(ctx, hipStreamSynchronize(s));
     const uint64_t nstaged = ctx->h_result[8], longest = ctx->h_result[9];
+    const uint64_t ndirect = ctx->h_result[11], ntiled = ctx->h_result[12], nitems = ctx->h_result[13];
+    ctx->rcounters[0] = ndirect;
+    ctx->rcounters[1] = nstaged;
+    ctx->rcounters[2] = ntiled;
+    ctx->rcounters[3] = nitems;
     const uint64_t stride = (longest + 15u) & ~15ull;
     uint64_t scratch_bytes = 0;
     if (nstaged) {
@@ -1965,7 +1989,25 @@ extern "C" int hufgpu_decode_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uin
     fix.blocks = ctx->d_fix_blocks;
     fix.flag = ctx->d_fix_flag;
     const unsigned fix_grid = (unsigned)(nb < 1024 ? nb : 1024);
-    if (d_sub_index) {
+    if (ntiled) {
+        /* one wave an item; a workgroup's eight waves take about four items each of a long range, so that the table build
+         * it starts with is paid once per 32 tiles - the longest range, known here, bounds the tiles a range has in a block */
+        uint64_t longest_range = 0;
+        for (uint64_t i = 0; i < nranges; i++)
+            if (range_hi[i] - range_lo[i] > longest_range) longest_range = range_hi[i] - range_lo[i];
+        uint64_t tile_y = (longest_range / HUF_SUB_TILE + 2 + 31) / 32;
+        if (tile_y > 1024) tile_y = 1024;
+        RangeTileArgs ta;
+        ta.stream = st;
+        ta.stream_len = stream_len;
+        ta.offsets = d_block_offsets;
+        ta.sub = sub_index_view((void *)d_sub_index, raw_size, blocksize);
+        drange_tiles_kernel<<<dim3((unsigned)nranges, (unsigned)tile_y), dim3(RTILE_THREADS), 0, s>>>(ra, ta);
+    }
+    /* (every touched block served by tiles: nothing for the block decoders to do) */
+    const bool block_decoders = !(ntiled && nstaged == 0 && ndirect == 0);
+    if (!block_decoders) {
+    } else if (d_sub_index) {
         const HufSubIndex sub = sub_index_view((void *)d_sub_index, raw_size, blocksize);
         decode_sub_kernel<DSUB_THREADS><<<dim3((unsigned)(nb * cpb)), dim3(DSUB_THREADS), 0, s>>>(st, stream_len, d_block_offsets, ctx->d_dmeta, ctx->d_out_offsets, blens, base, span, ctx->d_status, res, sub, blocksize, (uint32_t)cpb, fix);
     } else {
@@ -1974,7 +2016,8 @@ extern "C" int hufgpu_decode_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uin
         fa.lens = blens; fa.out = base; fa.out_cap = span; fa.status = ctx->d_status; fa.result = res; fa.fix = fix;
         decode_fast_kernel<DEC_THREADS><<<dim3((unsigned)nb), dim3(DEC_THREADS), 0, s>>>(fa);
     }
-    decode_fix_kernel<DEC_THREADS><<<dim3(fix_grid), dim3(DEC_THREADS), 0, s>>>(st, stream_len, d_block_offsets, ctx->d_dmeta, blens, base, span, ctx->d_status, res, fix);
+    if (block_decoders)
+        decode_fix_kernel<DEC_THREADS><<<dim3(fix_grid), dim3(DEC_THREADS), 0, s>>>(st, stream_len, d_block_offsets, ctx->d_dmeta, blens, base, span, ctx->d_status, res, fix);
     drange_result_kernel<<<dim3((unsigned)nranges), dim3(256), 0, s>>>(ra);
     if (nstaged) {
         const unsigned gather_y = nranges >= 1024 ? 2u : (nranges >= 64 ? 4u : 16u);
@@ -1982,7 +2025,21 @@ extern "C" int hufgpu_decode_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uin
     }
     HIP_OK(ctx, hipGetLastError());
     HIP_OK(ctx, hipMemcpyAsync(ctx->h_item_res, ctx->d_item_res, 3 * nranges * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (ntiled) HIP_OK(ctx, hipMemcpyAsync(ctx->h_result + 14, ctx->d_rcounters + 6, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIP_OK(ctx, hipStreamSynchronize(s));
+    if (ntiled && ctx->h_result[14] != 0) {
+        /* A tile-routed block failed a check (a sub-index that is not the stream's, damage in a touched tile or in the
+         * tree): the call once more by the staged route, which verifies everything and produces the reference's errors
+         * and partial deliveries - the slots are simply written again.  Of the counters, the blocks are then those of
+         * that call (none is served by tiles); the items and the failed blocks are this one's. */
+        const uint64_t nfailed = ctx->h_result[14];
+        const int rc2 = hufgpu_decode_ranges(ctx, d_stream, stream_len, d_block_offsets, nblocks, nranges, range_lo, range_hi, out_offsets,
+                                             d_sub_index, raw_size, blocksize, d_out, flags & ~HUFGPU_RANGES_TILES, range_errs,
+                                             range_raw_lens, stream);
+        ctx->rcounters[3] = nitems;
+        ctx->rcounters[4] = nfailed;
+        return rc2;
+    }
 
     int first_err = HUFE_OK;
     uint64_t first_range = 0;

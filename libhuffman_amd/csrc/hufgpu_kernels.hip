@@ -43,6 +43,7 @@
 #include "kernels/fill.hpp"
 #include "kernels/batch.hpp"
 #include "kernels/ranges.hpp"
+#include "kernels/range_tiles.hpp"
 #include "kernels/sub_build.hpp"
 #include "kernels/update.hpp"
 #include "kernels/append.hpp"

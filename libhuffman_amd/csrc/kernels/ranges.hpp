@@ -6,7 +6,9 @@
    ranges over every block, drange_class_kernel sorts the blocks into untouched (switched off: block_len = 0 in the
    context's copy of the headers), direct (wholly inside the one range that touches it: decoded straight into that
    range's slot) and staged (an edge that is cut, a block several ranges share: decoded once, whole, into the context's
-   scratch area).  drange_place_kernel turns that into the output offsets the indexed decoders read, which then run
+   scratch area).  With HUFGPU_RANGES_TILES a block that would be staged may instead be served tile by tile
+   (DRANGE_TILES: range_tiles.hpp; drange_mark_kernel counts the (range, tile) pairs that decide it) - the decoders
+   below do not see it.  drange_place_kernel turns that into the output offsets the indexed decoders read, which then run
    unchanged.  drange_result_kernel reduces the block states to one result per range and drange_gather_kernel copies
    the clipped pieces of the staged blocks into the slots. */
 #pragma once
@@ -15,12 +17,14 @@
 
 #include "../hufgpu_common.h"
 #include "offsets.hpp"
+#include "pack.hpp"
 
 namespace hufgpu {
 
 #define DRANGE_UNTOUCHED 0u
 #define DRANGE_DIRECT    1u
 #define DRANGE_STAGED    2u
+#define DRANGE_TILES     3u         /* switched off for the decoders like an untouched block: drange_tiles_kernel serves it */
 #define DRANGE_FLAG_MEMORY 1u       /* the slot is shorter than the range: nothing of it is decoded */
 #define DRANGE_FLAG_HEADER 2u       /* the range reaches the first block whose header does not parse */
 #define DRANGE_PIECE_CHUNKS 1024u   /* a gather workgroup's piece: 1 024 accesses of 16 bytes */
@@ -40,13 +44,17 @@ struct DecRangeArgs {
     uint32_t *kind;                         /* [nblocks] DRANGE_* */
     uint64_t *rplan;                        /* [4 nranges] the clipped range [lo, hi), its first and last block (first > last: none) */
     uint32_t *rflag;                        /* [nranges] DRANGE_FLAG_* */
-    unsigned long long *counters;           /* [3] staged blocks, the longest of them, the first block whose header does not parse */
+    unsigned long long *counters;           /* [7] staged blocks, the longest of them, the first block whose header does not parse; direct
+                                               blocks, tile-routed blocks, their (range, tile) pairs, tile-routed blocks that failed a check */
     unsigned long long *range_fail;         /* [nranges] the first failing touched block (~0: none) */
     uint64_t *range_res;                    /* [3 nranges] out: error, bytes delivered, failing block (~0: none) */
     /* known once the scratch area is: */
     uint64_t dout_off, scratch_off, stride; /* d_out and the scratch area from the decoders' base; bytes per staged block */
     const uint8_t *scratch;
     uint8_t *dout;
+    /* the tile route (NULL: none - no flag, no sub-index, or hufgpu_update_ranges' plan) */
+    unsigned long long *tpairs;             /* [nblocks] (range, tile) pairs over the block; bit 63: it failed a tile check */
+    uint64_t raw_size, blocksize;           /* the layout the sub-index rows are addressed by */
 };
 
 __device__ __forceinline__ uint64_t drange_pos(const DecRangeArgs &a, uint64_t b)
@@ -60,9 +68,15 @@ __device__ __forceinline__ uint64_t drange_pos(const DecRangeArgs &a, uint64_t b
 __global__ __launch_bounds__(256) void drange_plan_kernel(DecRangeArgs a)
 {
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t == 0) { a.counters[0] = 0; a.counters[1] = 0; a.counters[2] = *a.first_bad; }
+    if (t == 0) {
+        a.counters[0] = 0; a.counters[1] = 0; a.counters[2] = *a.first_bad;
+        a.counters[3] = 0; a.counters[4] = 0; a.counters[5] = 0; a.counters[6] = 0;
+    }
     if (t <= a.nblocks) a.bprefix[t] = drange_pos(a, t);
-    if (t < a.nblocks) a.cover[t] = 0;
+    if (t < a.nblocks) {
+        a.cover[t] = 0;
+        if (a.tpairs) a.tpairs[t] = 0;
+    }
     if (t >= a.nranges) return;
     const uint64_t kb = *a.first_bad;
     const bool bad = kb < a.nblocks;
@@ -97,17 +111,29 @@ __global__ __launch_bounds__(256) void drange_plan_kernel(DecRangeArgs a)
     a.rflag[t] = flag;
 }
 
-/* grid (nranges, y): range blockIdx.x adds itself to the cover of each of its blocks */
+/* grid (nranges, y): range blockIdx.x adds itself to the cover of each of its blocks - and, for the tile route, the
+ * sub-index tiles of the block that hold bytes of it to the block's pairs */
 __global__ __launch_bounds__(256) void drange_mark_kernel(DecRangeArgs a)
 {
+    asm volatile("; one VGPR more than the kernel uses (the build's ISA check: a 64-bit shift by the last of sixteen)" ::: "v16");
     const uint64_t i = blockIdx.x;
     const uint64_t fb = a.rplan[4 * i + 2], lb = a.rplan[4 * i + 3];
     if (fb > lb) return;
-    for (uint64_t b = fb + (uint64_t)blockIdx.y * 256 + threadIdx.x; b <= lb; b += (uint64_t)gridDim.y * 256)
+    const uint64_t lo = a.rplan[4 * i], hi = a.rplan[4 * i + 1];
+    for (uint64_t b = fb + (uint64_t)blockIdx.y * 256 + threadIdx.x; b <= lb; b += (uint64_t)gridDim.y * 256) {
         atomicAdd(&a.cover[b], (1ull << 32) + i);
+        if (a.tpairs) {
+            const uint64_t p0 = a.bprefix[b], p1 = a.bprefix[b + 1];
+            const uint64_t c0 = dmax<uint64_t>(lo, p0), c1 = dmin<uint64_t>(hi, p1);
+            if (c0 < c1) atomicAdd(&a.tpairs[b], (unsigned long long)((c1 - 1 - p0) / HUF_SUB_TILE - (c0 - p0) / HUF_SUB_TILE + 1));
+        }
+    }
 }
 
-/* One thread per block: untouched, direct or staged. */
+/* One thread per block: untouched, direct, staged - or, for the tile route, served by tiles: a block that would be
+ * staged, whose header length is the layout's (the sub-index rows are addressed by it), whose tree has more than one
+ * leaf (the encoder writes no rows for one-symbol blocks) and over which the ranges make no more (range, tile) pairs
+ * than it has tiles - the tile route then decodes no more symbols than the block has. */
 __global__ __launch_bounds__(256) void drange_class_kernel(DecRangeArgs a)
 {
     asm volatile("; one VGPR more than the kernel uses (the build's ISA check: a 64-bit shift by the last of sixteen)" ::: "v16");
@@ -130,9 +156,24 @@ __global__ __launch_bounds__(256) void drange_class_kernel(DecRangeArgs a)
             rel = a.out_offsets[i] + (p - lo);
         }
     }
+    if (kind == DRANGE_STAGED && a.tpairs) {
+        const uint64_t pairs = a.tpairs[b];
+        const uint64_t ntiles = (m.block_len + HUF_SUB_TILE - 1) / HUF_SUB_TILE;
+        if (b * a.blocksize < a.raw_size && m.block_len == dmin<uint64_t>(a.blocksize, a.raw_size - b * a.blocksize) &&
+            m.leaf < 0 && pairs <= ntiles) {
+            kind = DRANGE_TILES;
+            a.dmeta[b].block_len = 0;
+            atomicAdd(&a.counters[4], 1ull);
+            atomicAdd(&a.counters[5], (unsigned long long)pairs);
+        }
+    }
     if (kind == DRANGE_STAGED) {
         rel = atomicAdd(&a.counters[0], 1ull);
         atomicMax(&a.counters[1], (unsigned long long)m.block_len);
+    }
+    {   /* (one addition a wave: a long range is thousands of direct blocks) */
+        const unsigned long long dm = __ballot(kind == DRANGE_DIRECT);
+        if (dm != 0ull && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(dm)) atomicAdd(&a.counters[3], (unsigned long long)__builtin_popcountll(dm));
     }
     a.kind[b] = kind;
     a.rel[b] = rel;

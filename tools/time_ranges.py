@@ -1,6 +1,7 @@
 """hufgpu_decode_ranges against what the API offered before it (GPU): byte ranges out of one compressed buffer.
 
     python tools/time_ranges.py [--runs 5] [--mib 1024] [--out profiles/ranges/time_ranges.txt]
+    python tools/time_ranges.py --tiles-only [--out profiles/ranges/time_ranges_tiles.txt]
 
 1 GiB of zipf255 bytes in 64 KiB blocks, device-resident.  R = 1, 64, 4096 random ranges of 4 KiB, of 64 KiB at
 unaligned positions, and of 16 MiB, slots back to back; with and without the encoder's sub-index.  Against
@@ -10,6 +11,11 @@ unaligned positions, and of 16 MiB, slots back to back; with and without the enc
 Every figure is the median of --runs warm runs with [min, max]; the slots of every variant are compared with slices of
 the input.  Cases whose output would pass 8 GiB are left out.  Last: the single range [0, N) - every block direct -
 against hufgpu_decode / hufgpu_decode_sub of the same stream in the same process.
+
+The sub=1 lines carry a column for HUFGPU_RANGES_TILES (cut blocks decoded by the sub-index tile, not whole), and the
+tile lines - all that --tiles-only runs - set the call with the flag beside the same call without it, alternating, in
+the same process: 4 096 x 64 B and 4 096 x 4 KiB out of 64 KiB blocks, 1 x 4 KiB and 64 x 4 KiB out of the same bytes
+written as ONE block (blocksize = 0), each with the route hufgpu_ranges_counters() reports.
 """
 import argparse
 import ctypes as C
@@ -26,6 +32,7 @@ sys.path.insert(0, ROOT)
 from libhuffman_amd.codec import GpuCodec  # noqa: E402
 
 BS = 65536
+TILES = 4               # HUFGPU_RANGES_TILES
 OUT_CAP = 8 << 30
 
 
@@ -50,24 +57,24 @@ def fmt(s):
 
 
 class Setup:
-    def __init__(self, codec, n):
-        self.codec, self.n = codec, n
-        self.data = codec.fill(torch.empty(n, dtype=torch.uint8, device="cuda"), "zipf255")
-        self.sub = codec.new_sub_index(n, BS)
-        self.stream, self.offs, self.length = codec.encode(self.data, BS, sub_index=self.sub)
-        self.nb = codec.block_count(n, BS)
-        self.whole = torch.empty(n, dtype=torch.uint8, device="cuda")
+    def __init__(self, codec, n, bs=BS, data=None):
+        self.codec, self.n, self.bs = codec, n, bs
+        self.data = codec.fill(torch.empty(n, dtype=torch.uint8, device="cuda"), "zipf255") if data is None else data
+        self.sub = codec.new_sub_index(n, bs)
+        self.stream, self.offs, self.length = codec.encode(self.data, bs, sub_index=self.sub)
+        self.nb = codec.block_count(n, bs)
+        self.whole = torch.empty(n, dtype=torch.uint8, device="cuda") if data is None else None
 
 
-def ranges_call(s, lo, hi, oo, out, sub):
+def ranges_call(s, lo, hi, oo, out, sub, flags=0):
     lib, ctx = s.codec.lib, s.codec._ctx
     r = len(lo)
     errs, raws = (C.c_int32 * r)(), (C.c_uint64 * r)()
 
     def fn():
         rc = lib.hufgpu_decode_ranges(ctx, s.stream.data_ptr(), s.length, s.offs.data_ptr(), s.nb, r, lo, hi, oo,
-                                      s.sub.data_ptr() if sub else None, s.n if sub else 0, BS if sub else 0,
-                                      out.data_ptr(), 0, errs, raws, None)
+                                      s.sub.data_ptr() if sub else None, s.n if sub else 0, s.bs if sub else 0,
+                                      out.data_ptr(), flags, errs, raws, None)
         assert rc == 0
     return fn
 
@@ -133,6 +140,12 @@ def case(s, r, size, aligned, runs, lines):
         fn()
         check(s, ranges, oo_l, out, "decode_ranges")
         res["new", sub] = stats(timed(fn, runs))
+        if sub:
+            out.zero_()
+            fn = ranges_call(s, lo, hi, oo, out, sub, TILES)
+            fn()
+            check(s, ranges, oo_l, out, "decode_ranges, tiles")
+            res["tiles"] = stats(timed(fn, runs))
         out.zero_()
         fn = whole_call(s, sub, ranges, oo_l, out)
         fn()
@@ -145,7 +158,8 @@ def case(s, r, size, aligned, runs, lines):
     loop = stats(timed(fn, runs))
     for sub in (False, True):
         new, whole = res["new", sub], res["whole", sub]
-        lines.append(f"R={r:5d} x {size:9d} B {'aligned  ' if aligned else 'unaligned'} sub={int(sub)}  ranges {fmt(new)}   "
+        flag = f"tiles {fmt(res['tiles'])} = {new[0] / res['tiles'][0]:6.2f}x   " if sub else ""
+        lines.append(f"R={r:5d} x {size:9d} B {'aligned  ' if aligned else 'unaligned'} sub={int(sub)}  ranges {fmt(new)}   {flag}"
                      f"(a) whole + slices {fmt(whole)} = {whole[0] / new[0]:8.1f}x   (b) loop {fmt(loop)} = {loop[0] / new[0]:8.1f}x")
         print(lines[-1], flush=True)
 
@@ -166,22 +180,57 @@ def whole_range(s, runs, lines):
         print(lines[-1], flush=True)
 
 
+def tile_line(s, r, size, runs, lines, what):
+    """the same call without and with the flag, alternating: `runs` warm runs of each"""
+    rng = np.random.default_rng(r * 17 + size)
+    los = [int(x) | 1 for x in rng.integers(0, s.n - size - 1, r)]
+    ranges = [(x, x + size) for x in los]
+    oo_l = [i * size for i in range(r + 1)]
+    lo, hi, oo = (C.c_uint64 * r)(*los), (C.c_uint64 * r)(*[x + size for x in los]), (C.c_uint64 * (r + 1))(*oo_l)
+    out = torch.empty(r * size, dtype=torch.uint8, device="cuda")
+    fns, ts, route = {}, {0: [], TILES: []}, {}
+    for flags in (0, TILES):
+        out.zero_()
+        fns[flags] = ranges_call(s, lo, hi, oo, out, True, flags)
+        fns[flags]()
+        check(s, ranges, oo_l, out, f"{what}, flags {flags}")
+        route[flags] = s.codec.ranges_counters()[:5]
+    for _ in range(runs):
+        for flags in (0, TILES):
+            ts[flags] += timed(fns[flags], 1)
+    plain, tiles = stats(ts[0]), stats(ts[TILES])
+    lines.append(f"{what}: R={r:5d} x {size:5d} B  without the flag {fmt(plain)}   with {fmt(tiles)} = {plain[0] / tiles[0]:7.2f}x   "
+                 f"(direct, staged, tiles, items, failed) {route[0]} -> {route[TILES]}")
+    print(lines[-1], flush=True)
+
+
+def tile_lines(s, runs, lines):
+    tile_line(s, 4096, 64, runs, lines, "blocks of 64 KiB")
+    tile_line(s, 4096, 4096, runs, lines, "blocks of 64 KiB")
+    one = Setup(s.codec, s.n, 0, s.data)
+    tile_line(one, 1, 4096, runs, lines, "ONE block        ")
+    tile_line(one, 64, 4096, runs, lines, "ONE block        ")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--mib", type=int, default=1024)
     ap.add_argument("--out", default="")
+    ap.add_argument("--tiles-only", action="store_true", help="only the lines that compare HUFGPU_RANGES_TILES with the same call without it")
     a = ap.parse_args()
     codec = GpuCodec(0)
     s = Setup(codec, a.mib << 20)
     lines = [f"time_ranges.py: {torch.cuda.get_device_name(0)}, {a.mib} MiB of zipf255 in blocks of {BS}, median of {a.runs} warm runs "
              "[min, max]; a call = everything up to the synchronised result, slots on the device"]
     print(lines[0], flush=True)
-    for size, aligned in ((4096, True), (65536, False), (16 << 20, False)):
-        for r in (1, 64, 4096):
-            if size <= s.n:
-                case(s, r, size, aligned, a.runs, lines)
-    whole_range(s, a.runs, lines)
+    if not a.tiles_only:
+        for size, aligned in ((4096, True), (65536, False), (16 << 20, False)):
+            for r in (1, 64, 4096):
+                if size <= s.n:
+                    case(s, r, size, aligned, a.runs, lines)
+        whole_range(s, a.runs, lines)
+    tile_lines(s, a.runs, lines)
     codec.close()
     if a.out:
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
