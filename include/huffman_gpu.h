@@ -260,6 +260,53 @@ int hufgpu_decode_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t strea
                          int32_t *range_errs, uint64_t *range_raw_lens, void *stream);
 
 /*
+ * GATHER: records whose positions are on the device - an index lookup, a sampler or a join produced them one kernel
+ * earlier.  hufgpu_decode_ranges() takes host arrays and waits for the device twice; this call reads nothing of the
+ * records on the host, never waits, writes no host memory and only enqueues on `stream` (NULL = the context's): the
+ * host knows nrecords and max_len - the sizes of the caller's arrays - and nothing else.  On the device the records are
+ * grouped by block, so a block's tables are built once however many records fall into it.  There is no CPU path.
+ *
+ *   record i      : bytes [d_pos[i], d_pos[i] + len_i) of the original data, len_i = d_len[i] or, with d_len = NULL,
+ *                   max_len for every record.  Its slot is d_out + i * out_stride (out_stride >= max_len; any alignment
+ *                   of d_out, any stride).  Records may overlap, repeat and come in any order.  A record that reaches
+ *                   past raw_size is cut there: d_raw_lens[i] (optional) says so, with status 0.
+ *   positions     : are the layout's: block b holds [b * blocksize, b * blocksize + min(blocksize, raw_size - b *
+ *                   blocksize)) - for a stream of hufgpu_encode_sub() the positions of the original data.  No header is
+ *                   read to find a record's blocks; a touched block whose header gives another length is not served.
+ *                   (A batch's stream with (nblocks * row_blocksize, row_blocksize): block b's bytes are addressed from
+ *                   b * row_blocksize, records that touch an item's short last block are not served.)
+ *   d_sub_index   : required, with (raw_size, blocksize) as in hufgpu_decode_sub().  The call carries the statement of
+ *                   HUFGPU_RANGES_TILES: the sub-index is THIS stream's own.  Points 1-4 of the TILES paragraph above
+ *                   hold word for word, with "slot" = the first len_i bytes of slot i; no other byte is ever written.
+ *   d_errs[i]     : 0 - the record's bytes are delivered and are those of hufgpu_decode_ranges() with the flag.
+ *                   HUF_ERROR_INVALID_ARGUMENT - len_i > max_len; nothing is written for it.
+ *                   HUF_ERROR_READ_WRITE - a check of the tile route failed in a block the record touches (the tile
+ *                   start outside the payload, the bit sums, a group not taking its bits, the claimed lengths not the
+ *                   tree's), or such a block cannot be served by tiles (its header does not parse under `flags`, its
+ *                   block_len is not the layout's, tree_len reaches past the block's record).
+ *                   Any non-zero status means "not served here": hufgpu_decode_ranges() without the flag gives the
+ *                   authoritative bytes and error; bytes inside that record's cut length are unspecified.  There is no
+ *                   fail-over inside the call (it would need a host decision).  A record over several blocks gets the
+ *                   worst status of its parts; the statuses are zeroed by the call's first launch.
+ *   one-symbol blocks (a tree of one leaf; the encoder writes no sub-index rows for them) ARE served: once the header
+ *                   is checked and the record's own payload bits are seen to be 0, the slot part is a fill.
+ *   flags         : HUFGPU_RELAXED_TREE as for hufgpu_decode().
+ *
+ * Argument errors - no context, a NULL d_stream / d_block_offsets / d_pos / d_out / d_errs, out_stride < max_len, a
+ * missing or misaligned sub-index, (raw_size, blocksize) that do not give nblocks, more than 2^32 - 1 (record, block)
+ * parts by the bound nrecords * ((max_len + blocksize - 2) / blocksize + 1) - return HUF_ERROR_INVALID_ARGUMENT before
+ * anything is enqueued.  nrecords = 0 and max_len = 0 are success with nothing enqueued.  The workspaces are the
+ * context's, sized by those bounds and doubled when they grow (only then does the call wait); two calls back to back on
+ * one stream are safe, calls on different streams of one context are not.
+ */
+int hufgpu_gather(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                  const uint64_t *d_block_offsets, uint64_t nblocks,
+                  const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                  uint64_t nrecords, const uint64_t *d_pos, const uint32_t *d_len, uint32_t max_len,
+                  void *d_out, uint64_t out_stride,
+                  int32_t *d_errs, uint32_t *d_raw_lens, uint32_t flags, void *stream);
+
+/*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from
  * another rank, or encoded here by a caller that did not keep the 7 % of side data.  hufgpu_encode_sub() writes the
  * sub-index as a by-product of packing; these three rebuild exactly that - the same entries, entry for entry

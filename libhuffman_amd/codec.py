@@ -321,6 +321,47 @@ class GpuCodec:
         self._check(self.lib.hufgpu_ranges_counters(self._ctx, c), "counter readout failed")
         return tuple(int(x) for x in c)
 
+    # -- gather: records whose positions are on the GPU, enqueue-only ------------------------------
+    def gather(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, positions: torch.Tensor,
+               lengths, *, sub_index: torch.Tensor, raw_size: int, blocksize: int, max_len: int | None = None,
+               out: torch.Tensor | None = None, relaxed: bool = False):
+        """Record i = bytes [positions[i], positions[i] + length_i) of the original data into out[i, :length_i], on
+        torch's current stream and without a synchronisation (hufgpu_gather): `positions` is a CUDA int64 / uint64
+        tensor, `lengths` an int (every record that long) or a CUDA int32 tensor, with `max_len` their host-known
+        bound.  `sub_index` is vouched to be this stream's own (the TILES contract of include/huffman_gpu.h).
+        `out`: uint8 [nrecords, >= max_len], rows at any stride and alignment; made when not given.  Returns
+        (out, errs, raw_lens), CUDA tensors: per record 0, or the status that says "not served here: ask
+        decode_ranges" (HUF_ERROR_READ_WRITE; HUF_ERROR_INVALID_ARGUMENT for a length above max_len), and the
+        record's length cut at raw_size.  Nothing is raised for a record."""
+        assert positions.is_cuda and positions.dtype in (torch.int64, torch.uint64) and positions.dim() == 1
+        positions = positions.contiguous()
+        n = positions.numel()
+        if isinstance(lengths, torch.Tensor):
+            assert max_len is not None, "lengths on the device need max_len, their bound"
+            assert lengths.is_cuda and lengths.dtype == torch.int32 and lengths.numel() == n
+            lengths = lengths.contiguous()
+            len_ptr = lengths.data_ptr() if n else None
+        else:
+            max_len = int(lengths) if max_len is None else int(max_len)
+            assert int(lengths) == max_len, "a fixed record size is max_len"
+            len_ptr = None
+        max_len = int(max_len)
+        if out is None:
+            out = torch.empty((n, max_len), dtype=torch.uint8, device=self.tdev)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.dim() == 2 and out.size(0) == n and out.size(1) >= max_len
+        assert out.size(1) <= 1 or out.stride(1) == 1
+        stride = out.stride(0) if n > 1 else max(out.stride(0), out.size(1))
+        errs = torch.zeros(n, dtype=torch.int32, device=self.tdev)
+        raw_lens = torch.zeros(n, dtype=torch.int32, device=self.tdev)
+        err = self.lib.hufgpu_gather(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
+                                     offsets.data_ptr(), nblocks, sub_index.data_ptr(), raw_size, blocksize, n,
+                                     positions.data_ptr() if n else None, len_ptr, max_len,
+                                     out.data_ptr() if out.numel() else None, stride, errs.data_ptr() if n else None,
+                                     raw_lens.data_ptr() if n else None,
+                                     _native.RELAXED_TREE if relaxed else _native.STRICT_TREE, self._stream())
+        self._check(err, "Failed to enqueue the gather")
+        return out, errs, raw_lens
+
     # -- overwrite: bytes [lo, hi) of the original data replaced in one indexed stream ---------------
     def update_ranges(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, ranges,
                       data: torch.Tensor, src_offsets=None, sub_index: torch.Tensor | None = None, raw_size: int = 0,

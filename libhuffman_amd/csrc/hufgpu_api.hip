@@ -129,6 +129,15 @@ struct hufgpu_ctx {
     uint8_t *d_rscratch;
     uint64_t rscratch_bytes;
 
+    /* hufgpu_gather (kernels/gather.hpp): part counts and cursors per block, the list of touched blocks, the scan of the
+     * counts and its grand total, the parts */
+    uint64_t gws_blocks, gws_parts;
+    uint32_t *d_gcnt, *d_glist;
+    TwoLevel gat_scan;
+    uint64_t *d_gtotal;
+    void *d_gparts;
+    int cus;                                  /* compute units of the device */
+
     /* the sub-index builders (kernels/sub_build.hpp): what their kernels hand to one another, per block and per chunk */
     uint64_t sbws_blocks, sbws_chunks;
     uint32_t *d_sb_state;
@@ -224,6 +233,7 @@ extern "C" int hufgpu_ctx_create(hufgpu_ctx_t **out, int device)
     hufgpu_ctx *ctx = (hufgpu_ctx *)calloc(1, sizeof(hufgpu_ctx));
     if (!ctx) return HUFE_MEMORY;
     ctx->device = device;
+    ctx->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     HIP_OK(NULL, hipSetDevice(device));
     ctx->stream = NULL;   /* the device's default stream: ordered with every blocking stream (torch's default included) */
     HIP_OK(ctx, hipMalloc((void **)&ctx->d_result, 8 * sizeof(uint64_t)));
@@ -308,6 +318,16 @@ static void free_range_ws(hufgpu_ctx *c)
     c->rws_blocks = c->rws_ranges = 0;
 }
 
+static void free_gather_ws(hufgpu_ctx *c, int which)
+{
+    if (which & 1) {
+        if (c->gws_blocks) free_two_level(&c->gat_scan);
+        (void)hipFree(c->d_gcnt); (void)hipFree(c->d_glist);
+        c->d_gcnt = c->d_glist = NULL; c->gws_blocks = 0;
+    }
+    if (which & 2) { (void)hipFree(c->d_gparts); c->d_gparts = NULL; c->gws_parts = 0; }
+}
+
 static void free_range_scratch(hufgpu_ctx *c)
 {
     (void)hipFree(c->d_rscratch);
@@ -372,6 +392,8 @@ extern "C" int hufgpu_ctx_destroy(hufgpu_ctx_t *ctx)
     free_batch_ws(ctx);
     free_range_ws(ctx);
     free_range_scratch(ctx);
+    free_gather_ws(ctx, 3);
+    (void)hipFree(ctx->d_gtotal);
     (void)hipFree(ctx->d_rcounters);
     free_sub_build_ws(ctx, 3);
     (void)hipFree(ctx->d_sb_unbuilt);
@@ -2092,6 +2114,125 @@ extern "C" int hufgpu_decode_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uin
         set_err(ctx, "decode_ranges: range %llu failed with error %d (%llu ranges in all)", (unsigned long long)first_range, first_err,
                 (unsigned long long)nranges);
     return first_err;
+}
+
+/* ======================================================================================
+ * Records at device-resident positions (include/huffman_gpu.h, kernels/gather.hpp): enqueue-only
+ * ==================================================================================== */
+
+/* sized by bounds the host knows - the blocks, records x the parts a record can have - and doubled when they grow */
+static int ensure_gather_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t nparts)
+{
+    if (!c->d_gtotal) HIP_OK(c, hipMalloc((void **)&c->d_gtotal, sizeof(uint64_t)));
+    if (nblocks > c->gws_blocks) {
+        HIP_OK(c, hipDeviceSynchronize());
+        const uint64_t cap = (nblocks > 2 * c->gws_blocks ? nblocks : 2 * c->gws_blocks) + 16;
+        free_gather_ws(c, 1);
+        HIP_OK(c, hipMalloc((void **)&c->d_gcnt, 2 * cap * sizeof(uint32_t)));
+        HIP_OK(c, hipMalloc((void **)&c->d_glist, cap * sizeof(uint32_t)));
+        const int rc = alloc_two_level(c, &c->gat_scan, cap, false);
+        if (rc) return rc;
+        c->gws_blocks = cap;
+    }
+    if (nparts > c->gws_parts) {
+        HIP_OK(c, hipDeviceSynchronize());
+        const uint64_t cap = (nparts > 2 * c->gws_parts ? nparts : 2 * c->gws_parts) + 16;
+        free_gather_ws(c, 2);
+        HIP_OK(c, hipMalloc(&c->d_gparts, cap * sizeof(GatherPart)));
+        c->gws_parts = cap;
+    }
+    return HUFE_OK;
+}
+
+extern "C" int hufgpu_gather(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                             uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                             uint64_t nrecords, const uint64_t *d_pos, const uint32_t *d_len, uint32_t max_len, void *d_out,
+                             uint64_t out_stride, int32_t *d_errs, uint32_t *d_raw_lens, uint32_t flags, void *stream)
+{
+    if (nrecords == 0 || max_len == 0) return HUFE_OK;
+    if (!d_stream || !d_block_offsets || !d_pos || !d_out || !d_errs) {
+        set_err(ctx, "gather: the stream, its block index, d_pos, d_out and d_errs are required");
+        return HUFE_ARGUMENT;
+    }
+    if (out_stride < max_len) {
+        set_err(ctx, "gather: out_stride %llu is less than max_len %u", (unsigned long long)out_stride, max_len);
+        return HUFE_ARGUMENT;
+    }
+    if (!d_sub_index || ((uintptr_t)d_sub_index & 7u)) {
+        set_err(ctx, "gather: needs the stream's sub-index in an 8-byte aligned buffer");
+        return HUFE_ARGUMENT;
+    }
+    if (blocksize == 0) blocksize = raw_size;
+    if (raw_size == 0 || blocksize > HUFGPU_MAX_BLOCK || hufgpu_block_count(raw_size, blocksize) != nblocks || nblocks > 0x7fffffffull) {
+        set_err(ctx, "gather: (raw_size, blocksize) must be those of the encode that wrote these %llu blocks", (unsigned long long)nblocks);
+        return HUFE_ARGUMENT;
+    }
+    /* what the host knows of the records: how many, and how long at most - the parts a record can have, the tiles a part */
+    uint64_t per_record = ((uint64_t)max_len + blocksize - 2) / blocksize + 1;
+    if (per_record > nblocks) per_record = nblocks;
+    const uint64_t nparts = nrecords > 0x7fffffffull ? ~0ull : nrecords * per_record;
+    if (nparts > 0xffffffffull) {
+        set_err(ctx, "gather: %llu records of up to %u bytes are more than 2^32 - 1 (record, block) parts", (unsigned long long)nrecords, max_len);
+        return HUFE_ARGUMENT;
+    }
+    if (!ctx) {
+        set_err(NULL, "gather: needs a context (there is no CPU path)");
+        return HUFE_ARGUMENT;
+    }
+    HIP_OK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = pick_stream(ctx, stream);
+    const int rc = ensure_gather_ws(ctx, nblocks, nparts);
+    if (rc) return rc;
+
+    const uint64_t tiles_per_block = (blocksize + HUF_SUB_TILE - 1) / HUF_SUB_TILE;
+    uint64_t tmax = ((uint64_t)max_len + HUF_SUB_TILE - 2) / HUF_SUB_TILE + 1;
+    if (tmax > tiles_per_block) tmax = tiles_per_block;
+    /* The serving grid: no wider than the touched blocks can be, and a few workgroups a compute unit (three fit its LDS).
+     * Where the stream has fewer blocks than that, a block's items are dealt to several workgroups - one item a wave,
+     * as far as the grid goes: with blocksize = 0 every record lies in the one block. */
+    const uint64_t width = 4ull * (uint64_t)ctx->cus;
+    uint64_t shares = 1;
+    if (nblocks < width) {
+        shares = (nparts * tmax + GATHER_WAVES - 1) / GATHER_WAVES;
+        if (shares > width / nblocks) shares = width / nblocks;
+        if (shares < 1) shares = 1;
+    }
+    uint64_t grid = (nblocks < nparts ? nblocks : nparts) * shares;
+    if (grid > width) grid = width;
+
+    GatherArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.stream = (const uint8_t *)d_stream;
+    ga.stream_len = stream_len;
+    ga.offsets = d_block_offsets;
+    ga.nblocks = nblocks;
+    ga.sub = sub_index_view((void *)d_sub_index, raw_size, blocksize);
+    ga.raw_size = raw_size;
+    ga.bsize = blocksize;
+    ga.max_tree = (flags & HUFGPU_RELAXED_TREE) ? HUF_TREE_MAX : HUF_TREE_STRICT;
+    ga.max_len = max_len;
+    ga.nrecords = nrecords;
+    ga.pos = d_pos;
+    ga.len = d_len;
+    ga.out = (uint8_t *)d_out;
+    ga.stride = out_stride;
+    ga.errs = d_errs;
+    ga.raw_lens = d_raw_lens;
+    ga.cnt = ctx->d_gcnt;
+    ga.cur = ctx->d_gcnt + nblocks;
+    ga.scan = ctx->gat_scan;
+    ga.scan.total = ctx->d_gtotal;
+    ga.list = ctx->d_glist;
+    ga.parts = (GatherPart *)ctx->d_gparts;
+    ga.shares = (uint32_t)shares;
+    ga.tmax = (uint32_t)tmax;
+    HIP_OK(ctx, hipMemsetAsync(ctx->d_gcnt, 0, 2 * nblocks * sizeof(uint32_t), s));
+    gather_mark_kernel<<<dim3(grid256(nrecords)), dim3(256), 0, s>>>(ga);
+    gather_scan_kernel<<<dim3((unsigned)((nblocks + SCAN_GROUP - 1) / SCAN_GROUP)), dim3(SCAN_GROUP), 0, s>>>(ga);
+    gather_place_kernel<<<dim3(grid256(nblocks > nrecords ? nblocks : nrecords)), dim3(256), 0, s>>>(ga);
+    gather_serve_kernel<<<dim3((unsigned)grid), dim3(GATHER_THREADS), 0, s>>>(ga);
+    HIP_OK(ctx, hipGetLastError());
+    return HUFE_OK;
 }
 
 /* ======================================================================================

@@ -44,6 +44,7 @@
 #include "kernels/batch.hpp"
 #include "kernels/ranges.hpp"
 #include "kernels/range_tiles.hpp"
+#include "kernels/gather.hpp"
 #include "kernels/sub_build.hpp"
 #include "kernels/update.hpp"
 #include "kernels/append.hpp"
