@@ -18,11 +18,11 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 SO_PATH = os.environ.get("HUF_LIB_PATH") or os.path.join(PKG, "libhuffman.so")   # override: tooling experiments only
 SOURCES = ["hufgpu_api.hip", "huf_host.cpp", "hufgpu_sharded.hip"]
-KERNEL_PARTS = ["util", "histogram", "tree", "offsets", "hist_tree", "hist_lanes", "pack", "hist_chunk", "pack_chunk", "decode", "decode_sub", "decode_fast", "decode_regs", "spec_index", "discover", "fill", "batch", "ranges", "range_tiles", "gather", "sub_build", "update", "append"]
 DEPENDS = SOURCES + ["hufgpu_kernels.hip", "hufgpu_common.h",
                      os.path.join("..", "..", "include", "huffman.h"),
                      os.path.join("..", "..", "include", "huffman_gpu.h")] + \
-          [os.path.join("kernels", part + ".hpp") for part in KERNEL_PARTS]
+          [os.path.join(d, f) for d in ("kernels", "host")          # every part of the two translation units
+           for f in sorted(os.listdir(os.path.join(CSRC, d))) if f.endswith(".hpp")]
 
 
 def _hipcc() -> str:

@@ -47,7 +47,7 @@ namespace hufgpu {
 #define HL_LDS_BYTES (HUF_NSYM * 32 * 4)
 #define HL_MAX_PER_COUNTER 65535u      /* what a 16-bit counter holds: a counter sees the bytes of one lane of all the waves - a 64th of what a
                                           workgroup counts, + the up to 31 bytes a lane takes in front of and behind the vectors (asserted
-                                          at the kernels: hufgpu_api.hip's block sizes for them) */
+                                          at the kernels: the block sizes host/encode.hpp, host/batch.hpp and host/update.hpp launch them for) */
 
 /* col = (lane & 31) << 3 (twice the column's byte offset), one = 1 or 1 << 16 (the lane's half of the word) */
 __device__ __forceinline__ void hl_add_dword(uint8_t *hl_lds, uint32_t w, uint32_t col, uint32_t one)

@@ -1,7 +1,7 @@
 """A CPU reference of the encoder's sub-index (hufgpu_encode_sub, kernels/pack.hpp and pack_chunk.hpp), and the table of
 cases test_gpu_sub_index_content.py compares the encoder with.  Test infrastructure (CPU, numpy).
 
-Layout (hufgpu_api.hip, sub_index_view / hufgpu_sub_index_bytes).  blocksize 0 means one block of all n symbols.  With
+Layout (csrc/host/encode.hpp, sub_index_view / hufgpu_sub_index_bytes).  blocksize 0 means one block of all n symbols.  With
 nb blocks, tpb = ceil(blocksize / 2 048) tiles and gpb = ceil(blocksize / 32) groups rounded up to a multiple of 8 a block,
 the buffer holds, in this order:
   tile_bits   u64[nb][tpb]    the payload bit where tile t of the block starts (symbol 2 048 t)
@@ -36,7 +36,7 @@ GROUP = 32                              # HUF_SUB_GROUP (pack.hpp)
 TILE = 2048                             # HUF_SUB_TILE
 NSYM = 256
 
-# path thresholds of encode_impl (hufgpu_api.hip)
+# path thresholds of encode_impl (csrc/host/encode.hpp)
 HL_MIN_BLOCK = 32768                    # kernels/hist_lanes.hpp: below it the fused hist_tree_kernel
 SHORT_MAX = 121392                      # the SHORT pack_kernel: no code longer than 24 bits
 CHUNKED_FROM = 1 << 21                  # HUF_CHUNKED_FROM (kernels/hist_chunk.hpp): pack_chunk_kernel
