@@ -21,7 +21,7 @@ SOURCES = ["hufgpu_api.hip", "huf_host.cpp", "hufgpu_sharded.hip"]
 DEPENDS = SOURCES + ["hufgpu_kernels.hip", "hufgpu_common.h",
                      os.path.join("..", "..", "include", "huffman.h"),
                      os.path.join("..", "..", "include", "huffman_gpu.h")] + \
-          [os.path.join(d, f) for d in ("kernels", "host")          # every part of the two translation units
+          [os.path.join(d, f) for d in ("kernels", "host", "drop_in")         # every part of the two translation units
            for f in sorted(os.listdir(os.path.join(CSRC, d))) if f.endswith(".hpp")]
 
 
