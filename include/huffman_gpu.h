@@ -307,6 +307,55 @@ int hufgpu_gather(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
                   int32_t *d_errs, uint32_t *d_raw_lens, uint32_t flags, void *stream);
 
 /*
+ * FIND BYTES: the calls above take positions; this one produces them.  For a set of byte values it reports how many bytes of
+ * each block are in the set and at which positions of the original data they lie - the newlines of a compressed log, the
+ * separators of a table - straight from stream, block index and sub-index: every block is decoded once, no decoded byte
+ * is written to device memory (a match mask of one bit per byte, an eighth of the data, lives in a context workspace),
+ * and like hufgpu_gather() the call never waits, writes no host memory and only enqueues on `stream` (NULL = the
+ * context's): find_bytes -> a device op -> gather is a pipeline without a host wait.  There is no CPU path.
+ *
+ *   set           : a HOST array of 32 bytes, a 256-bit set: byte value v is looked for when bit v & 7 of set[v >> 3] is 1.
+ *                   It is read before the call returns.  The empty set and the full set are valid.
+ *   positions     : are the layout's, as in hufgpu_gather(): block b holds [b * blocksize, b * blocksize + min(blocksize,
+ *                   raw_size - b * blocksize)), blocksize = 0 means one block; (raw_size, blocksize) must give nblocks.  A
+ *                   block whose header gives another block_len is not served.  (A batch's stream with (nblocks *
+ *                   row_blocksize, row_blocksize): full blocks are served and addressed from b * row_blocksize, the items'
+ *                   short last blocks are reported not served.)
+ *   d_sub_index   : required, with (raw_size, blocksize) as in hufgpu_decode_sub().  The caller vouches for NOTHING: every
+ *                   block is walked from payload bit 0 through every tile, so checks (a), (b), (c) of hufgpu_decode_sub()
+ *                   close their induction, and for ANY content of the buffer a block is either served exactly or
+ *                   reported as not served.
+ *   d_block_errs  : required, nblocks words.  0 - served.  HUF_ERROR_READ_WRITE - "not served here": the header does not
+ *                   parse under `flags`, block_len is not the layout's, the claimed code lengths are not the tree's, one
+ *                   of (a) / (b) / (c) fails, a walk leaves the tree or the payload.  hufgpu_decode_sub() gives the
+ *                   authoritative bytes and error for such a block; there is no fail-over inside the call (it would
+ *                   need a host decision).  The statuses are zeroed by the call's first enqueued operation.
+ *   d_block_counts: optional, nblocks words: the matches in block b; 0 for a block that is not served.
+ *   d_pos         : may be NULL when pos_cap = 0.  The positions of the matches of all SERVED blocks in ascending order:
+ *                   the first min(total, pos_cap) of them are written and nothing else - words from d_totals[1] on are
+ *                   untouched.
+ *   d_totals      : required, 4 words: [0] matches in served blocks (exact whatever pos_cap is), [1] positions written,
+ *                   [2] blocks not served, [3] 0.  One read says whether the answer is complete.
+ *   one-symbol blocks (a tree of one leaf; the encoder writes no sub-index rows for them) ARE served: the header is
+ *                   checked, the block's block_len payload bits are seen to be 0, the count is block_len or 0.
+ *   flags         : HUFGPU_RELAXED_TREE as for hufgpu_decode().
+ *
+ * Argument errors - no context, a NULL d_stream / d_block_offsets / set / d_totals / d_block_errs, pos_cap > 0 with a NULL
+ * d_pos, a missing or misaligned sub-index, (raw_size, blocksize) that do not give nblocks (or more than 2^31 - 1 tiles of
+ * 2 048 bytes) - return HUF_ERROR_INVALID_ARGUMENT before anything is enqueued.  nblocks = 0 (with raw_size = 0) is
+ * success: d_totals is zeroed and nothing else is enqueued.  The workspaces are the context's, sized by the layout and
+ * doubled when they grow (only then does the call wait); two calls back to back on one stream are safe, calls on different
+ * streams of one context are not.
+ */
+int hufgpu_find_bytes(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                      const uint64_t *d_block_offsets, uint64_t nblocks,
+                      const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                      const uint8_t set[32],
+                      uint64_t *d_pos, uint64_t pos_cap,
+                      uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                      uint32_t flags, void *stream);
+
+/*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from
  * another rank, or encoded here by a caller that did not keep the 7 % of side data.  hufgpu_encode_sub() writes the
  * sub-index as a by-product of packing; these three rebuild exactly that - the same entries, entry for entry

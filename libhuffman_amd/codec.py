@@ -362,6 +362,53 @@ class GpuCodec:
         self._check(err, "Failed to enqueue the gather")
         return out, errs, raw_lens
 
+    # -- find: where byte values lie in the original data, enqueue-only -------------------------------
+    @staticmethod
+    def byte_set(values) -> bytes:
+        """the 32-byte set of hufgpu_find_bytes: bit v & 7 of byte v >> 3 is 1 for every v in `values`"""
+        s = bytearray(32)
+        for v in bytes(values) if isinstance(values, (bytes, bytearray)) else values:
+            v = int(v)
+            if not 0 <= v <= 255:
+                raise ValueError(f"byte value {v} out of range")
+            s[v >> 3] |= 1 << (v & 7)
+        return bytes(s)
+
+    def find_bytes(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
+                   sub_index: torch.Tensor, raw_size: int, blocksize: int, values, max_positions: int = 0,
+                   block_counts: bool = False, relaxed: bool = False, out: torch.Tensor | None = None):
+        """The positions in the original data of the bytes whose value is in `values` (an iterable of ints or a
+        `bytes`), on torch's current stream and without a synchronisation (hufgpu_find_bytes): no decoded byte is
+        written to memory, and for any content of `sub_index` a block is served exactly or its status is non-zero.
+        Returns CUDA tensors (positions[max_positions] int64 - the first totals[1] are written, ascending -,
+        totals[4] = matches in served blocks, positions written, blocks not served, 0; block_errs[nblocks] int32,
+        0 or HUF_ERROR_READ_WRITE = "ask decode"; block_counts[nblocks] int64 or None).  `out`: the positions' buffer,
+        contiguous int64 [max_positions]; made when not given."""
+        st = self.byte_set(values)
+        max_positions = int(max_positions)
+        pos = torch.empty(max_positions, dtype=torch.int64, device=self.tdev) if out is None else out
+        assert pos.is_cuda and pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == max_positions and pos.is_contiguous()
+        totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
+        errs = torch.empty(nblocks, dtype=torch.int32, device=self.tdev)
+        counts = torch.empty(nblocks, dtype=torch.int64, device=self.tdev) if block_counts else None
+        err = self.lib.hufgpu_find_bytes(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
+                                         offsets.data_ptr() if nblocks else None, nblocks,
+                                         sub_index.data_ptr() if nblocks else None, raw_size, blocksize, st,
+                                         pos.data_ptr() if max_positions else None, max_positions,
+                                         counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(),
+                                         errs.data_ptr() if nblocks else None,
+                                         _native.RELAXED_TREE if relaxed else _native.STRICT_TREE, self._stream())
+        self._check(err, "Failed to enqueue the search")
+        return pos, totals, errs, counts
+
+    def count_bytes(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
+                    sub_index: torch.Tensor, raw_size: int, blocksize: int, values, relaxed: bool = False):
+        """How many bytes of the original data have a value in `values`: find_bytes without positions, enqueue-only.
+        Returns CUDA tensors (totals[4], block_errs[nblocks]) as find_bytes does."""
+        _, totals, errs, _ = self.find_bytes(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, values,
+                                             relaxed=relaxed)
+        return totals, errs
+
     # -- overwrite: bytes [lo, hi) of the original data replaced in one indexed stream ---------------
     def update_ranges(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, ranges,
                       data: torch.Tensor, src_offsets=None, sub_index: torch.Tensor | None = None, raw_size: int = 0,

@@ -107,6 +107,11 @@ struct hufgpu_ctx {
     void *d_gparts;
     int cus;                                  /* compute units of the device */
 
+    /* hufgpu_find_bytes (kernels/find.hpp): a match mask per group of 32 symbols, a count per tile, the scan of the counts */
+    uint64_t fws_words, fws_tiles;
+    uint32_t *d_fbitmap, *d_ftcnt;
+    TwoLevel find_scan;
+
     /* the sub-index builders (kernels/sub_build.hpp): what their kernels hand to one another, per block and per chunk */
     uint64_t sbws_blocks, sbws_chunks;
     uint32_t *d_sb_state;
@@ -307,6 +312,16 @@ static void free_gather_ws(hufgpu_ctx *c, int which)
     if (which & 2) { (void)hipFree(c->d_gparts); c->d_gparts = NULL; c->gws_parts = 0; }
 }
 
+static void free_find_ws(hufgpu_ctx *c, int which)
+{
+    if (which & 1) { (void)hipFree(c->d_fbitmap); c->d_fbitmap = NULL; c->fws_words = 0; }
+    if (which & 2) {
+        if (c->fws_tiles) free_two_level(&c->find_scan);
+        (void)hipFree(c->d_ftcnt);
+        c->d_ftcnt = NULL; c->fws_tiles = 0;
+    }
+}
+
 static void free_range_scratch(hufgpu_ctx *c)
 {
     (void)hipFree(c->d_rscratch);
@@ -373,6 +388,7 @@ extern "C" int hufgpu_ctx_destroy(hufgpu_ctx_t *ctx)
     free_range_scratch(ctx);
     free_gather_ws(ctx, 3);
     (void)hipFree(ctx->d_gtotal);
+    free_find_ws(ctx, 3);
     (void)hipFree(ctx->d_rcounters);
     free_sub_build_ws(ctx, 3);
     (void)hipFree(ctx->d_sb_unbuilt);
@@ -506,6 +522,28 @@ static int ensure_gather_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t nparts)
         free_gather_ws(c, 2);
         HIP_OK(c, hipMalloc(&c->d_gparts, cap * sizeof(GatherPart)));
         c->gws_parts = cap;
+    }
+    return HUFE_OK;
+}
+
+/* sized by the layout - mask words and tiles of all blocks - and doubled when they grow */
+static int ensure_find_ws(hufgpu_ctx *c, uint64_t nwords, uint64_t ntiles)
+{
+    if (nwords > c->fws_words) {
+        HIP_OK(c, hipDeviceSynchronize());
+        const uint64_t cap = (nwords > 2 * c->fws_words ? nwords : 2 * c->fws_words) + 16;
+        free_find_ws(c, 1);
+        HIP_OK(c, hipMalloc((void **)&c->d_fbitmap, cap * sizeof(uint32_t)));
+        c->fws_words = cap;
+    }
+    if (ntiles > c->fws_tiles) {
+        HIP_OK(c, hipDeviceSynchronize());
+        const uint64_t cap = (ntiles > 2 * c->fws_tiles ? ntiles : 2 * c->fws_tiles) + 16;
+        free_find_ws(c, 2);
+        HIP_OK(c, hipMalloc((void **)&c->d_ftcnt, cap * sizeof(uint32_t)));
+        const int rc = alloc_two_level(c, &c->find_scan, cap, false);
+        if (rc) return rc;
+        c->fws_tiles = cap;
     }
     return HUFE_OK;
 }

@@ -45,6 +45,7 @@ using namespace hufgpu;
 #include "host/batch.hpp"       /* hufgpu_encode_batch, hufgpu_decode_batch, the pinned staging area */
 #include "host/ranges.hpp"      /* hufgpu_decode_ranges */
 #include "host/gather.hpp"      /* hufgpu_gather */
+#include "host/find.hpp"        /* hufgpu_find_bytes */
 #include "host/update.hpp"      /* hufgpu_update_ranges, the row encoders */
 #include "host/append.hpp"      /* hufgpu_append, hufgpu_truncate */
 #include "host/sub_build.hpp"   /* hufgpu_sub_index_from_raw, hufgpu_decode_build_sub, hufgpu_build_sub_index */

@@ -15,6 +15,7 @@
  *            sub_tile_add_kernel for blocks of 2 MiB and more)
  *   overwrite of byte ranges: decode_prepare_kernel -> drange_plan / drange_mark -> upd_class -> the indexed decoders on
  *            the staged blocks -> upd_overlay -> hist_*_pairs -> upd_index -> pack_pairs, update_copy_kernel
+ *   byte values looked for (hufgpu_find_bytes): find_sub -> find_scan -> find_finish (-> find_emit), no decoded byte stored
  *   append / truncate in place: decode_prepare_kernel on the one block that is opened again -> app_plan -> the indexed
  *            decoders on it -> app_join -> hist_*_pairs -> app_index -> pack_pairs -> app_commit (-> app_sub_rows)
  *
@@ -45,6 +46,7 @@
 #include "kernels/ranges.hpp"
 #include "kernels/range_tiles.hpp"
 #include "kernels/gather.hpp"
+#include "kernels/find.hpp"
 #include "kernels/sub_build.hpp"
 #include "kernels/update.hpp"
 #include "kernels/append.hpp"
