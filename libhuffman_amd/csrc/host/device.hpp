@@ -2,6 +2,15 @@
    calibration, and the counters of diagnostic builds.  Part of hufgpu_api.hip (one translation unit). */
 #pragma once
 
+/* What the routes that serve straight from the sub-index are told of the stream and its layout (kernels/sub_tile.hpp):
+ * hufgpu_gather, hufgpu_find_bytes and the tile route of hufgpu_decode_ranges.  blocksize: the layout's, never 0. */
+static SubStream sub_stream_args(const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets, uint64_t nblocks,
+                                 const void *d_sub_index, uint64_t raw_size, uint64_t blocksize, uint32_t flags)
+{
+    return {(const uint8_t *)d_stream, stream_len, d_block_offsets, nblocks, sub_index_view((void *)d_sub_index, raw_size, blocksize),
+            raw_size, blocksize, max_tree_of(flags)};
+}
+
 extern "C" int hufgpu_fill(hufgpu_ctx_t *ctx, void *d_out, uint64_t n, int kind, uint64_t seed,
                            uint64_t first, void *stream)
 {

@@ -56,14 +56,7 @@ extern "C" int hufgpu_find_bytes(hufgpu_ctx_t *ctx, const void *d_stream, uint64
 
     FindArgs fa;
     memset(&fa, 0, sizeof(fa));
-    fa.stream = (const uint8_t *)d_stream;
-    fa.stream_len = stream_len;
-    fa.offsets = d_block_offsets;
-    fa.nblocks = nblocks;
-    fa.sub = sub_index_view((void *)d_sub_index, raw_size, blocksize);
-    fa.raw_size = raw_size;
-    fa.bsize = blocksize;
-    fa.max_tree = max_tree_of(flags);
+    fa.s = sub_stream_args(d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize, flags);
     fa.cpb = (uint32_t)cpb;
     for (int i = 0; i < 32; i++) fa.set[i >> 2] |= (uint32_t)set[i] << (8 * (i & 3));
     fa.bitmap = ctx->d_fbitmap;

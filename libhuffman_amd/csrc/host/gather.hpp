@@ -60,14 +60,7 @@ extern "C" int hufgpu_gather(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t s
 
     GatherArgs ga;
     memset(&ga, 0, sizeof(ga));
-    ga.stream = (const uint8_t *)d_stream;
-    ga.stream_len = stream_len;
-    ga.offsets = d_block_offsets;
-    ga.nblocks = nblocks;
-    ga.sub = sub_index_view((void *)d_sub_index, raw_size, blocksize);
-    ga.raw_size = raw_size;
-    ga.bsize = blocksize;
-    ga.max_tree = max_tree_of(flags);
+    ga.s = sub_stream_args(d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize, flags);
     ga.max_len = max_len;
     ga.nrecords = nrecords;
     ga.pos = d_pos;

@@ -175,11 +175,7 @@ extern "C" int hufgpu_decode_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uin
             if (range_hi[i] - range_lo[i] > longest_range) longest_range = range_hi[i] - range_lo[i];
         uint64_t tile_y = (longest_range / HUF_SUB_TILE + 2 + 31) / 32;
         if (tile_y > 1024) tile_y = 1024;
-        RangeTileArgs ta;
-        ta.stream = st;
-        ta.stream_len = stream_len;
-        ta.offsets = d_block_offsets;
-        ta.sub = sub;
+        const SubStream ta = sub_stream_args(st, stream_len, d_block_offsets, nb, d_sub_index, raw_size, blocksize, flags);
         drange_tiles_kernel<<<dim3((unsigned)nranges, (unsigned)tile_y), dim3(RTILE_THREADS), 0, s>>>(ra, ta);
     }
     /* (every touched block served by tiles: nothing for the block decoders to do) */

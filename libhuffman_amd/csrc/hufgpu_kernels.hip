@@ -15,6 +15,8 @@
  *            sub_tile_add_kernel for blocks of 2 MiB and more)
  *   overwrite of byte ranges: decode_prepare_kernel -> drange_plan / drange_mark -> upd_class -> the indexed decoders on
  *            the staged blocks -> upd_overlay -> hist_*_pairs -> upd_index -> pack_pairs, update_copy_kernel
+ *   served straight from stream, block index and sub-index, tile by tile (sub_tile.hpp: the one checked tile item):
+ *            drange_tiles_kernel, gather_serve_kernel, find_sub_kernel
  *   byte values looked for (hufgpu_find_bytes): find_sub -> find_scan -> find_finish (-> find_emit), no decoded byte stored
  *   append / truncate in place: decode_prepare_kernel on the one block that is opened again -> app_plan -> the indexed
  *            decoders on it -> app_join -> hist_*_pairs -> app_index -> pack_pairs -> app_commit (-> app_sub_rows)
@@ -37,6 +39,7 @@
 #include "kernels/pack_chunk.hpp"
 #include "kernels/decode.hpp"
 #include "kernels/decode_sub.hpp"
+#include "kernels/sub_tile.hpp"
 #include "kernels/decode_fast.hpp"
 #include "kernels/decode_regs.hpp"
 #include "kernels/spec_index.hpp"

@@ -50,6 +50,31 @@ __device__ __forceinline__ int single_leaf_symbol(const uint8_t *tree)
     return one ? (int)(uint8_t)e5[1] : -1;
 }
 
+/* A block's record [o0, o1) of the stream, o1 the index's next offset (cut at the stream's end here), parsed as
+ * src/decoder.c:218-252 does, with the reference's statuses in the reference's order. */
+struct BlockHeader {
+    uint64_t block_len;
+    int tree_len;
+    const uint8_t *tree, *pay;
+    uint64_t pay_bytes;
+};
+
+__device__ __forceinline__ int parse_block_header(const uint8_t *stream, uint64_t stream_len, uint64_t o0, uint64_t o1,
+                                                  int max_tree, BlockHeader &h)
+{
+    o1 = dmin<uint64_t>(o1, stream_len);
+    if (o0 > o1 || o1 - o0 < HUF_HEADER_FIXED) return HUFE_RW;                     /* decoder.c:220-234 short read */
+    int16_t tl;
+    load_header10(stream, stream_len, o0, h.block_len, tl);
+    if (tl < 0 || tl > max_tree) return HUFE_OVERFLOW;                             /* decoder.c:237-239 */
+    if (o1 - o0 < HUF_HEADER_FIXED + 2ull * (uint64_t)tl) return HUFE_RW;          /* :248-252 */
+    h.tree_len = tl;
+    h.tree = stream + o0 + HUF_HEADER_FIXED;
+    h.pay = h.tree + 2 * (int)tl;
+    h.pay_bytes = o1 - o0 - HUF_HEADER_FIXED - 2ull * (uint64_t)tl;
+    return HUFE_OK;
+}
+
 /* decode_prepare_kernel - header parse of src/decoder.c:218-252 for every indexed block, one block
  * per thread, and the sums of the block lengths (= where each block's output starts) as a
  * two-level prefix: a workgroup is one SCAN_GROUP.  result words: [0] unused, [1] total raw
@@ -75,28 +100,18 @@ __global__ __launch_bounds__(SCAN_GROUP) void decode_prepare_kernel(const uint8_
     m.leaf = -1;
     m.status = HUFE_OK;
     if (b < nblocks) {
-        const uint64_t o0 = offsets[b];
-        const uint64_t o1 = dmin<uint64_t>(offsets[b + 1], stream_len);
-        if (o0 > o1 || o1 - o0 < HUF_HEADER_FIXED) {
-            m.status = HUFE_RW;                                /* decoder.c:220-234 short read */
-        } else {
-            uint64_t bl;
-            int16_t tl;
-            load_header10(stream, stream_len, o0, bl, tl);
-            if (tl < 0 || tl > max_tree_len) m.status = HUFE_OVERFLOW;          /* decoder.c:237-239 */
-            else if (o1 - o0 < HUF_HEADER_FIXED + 2ull * (uint64_t)tl) m.status = HUFE_RW;   /* :248-252 */
+        BlockHeader h;
+        m.status = parse_block_header(stream, stream_len, offsets[b], offsets[b + 1], max_tree_len, h);
+        if (m.status == HUFE_OK) {
+            /* A block cannot hold more symbols than its payload has bits: a larger block_len (a
+             * damaged header) is decoded as far as the input goes and then fails like the
+             * reference's reader does at the end of its input (decoder.c:53-56). */
+            const uint64_t bl = dmin<uint64_t>(h.block_len, h.pay_bytes * 8ull + 1);
+            if (bl > HUF_MAX_BLOCK_LEN) m.status = HUFE_ARGUMENT;                /* beyond kernel limits */
             else {
-                /* A block cannot hold more symbols than its payload has bits: a larger block_len (a
-                 * damaged header) is decoded as far as the input goes and then fails like the
-                 * reference's reader does at the end of its input (decoder.c:53-56). */
-                const uint64_t pay_bits = (o1 - o0 - HUF_HEADER_FIXED - 2ull * (uint64_t)tl) * 8ull;
-                if (bl > pay_bits) bl = pay_bits + 1;
-                if (bl > HUF_MAX_BLOCK_LEN) m.status = HUFE_ARGUMENT;            /* beyond kernel limits */
-                else {
-                    m.block_len = bl;
-                    m.tree_len = tl;
-                    if (tl == 5) m.leaf = (int16_t)single_leaf_symbol(stream + o0 + HUF_HEADER_FIXED);
-                }
+                m.block_len = bl;
+                m.tree_len = (int16_t)h.tree_len;
+                if (h.tree_len == 5) m.leaf = (int16_t)single_leaf_symbol(h.tree);
             }
         }
         dmeta[b] = m;
@@ -104,16 +119,7 @@ __global__ __launch_bounds__(SCAN_GROUP) void decode_prepare_kernel(const uint8_
     }
     __syncthreads();
     if (m.status != HUFE_OK) atomicMin(&s_bad, (unsigned long long)b);
-    uint64_t total;
-    const uint64_t ex = block_excl_scan<SCAN_GROUP, uint64_t>(m.block_len, s_part, total);
-    if (b < nblocks) lens.local[b] = ex;
-    __syncthreads();
-    if (threadIdx.x >= 64) return;
-    if (threadIdx.x == 0) {
-        handover_store(lens.gsum + blockIdx.x, total);
-        handover_store(lens.gmin + blockIdx.x, s_bad);
-    }
-    two_level_finish(lens, gridDim.x);
+    scan_group_publish<SCAN_GROUP>(lens, b, nblocks, m.block_len, s_part, &s_bad);
 }
 
 /* ======================================================================================

@@ -5,16 +5,16 @@
    Positions are the layout's, as in gather.hpp: block b holds [b B, b B + min(B, raw_size - b B)).
 
      find_sub_kernel     workgroup = one (block, chunk of 65 536 symbols), decode_sub_kernel's geometry with eight waves;
-                         a wave takes the chunk's tiles wave, wave + 8, ...  The header is parsed and checked as
-                         gather_serve_kernel does it, the tables come from dsub_fast_tables (the claimed code lengths
-                         checked against the stream's tree), and EVERY tile of EVERY chunk is decoded with the checks of
-                         decode_sub.hpp: (a) the block's first tile starts at payload bit 0, (b) every group takes
+                         a wave takes the chunk's tiles wave, wave + 8, ...  The header is parsed and its length must
+                         be the layout's, the tables come from dsub_fast_tables (the claimed code lengths checked
+                         against the stream's tree), and EVERY tile of EVERY chunk is the item of sub_tile.hpp, with
+                         its checks: (a) the block's first tile starts at payload bit 0, (b) every group takes
                          exactly the bits it is said to have and no walk leaves tree or payload, (c) a tile ends where
                          the next tile of the block is said to start (the last: inside the payload).  The whole block
                          is walked, so the induction of decode_sub.hpp closes and the caller vouches for nothing: a
                          block is served exactly or its status says that it is not.
                          A lane's 32 decoded bytes lie in the wave's 2 KiB of LDS (dsub_tile_slow, the step-by-step
-                         route of range_tiles.hpp: codes of any length, groups of any size) and are tested against the
+                         route of sub_tile.hpp: codes of any length, groups of any size) and are tested against the
                          set - eight words in LDS - there; what leaves the workgroup is ONE 32-bit match mask per
                          group (a bitmap row per block: block starts need not be 32-aligned raw positions) and the
                          tile's match count.  A block of one byte value has no sub-index rows: its payload bits are
@@ -34,24 +34,18 @@
 #include <stdint.h>
 
 #include "../hufgpu_common.h"
-#include "decode_sub.hpp"
 #include "offsets.hpp"
+#include "sub_tile.hpp"
 
 namespace hufgpu {
 
-#define FIND_THREADS 512                    /* as drange_tiles_kernel: decode_sub.hpp's step-by-step functions are instantiated for 512 threads already,
+#define FIND_THREADS 512                    /* as RTILE_THREADS (range_tiles.hpp): decode_sub.hpp's step-by-step functions are instantiated for 512 threads already,
                                                and decode_sub_kernel<256>'s code does not depend on what is called from here */
 #define FIND_WAVES (FIND_THREADS / 64)
 #define FIND_EMIT_THREADS 256
 
 struct FindArgs {
-    const uint8_t *stream;
-    uint64_t stream_len;
-    const uint64_t *offsets;                /* the block index */
-    uint64_t nblocks;
-    HufSubIndex sub;
-    uint64_t raw_size, bsize;               /* the layout (bsize: never 0) */
-    int max_tree;
+    SubStream s;
     uint32_t cpb;                           /* chunks a block */
     uint32_t set[8];                        /* bit v: byte value v is looked for */
     uint32_t *bitmap;                       /* [nblocks][wpb] match masks, one word a group */
@@ -68,12 +62,7 @@ struct FindArgs {
 
 __device__ __forceinline__ uint64_t find_block_len(const FindArgs &a, uint64_t b)
 {
-    return dmin<uint64_t>(a.bsize, a.raw_size - b * a.bsize);
-}
-
-__device__ __forceinline__ uint64_t find_rank(const FindArgs &a, uint64_t tile)
-{
-    return a.scan.gprefix[tile / SCAN_GROUP] + a.scan.local[tile];
+    return dmin<uint64_t>(a.s.bsize, a.s.raw_size - b * a.s.bsize);
 }
 
 /* grid nblocks * cpb */
@@ -92,30 +81,19 @@ __global__ __launch_bounds__(FIND_THREADS) void find_sub_kernel(FindArgs a)
     const uint64_t sym1 = dmin<uint64_t>(blen, sym0 + DSUB_CHUNK_SYMS);
     if (threadIdx.x < 8) s_set[threadIdx.x] = a.set[threadIdx.x];
     __syncthreads();
-    /* ---- the header, as gather_serve_kernel reads it - and its length must be the layout's ---- */
-    const uint64_t o0 = a.offsets[b], o1 = dmin<uint64_t>(a.offsets[b + 1], a.stream_len);
-    uint64_t bl = 0;
-    int16_t tl16 = 0;
-    bool parsed = o0 <= o1 && o1 - o0 >= HUF_HEADER_FIXED;
-    if (parsed) {
-        load_header10(a.stream, a.stream_len, o0, bl, tl16);
-        parsed = tl16 >= 0 && (int)tl16 <= a.max_tree && o1 - o0 >= HUF_HEADER_FIXED + 2ull * (uint64_t)tl16 && bl == blen;
-    }
-    if (!parsed) {
+    /* ---- the header - and its length must be the layout's ---- */
+    BlockHeader h;
+    if (parse_block_header(a.s.stream, a.s.stream_len, a.s.offsets[b], a.s.offsets[b + 1], a.s.max_tree, h) != HUFE_OK || h.block_len != blen) {
         if (threadIdx.x == 0) atomicMax(&a.errs[b], (int32_t)HUFE_RW);
         return;
     }
-    const int tl = (int)tl16;
-    const uint8_t *tree = a.stream + o0 + HUF_HEADER_FIXED;
-    const uint8_t *pay = tree + 2 * tl;
-    const uint64_t pay_bytes = o1 - (o0 + HUF_HEADER_FIXED + 2ull * (uint64_t)tl);
-    const uint64_t pay_bits = pay_bytes * 8ull;
+    const SubBlockView v = sub_block_view(h, a.s.sub, b);
     uint32_t *row = a.bitmap + b * a.wpb;
     uint32_t *trow = a.tcnt + b * a.tpb;
-    const int leaf = tl == 5 ? single_leaf_symbol(tree) : -1;
+    const int leaf = h.tree_len == 5 ? single_leaf_symbol(h.tree) : -1;
     if (leaf >= 0) {
         /* ---- one byte value: every symbol is a 0 bit (decode.hpp); the chunk's bits are seen to be 0 ---- */
-        if (blen > pay_bits) {
+        if (blen > v.pay_bits) {
             if (threadIdx.x == 0) atomicMax(&a.errs[b], (int32_t)HUFE_RW);
             return;
         }
@@ -123,9 +101,9 @@ __global__ __launch_bounds__(FIND_THREADS) void find_sub_kernel(FindArgs a)
         bool set = false;
         for (uint64_t g = (sym0 >> 5) + threadIdx.x; 32ull * g < sym1; g += FIND_THREADS) {
             const uint32_t nsym = (uint32_t)dmin<uint64_t>(DSUB_SPL, blen - 32ull * g);
-            uint32_t v = load_be32(pay, 4ull * g, pay_bytes);
-            if (nsym < 32u) v &= 0xffffffffu << (32u - nsym);
-            set |= v != 0u;
+            uint32_t x = load_be32(v.pay, 4ull * g, v.pay_bytes);
+            if (nsym < 32u) x &= 0xffffffffu << (32u - nsym);
+            set |= x != 0u;
             row[g] = match ? (nsym < 32u ? (1u << nsym) - 1u : 0xffffffffu) : 0u;
         }
         for (uint64_t t = sym0 / HUF_SUB_TILE + threadIdx.x; t * HUF_SUB_TILE < sym1; t += FIND_THREADS)
@@ -134,39 +112,18 @@ __global__ __launch_bounds__(FIND_THREADS) void find_sub_kernel(FindArgs a)
         return;
     }
     /* ---- the block's tables ---- */
-    const DsubTreeWords tw = dsub_tree_request<FIND_THREADS>(tree, tl, a.sub.lens + b * HUF_NSYM);
-    if (!dsub_fast_tables<FIND_THREADS>(sh, tl, tw)) {              /* (workgroup-uniform) */
+    const DsubTreeWords tw = dsub_tree_request<FIND_THREADS>(h.tree, h.tree_len, a.s.sub.lens + b * HUF_NSYM);
+    if (!dsub_fast_tables<FIND_THREADS>(sh, h.tree_len, tw)) {      /* (workgroup-uniform) */
         if (threadIdx.x == 0) atomicMax(&a.errs[b], (int32_t)HUFE_RW);
         return;
     }
     uint32_t *tile_words = s_tile[wave];
     uint32_t *top = DsubLds<FIND_THREADS>::slice(sh, (int)wave) + (SH::SLICE_WORDS - 1u);
-    const uint64_t ntiles = (blen + HUF_SUB_TILE - 1) / HUF_SUB_TILE, ngrp = (blen + DSUB_SPL - 1) / DSUB_SPL;
-    const uint64_t *told = a.sub.tile_bits + b * a.sub.tpb;
-    const uint16_t *grp = a.sub.group_bits + b * a.sub.gpb;
     bool good = true;
-    /* ---- the chunk's tiles, one wave each: drange_tiles_kernel's item, every one of them ---- */
+    /* ---- the chunk's tiles, one wave each, every one of them ---- */
     for (uint64_t t = sym0 / HUF_SUB_TILE + wave; t * HUF_SUB_TILE < sym1; t += FIND_WAVES) {
-        const uint64_t g = t * 64u + lane;
-        uint32_t gb = 0, nsym = 0;
-        if (g < ngrp) {
-            gb = grp[g];
-            nsym = (uint32_t)dmin<uint64_t>(DSUB_SPL, blen - g * DSUB_SPL);
-        }
-        const uint64_t tfirst = uni64(told[t]);
-        const uint64_t tnext = uni64(told[t + 1 < ntiles ? t + 1 : t]);
-        const bool wild = __ballot(gb > (uint32_t)DSUB_MAX_GROUP_BITS) != 0ull;
-        gb = dmin<uint32_t>(gb, DSUB_MAX_GROUP_BITS);
-        const uint32_t incl = wave_incl_scan_u32(gb);
-        const uint64_t sum = wave_lane_u32(incl, 63);
-        bool fine = !wild && tfirst <= pay_bits && sum <= pay_bits - tfirst && (t != 0 || tfirst == 0);    /* (a), inside the payload */
-        if (fine && t + 1 < ntiles && tfirst + sum != tnext) fine = false;                                 /* (c) */
-        if (fine) {
-            const bool ok = dsub_tile_slow<FIND_THREADS>(sh, top, pay, pay_bytes, tfirst, incl - gb, incl, nsym, true,
-                                                         reinterpret_cast<uint8_t *>(tile_words) + DSUB_SPL * lane);    /* (b) */
-            fine = __ballot(!ok) == 0ull;
-        }
-        if (!fine) {
+        uint32_t nsym;
+        if (!sub_tile_checked<FIND_THREADS>(sh, top, v, t, reinterpret_cast<uint8_t *>(tile_words), nsym)) {
             good = false;
             continue;
         }
@@ -179,12 +136,12 @@ __global__ __launch_bounds__(FIND_THREADS) void find_sub_kernel(FindArgs a)
         for (int j = 0; j < 8; j++) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const uint32_t v = (w[j] >> (8 * i)) & 0xffu;
-                m |= ((s_set[v >> 5] >> (v & 31u)) & 1u) << (4 * j + i);
+                const uint32_t x = (w[j] >> (8 * i)) & 0xffu;
+                m |= ((s_set[x >> 5] >> (x & 31u)) & 1u) << (4 * j + i);
             }
         }
         m = nsym == 0u ? 0u : (nsym < 32u ? m & ((1u << nsym) - 1u) : m);        /* (bytes behind a short group are stale) */
-        if (g < ngrp) row[g] = m;
+        if (nsym != 0u) row[t * 64u + lane] = m;
         const uint32_t cnt = wave_lane_u32(wave_incl_scan_u32((uint32_t)__popc(m)), 63);
         if (lane == 0) trow[t] = cnt;
     }
@@ -203,13 +160,7 @@ __global__ __launch_bounds__(SCAN_GROUP) void find_scan_kernel(FindArgs a)
         if (served && t * HUF_SUB_TILE < find_block_len(a, b)) c = a.tcnt[i];
         if (!served && t == 0) atomicAdd((unsigned long long *)&a.totals[2], 1ull);
     }
-    uint64_t total;
-    const uint64_t ex = block_excl_scan<SCAN_GROUP, uint64_t>(c, s_part, total);
-    if (i < a.ntiles) a.scan.local[i] = ex;
-    __syncthreads();
-    if (threadIdx.x >= 64) return;
-    if (threadIdx.x == 0) handover_store(a.scan.gsum + blockIdx.x, total);
-    two_level_finish(a.scan, gridDim.x);
+    scan_group_publish<SCAN_GROUP>(a.scan, i, a.ntiles, c, s_part);
 }
 
 /* one thread per block */
@@ -217,9 +168,9 @@ __global__ __launch_bounds__(256) void find_finish_kernel(FindArgs a)
 {
     const uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (b == 0) a.totals[1] = dmin<uint64_t>(a.totals[0], a.pos_cap);
-    if (b >= a.nblocks || !a.block_counts) return;
-    const uint64_t end = b + 1 < a.nblocks ? find_rank(a, (b + 1) * a.tpb) : a.totals[0];
-    a.block_counts[b] = end - find_rank(a, b * a.tpb);
+    if (b >= a.s.nblocks || !a.block_counts) return;
+    const uint64_t end = b + 1 < a.s.nblocks ? two_level_prefix(a.scan, (b + 1) * a.tpb) : a.totals[0];
+    a.block_counts[b] = end - two_level_prefix(a.scan, b * a.tpb);
 }
 
 /* a wave = one tile */
@@ -231,12 +182,12 @@ __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_emit_kernel(FindArgs a
     const uint64_t b = i / a.tpb, t = i % a.tpb;
     const uint64_t blen = find_block_len(a, b);
     if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK) return;
-    const uint64_t rank0 = find_rank(a, i);
+    const uint64_t rank0 = two_level_prefix(a.scan, i);
     if (rank0 >= a.pos_cap) return;
     const uint64_t g = t * 64u + lane;
     uint32_t m = g * DSUB_SPL < blen ? a.bitmap[b * a.wpb + g] : 0u;
     uint64_t r = rank0 + (wave_incl_scan_u32((uint32_t)__popc(m)) - (uint32_t)__popc(m));
-    const uint64_t base = b * a.bsize + g * DSUB_SPL;
+    const uint64_t base = b * a.s.bsize + g * DSUB_SPL;
     while (m != 0u && r < a.pos_cap) {
         a.pos[r++] = base + (uint32_t)__builtin_ctz(m);
         m &= m - 1u;

@@ -14,9 +14,9 @@
      gather_serve_kernel  workgroups of eight waves walk the list.  A block's header is parsed and checked and its tables
                           are built ONCE (dsub_fast_tables: the claimed code lengths checked against the stream's tree)
                           however many records fall into it; the waves then take the block's (part, tile) items, one wave
-                          an item - an item of drange_tiles_kernel (range_tiles.hpp), with the same checks.  A block of
-                          one byte value has no sub-index rows: its parts are fills, once the header and the parts' own
-                          payload bits (all zero) have been looked at.
+                          an item - the item of sub_tile.hpp, with its checks.  A block of one byte value has no
+                          sub-index rows: its parts are fills, once the header and the parts' own payload bits (all
+                          zero) have been looked at.
 
    A block with many items (blocksize = 0: one block holds every record) is the work of `shares` workgroups, each
    with the block's tables of its own: unit u of the walk is share u % shares of touched block u / shares.  The grid is
@@ -30,13 +30,12 @@
 #include <stdint.h>
 
 #include "../hufgpu_common.h"
-#include "decode_sub.hpp"
 #include "offsets.hpp"
-#include "range_tiles.hpp"
+#include "sub_tile.hpp"
 
 namespace hufgpu {
 
-#define GATHER_THREADS 512                  /* as drange_tiles_kernel: decode_sub.hpp's step-by-step functions are instantiated for 512 threads already */
+#define GATHER_THREADS 512                  /* as RTILE_THREADS (range_tiles.hpp): decode_sub.hpp's step-by-step functions are instantiated for 512 threads already */
 #define GATHER_WAVES (GATHER_THREADS / 64)
 
 /* a record's bytes inside one block */
@@ -49,13 +48,7 @@ struct __attribute__((aligned(16))) GatherPart {
 };
 
 struct GatherArgs {
-    const uint8_t *stream;
-    uint64_t stream_len;
-    const uint64_t *offsets;                /* the block index */
-    uint64_t nblocks;
-    HufSubIndex sub;
-    uint64_t raw_size, bsize;               /* the layout (bsize: never 0) */
-    int max_tree;
+    SubStream s;
     uint32_t max_len;
     uint64_t nrecords;
     const uint64_t *pos;
@@ -79,13 +72,8 @@ __device__ __forceinline__ bool gather_record(const GatherArgs &a, uint64_t i, u
     pos = a.pos[i];
     const uint32_t len = a.len ? a.len[i] : a.max_len;
     too_long = len > a.max_len;
-    n = (too_long || pos >= a.raw_size) ? 0u : (uint32_t)dmin<uint64_t>(len, a.raw_size - pos);
+    n = (too_long || pos >= a.s.raw_size) ? 0u : (uint32_t)dmin<uint64_t>(len, a.s.raw_size - pos);
     return n != 0u;
-}
-
-__device__ __forceinline__ uint64_t gather_prefix(const GatherArgs &a, uint64_t b)
-{
-    return a.scan.gprefix[b / SCAN_GROUP] + a.scan.local[b];
 }
 
 __global__ __launch_bounds__(256) void gather_mark_kernel(GatherArgs a)
@@ -99,7 +87,7 @@ __global__ __launch_bounds__(256) void gather_mark_kernel(GatherArgs a)
     a.errs[i] = too_long ? HUFE_ARGUMENT : HUFE_OK;
     if (a.raw_lens) a.raw_lens[i] = n;
     if (!any) return;
-    const uint64_t fb = pos / a.bsize, lb = (pos + n - 1) / a.bsize;
+    const uint64_t fb = pos / a.s.bsize, lb = (pos + n - 1) / a.s.bsize;
     for (uint64_t b = fb; b <= lb; b++) atomicAdd(&a.cnt[b], 1u);
 }
 
@@ -108,37 +96,31 @@ __global__ __launch_bounds__(SCAN_GROUP) void gather_scan_kernel(GatherArgs a)
 {
     __shared__ uint64_t s_part[SCAN_GROUP / 64];
     const uint64_t b = (uint64_t)blockIdx.x * SCAN_GROUP + threadIdx.x;
-    const uint64_t c = b < a.nblocks ? a.cnt[b] : 0u;
-    uint64_t total;
-    const uint64_t ex = block_excl_scan<SCAN_GROUP, uint64_t>(c + ((uint64_t)(c != 0) << 32), s_part, total);
-    if (b < a.nblocks) a.scan.local[b] = ex;
-    __syncthreads();
-    if (threadIdx.x >= 64) return;
-    if (threadIdx.x == 0) handover_store(a.scan.gsum + blockIdx.x, total);
-    two_level_finish(a.scan, gridDim.x);
+    const uint64_t c = b < a.s.nblocks ? a.cnt[b] : 0u;
+    scan_group_publish<SCAN_GROUP>(a.scan, b, a.s.nblocks, c + ((uint64_t)(c != 0) << 32), s_part);
 }
 
 /* one thread per block and per record */
 __global__ __launch_bounds__(256) void gather_place_kernel(GatherArgs a)
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < a.nblocks && a.cnt[i] != 0u) a.list[gather_prefix(a, i) >> 32] = (uint32_t)i;
+    if (i < a.s.nblocks && a.cnt[i] != 0u) a.list[two_level_prefix(a.scan, i) >> 32] = (uint32_t)i;
     if (i >= a.nrecords) return;
     uint64_t pos;
     uint32_t n;
     bool too_long;
     if (!gather_record(a, i, pos, n, too_long)) return;
-    const uint64_t fb = pos / a.bsize, lb = (pos + n - 1) / a.bsize;
+    const uint64_t fb = pos / a.s.bsize, lb = (pos + n - 1) / a.s.bsize;
     for (uint64_t b = fb; b <= lb; b++) {
-        const uint64_t p0 = b * a.bsize;
-        const uint64_t s = dmax<uint64_t>(pos, p0), e = dmin<uint64_t>(pos + n, p0 + a.bsize);
+        const uint64_t p0 = b * a.s.bsize;
+        const uint64_t s = dmax<uint64_t>(pos, p0), e = dmin<uint64_t>(pos + n, p0 + a.s.bsize);
         GatherPart p;
         p.start = s;
         p.dst = i * a.stride + (s - pos);
         p.n = (uint32_t)(e - s);
         p.rec = (uint32_t)i;
         p.pad_ = 0;
-        a.parts[(uint32_t)gather_prefix(a, b) + atomicAdd(&a.cur[b], 1u)] = p;   /* (the order inside a segment is free) */
+        a.parts[(uint32_t)two_level_prefix(a.scan, b) + atomicAdd(&a.cur[b], 1u)] = p;   /* (the order inside a segment is free) */
     }
 }
 
@@ -178,33 +160,22 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_serve_kernel(GatherArgs
         __syncthreads();                                            /* the waves are through with the tables of the unit before */
         const uint32_t share = (uint32_t)(u % a.shares);
         const uint64_t b = a.list[u / a.shares];
-        const uint32_t count = a.cnt[b], seg = (uint32_t)gather_prefix(a, b);
+        const uint32_t count = a.cnt[b], seg = (uint32_t)two_level_prefix(a.scan, b);
         const uint64_t nids = (uint64_t)count * a.tmax;             /* item id = part * tmax + the tile's number inside the part */
         const uint64_t id0 = (uint64_t)share * GATHER_WAVES, idstep = (uint64_t)a.shares * GATHER_WAVES;
         if (id0 >= nids) continue;
         /* ---- the header, as decode_prepare_kernel reads it - and its length must be the layout's ---- */
-        const uint64_t p0 = b * a.bsize, blen = dmin<uint64_t>(a.bsize, a.raw_size - p0);
-        const uint64_t o0 = a.offsets[b], o1 = dmin<uint64_t>(a.offsets[b + 1], a.stream_len);
-        uint64_t bl = 0;
-        int16_t tl16 = 0;
-        bool parsed = o0 <= o1 && o1 - o0 >= HUF_HEADER_FIXED;
-        if (parsed) {
-            load_header10(a.stream, a.stream_len, o0, bl, tl16);
-            parsed = tl16 >= 0 && (int)tl16 <= a.max_tree && o1 - o0 >= HUF_HEADER_FIXED + 2ull * (uint64_t)tl16 && bl == blen;
-        }
-        if (!parsed) {
+        const uint64_t p0 = b * a.s.bsize, blen = dmin<uint64_t>(a.s.bsize, a.s.raw_size - p0);
+        BlockHeader h;
+        if (parse_block_header(a.s.stream, a.s.stream_len, a.s.offsets[b], a.s.offsets[b + 1], a.s.max_tree, h) != HUFE_OK || h.block_len != blen) {
             gather_fail_block(a, seg, count, share);
             continue;
         }
-        const int tl = (int)tl16;
-        const uint8_t *tree = a.stream + o0 + HUF_HEADER_FIXED;
-        const uint8_t *pay = tree + 2 * tl;
-        const uint64_t pay_bytes = o1 - (o0 + HUF_HEADER_FIXED + 2ull * (uint64_t)tl);
-        const uint64_t pay_bits = pay_bytes * 8ull;
-        const int leaf = tl == 5 ? single_leaf_symbol(tree) : -1;
+        const SubBlockView v = sub_block_view(h, a.s.sub, b);
+        const int leaf = h.tree_len == 5 ? single_leaf_symbol(h.tree) : -1;
         if (leaf >= 0) {
             /* ---- one byte value: every symbol is a 0 bit (decode.hpp), a part is a fill once its own bits are seen to be 0 ---- */
-            if (blen > pay_bits) {
+            if (blen > v.pay_bits) {
                 gather_fail_block(a, seg, count, share);
                 continue;
             }
@@ -214,10 +185,10 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_serve_kernel(GatherArgs
                 const uint64_t w0 = c0 >> 5, w1 = (c1 - 1) >> 5;
                 bool set = false;
                 for (uint64_t w = w0 + lane; w <= w1; w += 64u) {
-                    uint32_t v = load_be32(pay, 4ull * w, pay_bytes);
-                    if (w == w0) v &= 0xffffffffu >> (uint32_t)(c0 & 31u);
-                    if (w == w1) v &= 0xffffffffu << (31u - (uint32_t)((c1 - 1) & 31u));
-                    set |= v != 0u;
+                    uint32_t x = load_be32(v.pay, 4ull * w, v.pay_bytes);
+                    if (w == w0) x &= 0xffffffffu >> (uint32_t)(c0 & 31u);
+                    if (w == w1) x &= 0xffffffffu << (31u - (uint32_t)((c1 - 1) & 31u));
+                    set |= x != 0u;
                 }
                 if (__ballot(set) != 0ull) {
                     if (lane == 0) atomicMax(&a.errs[part.rec], (int32_t)HUFE_RW);
@@ -228,40 +199,19 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_serve_kernel(GatherArgs
             continue;
         }
         /* ---- the block's tables, once ---- */
-        const DsubTreeWords tw = dsub_tree_request<GATHER_THREADS>(tree, tl, a.sub.lens + b * HUF_NSYM);
-        if (!dsub_fast_tables<GATHER_THREADS>(sh, tl, tw)) {        /* (workgroup-uniform) */
+        const DsubTreeWords tw = dsub_tree_request<GATHER_THREADS>(h.tree, h.tree_len, a.s.sub.lens + b * HUF_NSYM);
+        if (!dsub_fast_tables<GATHER_THREADS>(sh, h.tree_len, tw)) {  /* (workgroup-uniform) */
             gather_fail_block(a, seg, count, share);
             continue;
         }
-        const uint64_t ntiles = (blen + HUF_SUB_TILE - 1) / HUF_SUB_TILE, ngrp = (blen + DSUB_SPL - 1) / DSUB_SPL;
-        const uint64_t *told = a.sub.tile_bits + b * a.sub.tpb;
-        const uint16_t *grp = a.sub.group_bits + b * a.sub.gpb;
-        /* ---- the items, one wave each: drange_tiles_kernel's item ---- */
+        /* ---- the items, one wave each ---- */
         for (uint64_t id = id0 + wave; id < nids; id += idstep) {
             const GatherPart part = a.parts[seg + id / a.tmax];
             const uint64_t c0 = part.start - p0, c1 = c0 + part.n;
             const uint64_t t = c0 / HUF_SUB_TILE + id % a.tmax;
             if (t > (c1 - 1) / HUF_SUB_TILE) continue;
-            const uint64_t g = t * 64u + lane;
-            uint32_t gb = 0, nsym = 0;
-            if (g < ngrp) {
-                gb = grp[g];
-                nsym = (uint32_t)dmin<uint64_t>(DSUB_SPL, blen - g * DSUB_SPL);
-            }
-            const uint64_t tfirst = uni64(told[t]);
-            const uint64_t tnext = uni64(told[t + 1 < ntiles ? t + 1 : t]);
-            const bool wild = __ballot(gb > (uint32_t)DSUB_MAX_GROUP_BITS) != 0ull;
-            gb = dmin<uint32_t>(gb, DSUB_MAX_GROUP_BITS);
-            const uint32_t incl = wave_incl_scan_u32(gb);
-            const uint64_t sum = wave_lane_u32(incl, 63);
-            bool fine = !wild && tfirst <= pay_bits && sum <= pay_bits - tfirst && (t != 0 || tfirst == 0);
-            if (fine && t + 1 < ntiles && tfirst + sum != tnext) fine = false;
-            if (fine) {
-                const bool ok = dsub_tile_slow<GATHER_THREADS>(sh, top, pay, pay_bytes, tfirst, incl - gb, incl, nsym, true,
-                                                               reinterpret_cast<uint8_t *>(tile_words) + DSUB_SPL * lane);
-                fine = __ballot(!ok) == 0ull;
-            }
-            if (!fine) {
+            uint32_t nsym;
+            if (!sub_tile_checked<GATHER_THREADS>(sh, top, v, t, reinterpret_cast<uint8_t *>(tile_words), nsym)) {
                 if (lane == 0) atomicMax(&a.errs[part.rec], (int32_t)HUFE_RW);
                 continue;
             }

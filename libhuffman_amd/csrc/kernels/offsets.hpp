@@ -188,6 +188,32 @@ __device__ __forceinline__ void two_level_finish(const TwoLevel &t, uint64_t ngr
     }
 }
 
+/* What a consumer adds up: the sum of the values in front of element i. */
+__device__ __forceinline__ uint64_t two_level_prefix(const TwoLevel &t, uint64_t i)
+{
+    return t.gprefix[i / SCAN_GROUP] + t.local[i];
+}
+
+/* The tail of a kernel whose workgroup IS one group (THREADS == SCAN_GROUP, thread = element i of n, all threads call):
+ * the value's exclusive sum inside the group to local[i], the group's total - and *low, the group's minimum in LDS,
+ * written before the scan's barriers, for a scan with gmin - handed over, and the ticket. */
+template <int THREADS>
+__device__ __forceinline__ void scan_group_publish(const TwoLevel &t, uint64_t i, uint64_t n, uint64_t value, uint64_t *s_part,
+                                                   const unsigned long long *low = nullptr)
+{
+    static_assert(THREADS == SCAN_GROUP, "a workgroup is one group");
+    uint64_t total;
+    const uint64_t ex = block_excl_scan<THREADS, uint64_t>(value, s_part, total);
+    if (i < n) t.local[i] = ex;
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    if (threadIdx.x == 0) {
+        handover_store(t.gsum + blockIdx.x, total);
+        if (low) handover_store(t.gmin + blockIdx.x, *low);
+    }
+    two_level_finish(t, gridDim.x);
+}
+
 /* Called by ONE full wavefront with the value of its block. */
 __device__ __forceinline__ void two_level_arrive(const TwoLevel &t, uint64_t b, uint64_t nblocks, uint64_t value)
 {

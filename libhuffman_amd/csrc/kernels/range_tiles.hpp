@@ -15,20 +15,11 @@
    thousands of tiles inside one giant block is the work of all y workgroups, a workgroup without an item leaves before
    the table build.  Two ranges in one block build the block's tables once each.
 
-   An item, as decode_sub_kernel takes a tile: lane l has group 64 t + l, its first bit is tile_bits[t] + the wave's
-   exclusive scan of group_bits.  Checked per item:
-     - tile_bits[t] lies inside the payload (and is 0 for the block's first tile), no group claims more than 32 codes
-       of the longest length can have;
-     - tile_bits[t] + the SUM of the tile's group_bits is the next tile's recorded start (the block's last tile: inside
-       the payload) - summed, not decoded;
-     - (b) of decode_sub.hpp for EVERY group of the tile, also those outside the range: a lane's codewords take exactly
-       the bits its group is said to have, no walk leaves the tree or the payload.  (The lanes of a wave run in
-       lockstep: the groups outside the range cost LDS look-ups but no time, and with them damage anywhere in a touched
-       tile is seen, not only in the groups that are delivered.)
-   What cannot be checked is that tile_bits[t] is where the in-order decoder arrives: that is the caller's word (the
-   flag).  All groups go through decode_sub.hpp's step-by-step path (dsub_tile_slow: staged word by word, codes of any
-   length, groups of any size) - there is no separate route for unusual groups, and none of them fails over for being
-   unusual.
+   An item is the item of sub_tile.hpp (sub_tile_checked), with its checks - for EVERY group of the tile, also those
+   outside the range: the lanes of a wave run in lockstep, so the groups outside the range cost LDS look-ups but no time,
+   and with them damage anywhere in a touched tile is seen, not only in the groups that are delivered.  What cannot be
+   checked is that tile_bits[t] is where the in-order decoder arrives: that is the caller's word (the flag).  No group
+   fails over for being unusual.
 
    Any failure puts the block on the call's fail count, once (a bit in the block's pair word says it is listed); the host
    then serves the whole call again by the staged route.  The decoded tile lies in the wave's 2 KiB of LDS; the part
@@ -39,8 +30,8 @@
 #include <stdint.h>
 
 #include "../hufgpu_common.h"
-#include "decode_sub.hpp"
 #include "ranges.hpp"
+#include "sub_tile.hpp"
 
 namespace hufgpu {
 
@@ -50,50 +41,13 @@ namespace hufgpu {
 #define RTILE_WAVES (RTILE_THREADS / 64)
 #define RTILE_FAILED (1ull << 63)           /* in DecRangeArgs::tpairs[b]: the block is on the fail count */
 
-struct RangeTileArgs {
-    const uint8_t *stream;
-    uint64_t stream_len;
-    const uint64_t *offsets;                /* the block index */
-    HufSubIndex sub;
-};
-
 __device__ __forceinline__ void rtile_fail(const DecRangeArgs &a, uint64_t b)
 {
     if ((atomicOr(&a.tpairs[b], RTILE_FAILED) & RTILE_FAILED) == 0ull) atomicAdd(&a.counters[6], 1ull);
 }
 
-/* bytes [s0, s0 + n) of the wave's decoded tile (LDS, `words` 16-byte aligned, readable 8 words past the tile) to dst,
- * which has any alignment: 16-byte stores are aligned on the global side, their four words come from five aligned LDS
- * words shifted into place */
-__device__ __forceinline__ void rtile_store(uint8_t *__restrict__ dst, const uint32_t *words, uint32_t s0, uint32_t n)
-{
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    const uint32_t lane = (uint32_t)lane_id();
-    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(words);
-    const uint32_t head = dmin<uint32_t>(n, (16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u);
-    const uint32_t chunks = (n - head) >> 4, tail = (n - head) & 15u;
-    if (lane < head) dst[lane] = bytes[s0 + lane];
-    if (lane < tail) dst[head + 16u * chunks + lane] = bytes[s0 + head + 16u * chunks + lane];
-    v4u *d = reinterpret_cast<v4u *>(dst + head);
-    for (uint32_t c = lane; c < chunks; c += 64u) {
-        const uint32_t off = s0 + head + 16u * c;
-        const uint32_t *w = words + (off >> 2);
-        const uint32_t sh = 8u * (off & 3u);
-        uint32_t x[5];
-#pragma unroll
-        for (int k = 0; k < 5; k++) x[k] = w[k];
-        v4u v;
-        /* (v_alignbit_b32 shifts by the amount's low five bits: 0 leaves x[k]) */
-        v.x = __builtin_amdgcn_alignbit(x[1], x[0], sh);
-        v.y = __builtin_amdgcn_alignbit(x[2], x[1], sh);
-        v.z = __builtin_amdgcn_alignbit(x[3], x[2], sh);
-        v.w = __builtin_amdgcn_alignbit(x[4], x[3], sh);
-        d[c] = v;
-    }
-}
-
 /* grid (nranges, y) */
-__global__ __launch_bounds__(RTILE_THREADS) void drange_tiles_kernel(DecRangeArgs a, RangeTileArgs ta)
+__global__ __launch_bounds__(RTILE_THREADS) void drange_tiles_kernel(DecRangeArgs a, SubStream ta)
 {
     typedef DsubShared<RTILE_THREADS> SH;
     __shared__ SH sh;
@@ -116,40 +70,20 @@ __global__ __launch_bounds__(RTILE_THREADS) void drange_tiles_kernel(DecRangeArg
         if ((uint64_t)blockIdx.y * RTILE_WAVES >= nitems) continue;
         const HufDecodeMeta m = a.dmeta[b];
         const uint64_t o0 = ta.offsets[b], o1 = dmin<uint64_t>(ta.offsets[b + 1], ta.stream_len);
-        const uint64_t pay_bytes = o1 - (o0 + HUF_HEADER_FIXED + 2ull * (uint64_t)m.tree_len);      /* (the header parsed: it fits) */
-        const uint64_t pay_bits = pay_bytes * 8ull;
         const uint8_t *tree = ta.stream + o0 + HUF_HEADER_FIXED;
         const uint8_t *pay = tree + 2 * (int)m.tree_len;
+        const BlockHeader h = {blen, m.tree_len, tree, pay, o1 - (o0 + HUF_HEADER_FIXED + 2ull * (uint64_t)m.tree_len)};    /* (the header parsed: it fits) */
         __syncthreads();                                            /* the waves are through with the tables of the other edge */
         const DsubTreeWords tw = dsub_tree_request<RTILE_THREADS>(tree, m.tree_len, ta.sub.lens + b * HUF_NSYM);
         if (!dsub_fast_tables<RTILE_THREADS>(sh, m.tree_len, tw)) {  /* (workgroup-uniform) */
             if (threadIdx.x == 0) rtile_fail(a, b);
             continue;
         }
-        const uint64_t ntiles = (blen + HUF_SUB_TILE - 1) / HUF_SUB_TILE, ngrp = (blen + DSUB_SPL - 1) / DSUB_SPL;
-        const uint64_t *told = ta.sub.tile_bits + b * ta.sub.tpb;
-        const uint16_t *grp = ta.sub.group_bits + b * ta.sub.gpb;
+        const SubBlockView v = sub_block_view(h, ta.sub, b);
         for (uint64_t j = (uint64_t)blockIdx.y * RTILE_WAVES + wave; j < nitems; j += (uint64_t)gridDim.y * RTILE_WAVES) {
-            const uint64_t t = t0 + j, g = t * 64u + lane;
-            uint32_t gb = 0, nsym = 0;
-            if (g < ngrp) {
-                gb = grp[g];
-                nsym = (uint32_t)dmin<uint64_t>(DSUB_SPL, blen - g * DSUB_SPL);
-            }
-            const uint64_t tfirst = uni64(told[t]);
-            const uint64_t tnext = uni64(told[t + 1 < ntiles ? t + 1 : t]);
-            const bool wild = __ballot(gb > (uint32_t)DSUB_MAX_GROUP_BITS) != 0ull;
-            gb = dmin<uint32_t>(gb, DSUB_MAX_GROUP_BITS);
-            const uint32_t incl = wave_incl_scan_u32(gb);
-            const uint64_t sum = wave_lane_u32(incl, 63);
-            bool fine = !wild && tfirst <= pay_bits && sum <= pay_bits - tfirst && (t != 0 || tfirst == 0);
-            if (fine && t + 1 < ntiles && tfirst + sum != tnext) fine = false;
-            if (fine) {
-                const bool ok = dsub_tile_slow<RTILE_THREADS>(sh, top, pay, pay_bytes, tfirst, incl - gb, incl, nsym, true,
-                                                              reinterpret_cast<uint8_t *>(tile_words) + DSUB_SPL * lane);
-                fine = __ballot(!ok) == 0ull;
-            }
-            if (!fine) {
+            const uint64_t t = t0 + j;
+            uint32_t nsym;
+            if (!sub_tile_checked<RTILE_THREADS>(sh, top, v, t, reinterpret_cast<uint8_t *>(tile_words), nsym)) {
                 if (lane == 0) rtile_fail(a, b);
                 continue;
             }

@@ -75,15 +75,11 @@ __global__ __launch_bounds__(SB_THREADS) void sub_lens_kernel(SubBuildArgs a)
     const uint64_t lb = blockIdx.x, b = a.blk0 + lb;
     const uint64_t s0 = b * a.blocksize;
     const uint64_t len = dmin<uint64_t>(a.blocksize, a.n - s0);
-    const uint64_t o0 = a.offsets[b];
-    const uint64_t o1 = dmin<uint64_t>(a.offsets[b + 1], a.stream_len);
+    BlockHeader h;
     int tl = -1;
-    if (!(a.dec_status && a.dec_status[lb] != 0) && o0 <= o1 && o1 - o0 >= HUF_HEADER_FIXED && lb * a.blocksize + len <= a.raw_avail) {
-        uint64_t bl;
-        int16_t t16;
-        load_header10(a.stream, a.stream_len, o0, bl, t16);
-        if (t16 >= 0 && t16 <= a.max_tree && o1 - o0 >= HUF_HEADER_FIXED + 2ull * (uint64_t)t16 && bl == len) tl = t16;
-    }
+    if (!(a.dec_status && a.dec_status[lb] != 0) && lb * a.blocksize + len <= a.raw_avail &&
+        parse_block_header(a.stream, a.stream_len, a.offsets[b], a.offsets[b + 1], a.max_tree, h) == HUFE_OK && h.block_len == len)
+        tl = h.tree_len;
     tl = (int)uni32((uint32_t)tl);
     if (tl == 5) {                                                   /* one distinct byte: the encoder writes nothing */
         if (tid == 0) a.state[lb] = SB_SKIP;
@@ -92,7 +88,7 @@ __global__ __launch_bounds__(SB_THREADS) void sub_lens_kernel(SubBuildArgs a)
     bool bad = tl < 0;
     if (!bad) {
         typedef int16_t __attribute__((aligned(1))) unaligned_i16;
-        const unaligned_i16 *ent = reinterpret_cast<const unaligned_i16 *>(a.stream + o0 + HUF_HEADER_FIXED);
+        const unaligned_i16 *ent = reinterpret_cast<const unaligned_i16 *>(h.tree);
         int e[4];
         int x = 0;
 #pragma unroll
@@ -176,7 +172,7 @@ __global__ __launch_bounds__(SB_THREADS) void sub_lens_kernel(SubBuildArgs a)
             s_len[4 * tid] | (s_len[4 * tid + 1] << 8) | (s_len[4 * tid + 2] << 16) | (s_len[4 * tid + 3] << 24);
     if (tid == 0) {
         a.state[lb] = SB_BUILD;
-        a.pay_bytes[lb] = o1 - o0 - HUF_HEADER_FIXED - 2ull * (uint64_t)tl;
+        a.pay_bytes[lb] = h.pay_bytes;
     }
 }
 
