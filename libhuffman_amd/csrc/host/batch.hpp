@@ -51,16 +51,9 @@ static int batch_stage(hufgpu_ctx *c, uint64_t words, uint64_t **h)
     if (!c->bstage_ev) HIP_OK(c, hipEventCreateWithFlags(&c->bstage_ev, hipEventDisableTiming));
     if (c->bstage_pending) HIP_OK(c, hipEventSynchronize(c->bstage_ev));
     c->bstage_pending = 0;
-    if (words > c->bstage_words) {
-        HIP_OK(c, hipDeviceSynchronize());          /* (kernels of an earlier batch may still read the device copy) */
-        free_batch_stage(c);
-        const uint64_t cap = words + words / 4 + 64;
-        HIP_OK(c, hipHostMalloc((void **)&c->h_bstage, cap * sizeof(uint64_t), hipHostMallocDefault));
-        HIP_OK(c, hipMalloc((void **)&c->d_bstage, cap * sizeof(uint64_t)));
-        c->bstage_words = cap;
-    }
+    const int rc = grow_ws(c, G_BSTAGE, words);
     *h = c->h_bstage;
-    return HUFE_OK;
+    return rc;
 }
 
 static int batch_upload(hufgpu_ctx *c, uint64_t words, hipStream_t s)

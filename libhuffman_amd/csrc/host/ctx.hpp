@@ -1,11 +1,13 @@
-/* ctx.hpp - the per-device context of the device C ABI (include/huffman_gpu.h): the struct, the error text, create and
-   destroy, and every workspace of it - each feature's free_* / ensure_* pair lives here, next to the members it owns.
-   Part of hufgpu_api.hip (one translation unit). */
+/* ctx.hpp - the per-device context of the device C ABI (include/huffman_gpu.h): the struct, the error text, the one
+   table of its workspaces behind the struct (host/workspace.hpp grows and frees what the table describes; DESIGN.md,
+   "The context's workspaces"), create and destroy.  Part of hufgpu_api.hip (one translation unit). */
 #pragma once
+
+#include "workspace.hpp"
 
 struct hufgpu_ctx {
     int device;
-    hipStream_t stream;
+    hipStream_t stream;           /* NULL, the device's default stream: ordered with every blocking stream (torch's default included) */
     char err[512];
 
     /* encode workspace, sized for ws_blocks blocks */
@@ -39,7 +41,7 @@ struct hufgpu_ctx {
     uint64_t *d_cand, *d_cand_end, *d_chain;
     int32_t *d_cand_status;
     uint32_t *d_nxt;
-    uint64_t *d_walk;             /* 5 result words of walk_kernel */
+    uint64_t *d_walk;             /* 5 result words of walk_kernel (fixed) */
     uint64_t *d_spec_off;         /* speculative output offsets of the candidates (disc_cands + 1) */
 
     /* blocks of many MiB in a raw stream: the sub-index built for them (kernels/spec_index.hpp) */
@@ -47,11 +49,12 @@ struct hufgpu_ctx {
     uint64_t *d_big_entry, *d_big_exit, *d_big_pre, *d_big_wgpre, *d_big_wgscratch, *d_big_first_pos, *d_big_first_g, *d_big_last_pos;
     uint32_t *d_big_cnt;
     void *d_big_sub;
-    uint64_t *d_big_offs;         /* SPEC_WORDS status words, then the two-entry block index */
+    uint64_t *d_big_offs;         /* SPEC_WORDS status words, then the two-entry block index (fixed) */
 
+    uint64_t fixed_ws;            /* 1 once the fixed group stands: the buffers marked (fixed), allocated by create */
     uint64_t *d_result;           /* 8 words: err, raw_len, failing block / consumed, blocks, complete consumed, complete raw */
     uint64_t complete_used, complete_raw;   /* of the last hufgpu_decode_stream(): see hufgpu_decode_stream_complete() */
-    uint64_t *h_result;           /* pinned mirror */
+    uint64_t *h_result;           /* pinned mirror (d_result, h_result, d_zipf: fixed) */
     uint64_t *d_zipf;             /* 255 cumulative weights */
 
     /* per-kernel timing: every profiled call records HIP events around its kernels into the
@@ -92,7 +95,7 @@ struct hufgpu_ctx {
     unsigned long long *d_rcover;
     uint64_t *d_rrel, *d_rplan;
     uint32_t *d_rflag;
-    unsigned long long *d_rcounters;
+    unsigned long long *d_rcounters;          /* (fixed) */
     unsigned long long *d_rtpairs;            /* the tile route's (range, tile) pairs per block (kernels/range_tiles.hpp) */
     uint64_t rcounters[8];                    /* hufgpu_ranges_counters(): of the last hufgpu_decode_ranges */
     uint8_t *d_rscratch;
@@ -103,7 +106,7 @@ struct hufgpu_ctx {
     uint64_t gws_blocks, gws_parts;
     uint32_t *d_gcnt, *d_glist;
     TwoLevel gat_scan;
-    uint64_t *d_gtotal;
+    uint64_t *d_gtotal;                       /* (fixed) */
     void *d_gparts;
     int cus;                                  /* compute units of the device */
 
@@ -116,14 +119,14 @@ struct hufgpu_ctx {
     uint64_t sbws_blocks, sbws_chunks;
     uint32_t *d_sb_state;
     uint64_t *d_sb_pay, *d_sb_chunk_tot, *d_sb_chunk_bits;
-    unsigned long long *d_sb_unbuilt;
+    unsigned long long *d_sb_unbuilt;         /* (fixed) */
 
     /* hufgpu_update_ranges (kernels/update.hpp): the touched blocks' rows, the new index when the caller wants none,
      * the copy pieces' first blocks */
     uint64_t uws_blocks, uws_pieces;
     uint32_t *d_urow_of, *d_urow_blk, *d_upiece;
     uint64_t *d_upairs, *d_unew;
-    unsigned long long *d_ucount;
+    unsigned long long *d_ucount;             /* (fixed) */
 };
 
 static char g_err[512] = "";
@@ -150,6 +153,196 @@ static void set_err(hufgpu_ctx *ctx, const char *fmt, ...)
         }                                                                                   \
     } while (0)
 
+/* ---- the workspaces: every buffer above but the profiling events is a row here (host/workspace.hpp) ---- */
+
+static hipError_t g_ws_error = hipSuccess;   /* of the hook that failed last: grow_ws() words its report with it */
+static int ws_hip(hipError_t e)
+{
+    if (e == hipSuccess) return 0;
+    g_ws_error = e;
+    (void)hipGetLastError();
+    return 1;
+}
+static int ws_hip_alloc_device(void **p, uint64_t bytes) { return ws_hip(hipMalloc(p, bytes)); }
+static int ws_hip_alloc_pinned(void **p, uint64_t bytes) { return ws_hip(hipHostMalloc(p, bytes, hipHostMallocDefault)); }
+static void ws_hip_free_device(void *p) { (void)hipFree(p); }
+static void ws_hip_free_pinned(void *p) { (void)hipHostFree(p); }
+static int ws_hip_zero_device(void *p, uint64_t bytes) { return ws_hip(hipMemset(p, 0, bytes)); }
+/* The one wait rule: the whole device.  A call may have left work on any stream of the caller's, a non-blocking one
+ * included, that still uses the buffers about to go, and the zeros of a new buffer must be there before a kernel on such
+ * a stream counts on them.  Only a growth pays for it. */
+static int ws_hip_wait(void) { return ws_hip(hipDeviceSynchronize()); }
+static const ws_hooks WS_HIP = {ws_hip_alloc_device, ws_hip_alloc_pinned, ws_hip_free_device, ws_hip_free_pinned,
+                                ws_hip_zero_device, ws_hip_wait};
+
+/* a buffer of `expr` bytes, n and m being the capacities of its group */
+#define WS_ROW(type, member, flags, expr) \
+    {offsetof(type, member), [](uint64_t n, uint64_t m) -> uint64_t { (void)n; (void)m; return (expr); }, flags}
+#define DEV(member, expr) WS_ROW(hufgpu_ctx, member, 0, expr)
+#define DEV0(member, expr) WS_ROW(hufgpu_ctx, member, WS_ZERO, expr)
+#define PIN(member, expr) WS_ROW(hufgpu_ctx, member, WS_PINNED, expr)
+#define SCAN_GROUPS(n) ((n) / SCAN_GROUP + 2)
+
+/* a two-level prefix sum over n values (kernels/offsets.hpp); the counters start, and are left, at zero.  gmin is a row
+ * of the one group that combines a minimum */
+static const ws_buf WS_SCAN[] = {
+    WS_ROW(TwoLevel, vals, 0, n * sizeof(uint64_t)),
+    WS_ROW(TwoLevel, local, 0, n * sizeof(uint64_t)),
+    WS_ROW(TwoLevel, gsum, 0, SCAN_GROUPS(n) * sizeof(uint64_t)),
+    WS_ROW(TwoLevel, gprefix, 0, SCAN_GROUPS(n) * sizeof(uint64_t)),
+    WS_ROW(TwoLevel, gcount, WS_ZERO, SCAN_GROUPS(n) * SCAN_TICKET_STRIDE * sizeof(uint32_t)),
+    WS_ROW(TwoLevel, done, WS_ZERO, sizeof(uint32_t)),
+};
+/* what create allocates once: the result words and their pinned mirror, the zipf weights, the status words of the
+ * features (SPEC_WORDS status words, then the two-entry block index, for the blocks of many MiB) */
+static const ws_buf WS_FIXED[] = {
+    DEV(d_result, 8 * sizeof(uint64_t)), PIN(h_result, 16 * sizeof(uint64_t)), DEV(d_walk, DISC_WORDS * sizeof(uint64_t)),
+    DEV(d_zipf, 255 * sizeof(uint64_t)), DEV(d_big_offs, (SPEC_WORDS + 2) * sizeof(uint64_t)),
+    DEV(d_rcounters, 8 * sizeof(unsigned long long)), DEV(d_gtotal, sizeof(uint64_t)),
+    DEV(d_ucount, UPD_WORDS * sizeof(unsigned long long)), DEV(d_sb_unbuilt, sizeof(unsigned long long)),
+};
+static const ws_buf WS_ENCODE[] = {
+    DEV(d_hist, n * HUF_NSYM * sizeof(uint64_t)),   /* (64-bit counts for chunked blocks) */
+    DEV(d_codetab, n * HUF_NSYM * sizeof(hufcode_t)), DEV(d_treebuf, n * HUF_TREE_STRIDE * sizeof(int16_t)),
+    DEV(d_meta, n * sizeof(HufBlockMeta)), DEV(d_offsets, (n + 1) * sizeof(uint64_t)),
+};
+static const ws_buf WS_CHUNK[] = {
+    DEV(d_chunk_hist, n * HUF_NSYM * sizeof(uint32_t)), DEV(d_chunk_tot, n * sizeof(uint64_t)), DEV(d_chunk_bits, n * sizeof(uint64_t)),
+};
+static const ws_buf WS_DECODE[] = {
+    DEV(d_dmeta, n * sizeof(HufDecodeMeta)), DEV(d_out_offsets, (n + 1) * sizeof(uint64_t)), DEV(d_status, n * sizeof(int32_t)),
+    DEV0(d_fix_count, 2 * sizeof(uint32_t)), DEV(d_fix_blocks, n * sizeof(uint32_t)), DEV0(d_fix_flag, n * sizeof(uint32_t)),
+    DEV(dec_lens.gmin, SCAN_GROUPS(n) * sizeof(uint64_t)),
+};
+#define DISC_GCAP(n) (((n) + DISC_SCAN_GROUP - 1) / DISC_SCAN_GROUP + 1)
+static const ws_buf WS_DISC_WGS[] = {
+    DEV(d_wg_counts, n * sizeof(uint32_t)),
+    DEV(d_wg_base, (n + 1 + 2 * DISC_GCAP(n)) * sizeof(uint64_t)),     /* local sums, then the groups' bases and totals */
+    DEV(d_disc_masks, n * DISC_THREADS * sizeof(uint64_t)), DEV(d_disc_slots, n * DISC_SLOTS * sizeof(DiscSlot)),
+};
+static const ws_buf WS_DISC_CANDS[] = {
+    DEV(d_cand, n * sizeof(uint64_t)), DEV(d_cand_end, n * sizeof(uint64_t)), DEV(d_chain, (n + 1) * sizeof(uint64_t)),
+    DEV(d_cand_status, n * sizeof(int32_t)), DEV(d_nxt, n * sizeof(uint32_t)), DEV(d_spec_off, (n + 1) * sizeof(uint64_t)),
+};
+static const ws_buf WS_BIG_LANES[] = {
+    DEV(d_big_entry, n * sizeof(uint64_t)), DEV(d_big_exit, n * sizeof(uint64_t)), DEV(d_big_pre, (n + 1) * sizeof(uint64_t)),
+    DEV(d_big_wgpre, (n / DEC_THREADS + 4) * sizeof(uint64_t)), DEV(d_big_wgscratch, (n / DEC_THREADS + 4) * sizeof(uint64_t)),
+    DEV(d_big_first_pos, n * sizeof(uint64_t)), DEV(d_big_first_g, n * sizeof(uint64_t)), DEV(d_big_last_pos, n * sizeof(uint64_t)),
+    DEV(d_big_cnt, n * sizeof(uint32_t)),
+};
+static const ws_buf WS_BIG_SUB[] = {DEV(d_big_sub, n)};
+static const ws_buf WS_BSTAGE[] = {PIN(h_bstage, n * sizeof(uint64_t)), DEV(d_bstage, n * sizeof(uint64_t))};
+static const ws_buf WS_BATCH[] = {     /* n blocks, m items */
+    DEV(d_bprefix, (n + 1) * sizeof(uint64_t)), DEV(d_bobase, n * sizeof(uint64_t)), DEV0(d_bzero, SCAN_GROUPS(n) * sizeof(uint64_t)),
+    DEV(d_blk_item, n * sizeof(uint32_t)), DEV(d_item_fail, m * sizeof(unsigned long long)), DEV(d_item_res, 3 * m * sizeof(uint64_t)),
+    DEV(d_bitem_offs, (m + 1) * sizeof(uint64_t)), PIN(h_item_res, 3 * m * sizeof(uint64_t)),
+};
+static const ws_buf WS_RANGE[] = {     /* n blocks, m ranges */
+    DEV(d_rcover, n * sizeof(unsigned long long)), DEV(d_rrel, n * sizeof(uint64_t)), DEV(d_rtpairs, n * sizeof(unsigned long long)),
+    DEV(d_rplan, 4 * m * sizeof(uint64_t)), DEV(d_rflag, m * sizeof(uint32_t)),
+};
+static const ws_buf WS_RSCRATCH[] = {DEV(d_rscratch, n)};
+static const ws_buf WS_GATHER_BLOCKS[] = {DEV(d_gcnt, 2 * n * sizeof(uint32_t)), DEV(d_glist, n * sizeof(uint32_t))};
+static const ws_buf WS_GATHER_PARTS[] = {DEV(d_gparts, n * sizeof(GatherPart))};
+static const ws_buf WS_FIND_WORDS[] = {DEV(d_fbitmap, n * sizeof(uint32_t))};
+static const ws_buf WS_FIND_TILES[] = {DEV(d_ftcnt, n * sizeof(uint32_t))};
+static const ws_buf WS_SB_BLOCKS[] = {DEV(d_sb_state, n * sizeof(uint32_t)), DEV(d_sb_pay, n * sizeof(uint64_t))};
+static const ws_buf WS_SB_CHUNKS[] = {DEV(d_sb_chunk_tot, n * sizeof(uint64_t)), DEV(d_sb_chunk_bits, n * sizeof(uint64_t))};
+static const ws_buf WS_UPD_BLOCKS[] = {
+    DEV(d_urow_of, n * sizeof(uint32_t)), DEV(d_urow_blk, n * sizeof(uint32_t)), DEV(d_upairs, 2 * n * sizeof(uint64_t)),
+    DEV(d_unew, (n + 1) * sizeof(uint64_t)),
+};
+static const ws_buf WS_UPD_PIECES[] = {DEV(d_upiece, n * sizeof(uint32_t))};
+
+/* The groups.  Most grow by an eighth; the staging area by a quarter; gather and find double, since their bounds come
+ * from the host's arguments (records x parts, the layout of all blocks) and jump from call to call; the sub-index of a
+ * block of many MiB and the range scratch take what they are asked for (grow_range_scratch adds its own eighth).
+ * Soft groups report nothing: the caller has another way, or words the error itself. */
+enum { G_FIXED, G_ENCODE, G_CHUNK, G_DECODE, G_DISC_WGS, G_DISC_CANDS, G_BIG_LANES, G_BIG_SUB, G_BSTAGE, G_BATCH, G_RANGE,
+       G_RSCRATCH, G_GATHER_BLOCKS, G_GATHER_PARTS, G_FIND_WORDS, G_FIND_TILES, G_SB_BLOCKS, G_SB_CHUNKS, G_UPD_BLOCKS,
+       G_UPD_PIECES, G_COUNT };
+#define ROWS(a) a, (int)(sizeof(a) / sizeof(a[0]))
+#define CAP(member) {offsetof(hufgpu_ctx, member), WS_NO_CAP}
+#define CAPS(m0, m1) {offsetof(hufgpu_ctx, m0), offsetof(hufgpu_ctx, m1)}
+#define NO_SCAN NULL, 0, 0
+#define SCAN_AT(member) ROWS(WS_SCAN), offsetof(hufgpu_ctx, member)
+static const ws_group WS[G_COUNT] = {
+    {"fixed", ROWS(WS_FIXED), CAP(fixed_ws), WS_EXACT, false, NO_SCAN},
+    {"encode", ROWS(WS_ENCODE), CAP(ws_blocks), WS_EIGHTH, false, SCAN_AT(enc_sizes)},
+    {"encode chunks", ROWS(WS_CHUNK), CAP(ws_chunks), WS_EIGHTH, false, NO_SCAN},
+    {"decode", ROWS(WS_DECODE), CAP(dws_blocks), WS_EIGHTH, false, SCAN_AT(dec_lens)},
+    {"discovery workgroups", ROWS(WS_DISC_WGS), CAP(disc_wgs), WS_EIGHTH, false, NO_SCAN},
+    {"discovery candidates", ROWS(WS_DISC_CANDS), CAP(disc_cands), WS_EIGHTH, false, NO_SCAN},
+    {"big-block lanes", ROWS(WS_BIG_LANES), CAP(big_lanes), WS_EIGHTH, true, NO_SCAN},
+    {"big-block sub-index", ROWS(WS_BIG_SUB), CAP(big_sub_bytes), WS_EXACT, true, NO_SCAN},
+    {"batch staging", ROWS(WS_BSTAGE), CAP(bstage_words), WS_QUARTER, false, NO_SCAN},
+    {"batch", ROWS(WS_BATCH), CAPS(bws_blocks, bws_items), WS_EIGHTH, false, NO_SCAN},
+    {"ranges", ROWS(WS_RANGE), CAPS(rws_blocks, rws_ranges), WS_EIGHTH, false, NO_SCAN},
+    {"range scratch", ROWS(WS_RSCRATCH), CAP(rscratch_bytes), WS_EXACT, true, NO_SCAN},
+    {"gather blocks", ROWS(WS_GATHER_BLOCKS), CAP(gws_blocks), WS_DOUBLE, false, SCAN_AT(gat_scan)},
+    {"gather parts", ROWS(WS_GATHER_PARTS), CAP(gws_parts), WS_DOUBLE, false, NO_SCAN},
+    {"find words", ROWS(WS_FIND_WORDS), CAP(fws_words), WS_DOUBLE, false, NO_SCAN},
+    {"find tiles", ROWS(WS_FIND_TILES), CAP(fws_tiles), WS_DOUBLE, false, SCAN_AT(find_scan)},
+    {"sub-build blocks", ROWS(WS_SB_BLOCKS), CAP(sbws_blocks), WS_EIGHTH, false, NO_SCAN},
+    {"sub-build chunks", ROWS(WS_SB_CHUNKS), CAP(sbws_chunks), WS_EIGHTH, false, NO_SCAN},
+    {"update blocks", ROWS(WS_UPD_BLOCKS), CAP(uws_blocks), WS_EIGHTH, false, NO_SCAN},
+    {"update pieces", ROWS(WS_UPD_PIECES), CAP(uws_pieces), WS_EIGHTH, false, NO_SCAN},
+};
+
+/* Room in one group (ws_grow): HUFE_OK; HUFE_FATAL with the error text for a hard group; HUFE_MEMORY, silently, for a
+ * soft one.  A failed growth leaves the group without buffers and at capacity 0. */
+static int grow_ws(hufgpu_ctx *c, int group, uint64_t need0, uint64_t need1 = 0)
+{
+    if (ws_grow(&WS_HIP, c, &WS[group], need0, need1) == 0) return HUFE_OK;
+    if (WS[group].soft) return HUFE_MEMORY;
+    set_err(c, "no workspace for %s (%llu, %llu): %s", WS[group].name, (unsigned long long)need0, (unsigned long long)need1,
+            hipGetErrorString(g_ws_error));
+    return HUFE_FATAL;
+}
+static int grow_ws2(hufgpu_ctx *c, int g0, uint64_t need0, int g1, uint64_t need1)
+{
+    const int rc = grow_ws(c, g0, need0);
+    return rc ? rc : grow_ws(c, g1, need1);
+}
+
+static int ensure_encode_ws(hufgpu_ctx *c, uint64_t nblocks)
+{
+    const bool grows = nblocks > c->ws_blocks;
+    const int rc = grow_ws(c, G_ENCODE, nblocks);
+    if (grows) ws_release(&WS_HIP, c, &WS[G_CHUNK]);   /* the chunk arrays have always gone with it (grow_ws has waited) */
+    return rc;
+}
+static int ensure_chunk_ws(hufgpu_ctx *c, uint64_t nchunks) { return grow_ws(c, G_CHUNK, nchunks); }
+static int ensure_decode_ws(hufgpu_ctx *c, uint64_t nblocks) { return grow_ws(c, G_DECODE, nblocks); }
+static int ensure_batch_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t nitems) { return grow_ws(c, G_BATCH, nblocks, nitems); }
+static int ensure_range_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t nranges) { return grow_ws(c, G_RANGE, nblocks, nranges); }
+static int ensure_gather_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t nparts) { return grow_ws2(c, G_GATHER_BLOCKS, nblocks, G_GATHER_PARTS, nparts); }
+static int ensure_find_ws(hufgpu_ctx *c, uint64_t nwords, uint64_t ntiles) { return grow_ws2(c, G_FIND_WORDS, nwords, G_FIND_TILES, ntiles); }
+static int ensure_update_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t npieces) { return grow_ws2(c, G_UPD_BLOCKS, nblocks, G_UPD_PIECES, npieces); }
+static int ensure_sub_build_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t nchunks) { return grow_ws2(c, G_SB_BLOCKS, nblocks, G_SB_CHUNKS, nchunks); }
+
+/* The scratch area that hufgpu_decode_ranges, hufgpu_build_sub_index, hufgpu_update_ranges and hufgpu_append share: at
+ * least `bytes` bytes, with an eighth of room to grow into when that can be had.  HUFE_MEMORY (the area is then gone)
+ * when it cannot; the caller words the error. */
+static int grow_range_scratch(hufgpu_ctx *ctx, uint64_t bytes)
+{
+    if (bytes <= ctx->rscratch_bytes) return HUFE_OK;
+    if (bytes > ((uint64_t)1 << 46)) {
+        (void)ws_hip_wait();
+        ws_release(&WS_HIP, ctx, &WS[G_RSCRATCH]);
+        return HUFE_MEMORY;
+    }
+    if (grow_ws(ctx, G_RSCRATCH, bytes + bytes / 8) == HUFE_OK) return HUFE_OK;
+    return grow_ws(ctx, G_RSCRATCH, bytes);
+}
+
+static void free_batch_stage(hufgpu_ctx *c)
+{
+    if (c->bstage_pending) (void)hipEventSynchronize(c->bstage_ev);
+    ws_release(&WS_HIP, c, &WS[G_BSTAGE]);
+    c->bstage_pending = 0;
+}
+
 extern "C" int hufgpu_device_count(void)
 {
     int n = 0;
@@ -166,6 +359,22 @@ extern "C" int hufgpu_device_count(void)
 }
 
 extern "C" const char *hufgpu_last_error(const hufgpu_ctx_t *ctx) { return ctx ? ctx->err : g_err; }
+
+/* the device side of a new context: the fixed group and the zipf weights */
+static int ctx_init(hufgpu_ctx *ctx)
+{
+    HIP_OK(NULL, hipSetDevice(ctx->device));
+    const int rc = grow_ws(ctx, G_FIXED, 1);
+    if (rc) return rc;
+    /* zipf255 cumulative weights: w_r = floor(2^32 / r), r = 1..255 (SURVEY §8d) */
+    uint64_t cum[255], acc = 0;
+    for (int r = 1; r <= 255; r++) {
+        acc += (1ull << 32) / (uint64_t)r;
+        cum[r - 1] = acc;
+    }
+    HIP_OK(ctx, hipMemcpy(ctx->d_zipf, cum, sizeof(cum), hipMemcpyHostToDevice));
+    return HUFE_OK;
+}
 
 extern "C" int hufgpu_ctx_create(hufgpu_ctx_t **out, int device)
 {
@@ -193,403 +402,31 @@ extern "C" int hufgpu_ctx_create(hufgpu_ctx_t **out, int device)
     if (!ctx) return HUFE_MEMORY;
     ctx->device = device;
     ctx->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HIP_OK(NULL, hipSetDevice(device));
-    ctx->stream = NULL;   /* the device's default stream: ordered with every blocking stream (torch's default included) */
-    HIP_OK(ctx, hipMalloc((void **)&ctx->d_result, 8 * sizeof(uint64_t)));
-    HIP_OK(ctx, hipMalloc((void **)&ctx->d_walk, DISC_WORDS * sizeof(uint64_t)));
-    HIP_OK(ctx, hipHostMalloc((void **)&ctx->h_result, 16 * sizeof(uint64_t), hipHostMallocDefault));
-
-    /* zipf255 cumulative weights: w_r = floor(2^32 / r), r = 1..255 (SURVEY §8d) */
-    uint64_t cum[255], acc = 0;
-    for (int r = 1; r <= 255; r++) {
-        acc += (1ull << 32) / (uint64_t)r;
-        cum[r - 1] = acc;
+    const int rc = ctx_init(ctx);
+    if (rc) {
+        (void)hufgpu_ctx_destroy(ctx);   /* (the text stays in hufgpu_last_error(NULL)) */
+        return rc;
     }
-    HIP_OK(ctx, hipMalloc((void **)&ctx->d_zipf, sizeof(cum)));
-    HIP_OK(ctx, hipMemcpy(ctx->d_zipf, cum, sizeof(cum), hipMemcpyHostToDevice));
     *out = ctx;
     return HUFE_OK;
 }
 
 extern "C" int hufgpu_ctx_device(const hufgpu_ctx_t *ctx) { return ctx ? ctx->device : -1; }
 
-/* workspace of a two-level prefix sum over `cap` blocks; counters start (and are left) at zero */
-static int alloc_two_level(hufgpu_ctx *c, TwoLevel *t, uint64_t cap, bool with_min)
-{
-    const uint64_t groups = cap / SCAN_GROUP + 2;
-    memset(t, 0, sizeof(*t));
-    HIP_OK(c, hipMalloc((void **)&t->vals, cap * sizeof(uint64_t)));
-    HIP_OK(c, hipMalloc((void **)&t->local, cap * sizeof(uint64_t)));
-    HIP_OK(c, hipMalloc((void **)&t->gsum, groups * sizeof(uint64_t)));
-    HIP_OK(c, hipMalloc((void **)&t->gprefix, groups * sizeof(uint64_t)));
-    HIP_OK(c, hipMalloc((void **)&t->gcount, groups * SCAN_TICKET_STRIDE * sizeof(uint32_t)));
-    HIP_OK(c, hipMalloc((void **)&t->done, sizeof(uint32_t)));
-    if (with_min) HIP_OK(c, hipMalloc((void **)&t->gmin, groups * sizeof(uint64_t)));
-    HIP_OK(c, hipMemset(t->gcount, 0, groups * SCAN_TICKET_STRIDE * sizeof(uint32_t)));
-    HIP_OK(c, hipMemset(t->done, 0, sizeof(uint32_t)));
-    HIP_OK(c, hipDeviceSynchronize());   /* the kernels may run on a non-blocking stream: the zeros must be there first */
-    return HUFE_OK;
-}
-
-static void free_two_level(TwoLevel *t)
-{
-    (void)hipFree(t->vals); (void)hipFree(t->local); (void)hipFree(t->gsum); (void)hipFree(t->gprefix);
-    (void)hipFree(t->gcount); (void)hipFree(t->done); (void)hipFree(t->gmin);
-    memset(t, 0, sizeof(*t));
-}
-
-static void free_encode_ws(hufgpu_ctx *c)
-{
-    free_two_level(&c->enc_sizes);
-    (void)hipFree(c->d_hist);
-    (void)hipFree(c->d_codetab);
-    (void)hipFree(c->d_treebuf);
-    (void)hipFree(c->d_meta);
-    (void)hipFree(c->d_offsets);
-    (void)hipFree(c->d_chunk_hist); (void)hipFree(c->d_chunk_tot); (void)hipFree(c->d_chunk_bits);
-    c->d_chunk_hist = NULL; c->d_chunk_tot = NULL; c->d_chunk_bits = NULL; c->ws_chunks = 0;
-    c->d_hist = NULL; c->d_codetab = NULL; c->d_treebuf = NULL; c->d_meta = NULL; c->d_offsets = NULL;
-    c->ws_blocks = 0;
-}
-
-static void free_disc_ws(hufgpu_ctx *c, int which)
-{
-    if (which & 1) { (void)hipFree(c->d_wg_counts); (void)hipFree(c->d_wg_base); (void)hipFree(c->d_disc_masks); (void)hipFree(c->d_disc_slots); c->d_disc_slots = NULL; c->d_wg_counts = NULL; c->d_wg_base = NULL; c->d_disc_masks = NULL; c->disc_wgs = 0; }
-    if (which & 2) {
-        (void)hipFree(c->d_cand); (void)hipFree(c->d_cand_end); (void)hipFree(c->d_chain); (void)hipFree(c->d_cand_status); (void)hipFree(c->d_nxt); (void)hipFree(c->d_spec_off);
-        c->d_cand = c->d_cand_end = c->d_chain = NULL; c->d_cand_status = NULL; c->d_nxt = NULL; c->d_spec_off = NULL; c->disc_cands = 0;
-    }
-}
-
-static void free_big_ws(hufgpu_ctx *c, int which)
-{
-    if (which & 1) {
-        (void)hipFree(c->d_big_entry); (void)hipFree(c->d_big_exit); (void)hipFree(c->d_big_pre); (void)hipFree(c->d_big_cnt);
-        (void)hipFree(c->d_big_wgpre); (void)hipFree(c->d_big_wgscratch);
-        (void)hipFree(c->d_big_first_pos); (void)hipFree(c->d_big_first_g); (void)hipFree(c->d_big_last_pos);
-        c->d_big_entry = c->d_big_exit = c->d_big_pre = c->d_big_wgpre = c->d_big_wgscratch = NULL; c->d_big_cnt = NULL; c->big_lanes = 0;
-        c->d_big_first_pos = c->d_big_first_g = c->d_big_last_pos = NULL;
-    }
-    if (which & 4) { (void)hipFree(c->d_big_sub); c->d_big_sub = NULL; c->big_sub_bytes = 0; }
-    if (which & 8) { (void)hipFree(c->d_big_offs); c->d_big_offs = NULL; }
-}
-
-static void free_decode_ws(hufgpu_ctx *c)
-{
-    free_two_level(&c->dec_lens);
-    (void)hipFree(c->d_dmeta);
-    (void)hipFree(c->d_out_offsets);
-    (void)hipFree(c->d_status);
-    (void)hipFree(c->d_fix_count); (void)hipFree(c->d_fix_blocks); (void)hipFree(c->d_fix_flag);
-    c->d_fix_count = NULL; c->d_fix_blocks = NULL; c->d_fix_flag = NULL;
-    c->d_dmeta = NULL; c->d_out_offsets = NULL; c->d_status = NULL;
-    c->dws_blocks = 0;
-}
-
-static void free_batch_ws(hufgpu_ctx *c)
-{
-    (void)hipFree(c->d_bprefix); (void)hipFree(c->d_bobase); (void)hipFree(c->d_bzero); (void)hipFree(c->d_blk_item);
-    (void)hipFree(c->d_item_fail); (void)hipFree(c->d_item_res); (void)hipFree(c->d_bitem_offs); (void)hipHostFree(c->h_item_res);
-    c->d_bprefix = c->d_bobase = c->d_bzero = NULL; c->d_blk_item = NULL; c->d_item_fail = NULL;
-    c->d_item_res = c->h_item_res = c->d_bitem_offs = NULL;
-    c->bws_blocks = c->bws_items = 0;
-}
-
-static void free_range_ws(hufgpu_ctx *c)
-{
-    (void)hipFree(c->d_rcover); (void)hipFree(c->d_rrel); (void)hipFree(c->d_rplan); (void)hipFree(c->d_rflag); (void)hipFree(c->d_rtpairs);
-    c->d_rcover = NULL; c->d_rrel = c->d_rplan = NULL; c->d_rflag = NULL; c->d_rtpairs = NULL;
-    c->rws_blocks = c->rws_ranges = 0;
-}
-
-static void free_gather_ws(hufgpu_ctx *c, int which)
-{
-    if (which & 1) {
-        if (c->gws_blocks) free_two_level(&c->gat_scan);
-        (void)hipFree(c->d_gcnt); (void)hipFree(c->d_glist);
-        c->d_gcnt = c->d_glist = NULL; c->gws_blocks = 0;
-    }
-    if (which & 2) { (void)hipFree(c->d_gparts); c->d_gparts = NULL; c->gws_parts = 0; }
-}
-
-static void free_find_ws(hufgpu_ctx *c, int which)
-{
-    if (which & 1) { (void)hipFree(c->d_fbitmap); c->d_fbitmap = NULL; c->fws_words = 0; }
-    if (which & 2) {
-        if (c->fws_tiles) free_two_level(&c->find_scan);
-        (void)hipFree(c->d_ftcnt);
-        c->d_ftcnt = NULL; c->fws_tiles = 0;
-    }
-}
-
-static void free_range_scratch(hufgpu_ctx *c)
-{
-    (void)hipFree(c->d_rscratch);
-    c->d_rscratch = NULL;
-    c->rscratch_bytes = 0;
-}
-
-/* The scratch area that hufgpu_decode_ranges, hufgpu_build_sub_index and hufgpu_update_ranges share: at least `bytes`
- * bytes, with an eighth of room to grow into when that can be had.  HUFE_MEMORY (the area is then gone) when it cannot. */
-static int grow_range_scratch(hufgpu_ctx *ctx, uint64_t bytes)
-{
-    if (bytes <= ctx->rscratch_bytes) return HUFE_OK;
-    HIP_OK(ctx, hipDeviceSynchronize());
-    free_range_scratch(ctx);
-    if (bytes > ((uint64_t)1 << 46)) return HUFE_MEMORY;
-    uint64_t got = bytes + bytes / 8;
-    if (hipMalloc((void **)&ctx->d_rscratch, got) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->d_rscratch = NULL;
-        got = bytes;
-        if (hipMalloc((void **)&ctx->d_rscratch, got) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->d_rscratch = NULL;
-            return HUFE_MEMORY;
-        }
-    }
-    ctx->rscratch_bytes = got;
-    return HUFE_OK;
-}
-
-static void free_sub_build_ws(hufgpu_ctx *c, int which)
-{
-    if (which & 1) { (void)hipFree(c->d_sb_state); (void)hipFree(c->d_sb_pay); c->d_sb_state = NULL; c->d_sb_pay = NULL; c->sbws_blocks = 0; }
-    if (which & 2) { (void)hipFree(c->d_sb_chunk_tot); (void)hipFree(c->d_sb_chunk_bits); c->d_sb_chunk_tot = c->d_sb_chunk_bits = NULL; c->sbws_chunks = 0; }
-}
-
-static void free_update_ws(hufgpu_ctx *c, int which)
-{
-    if (which & 1) {
-        (void)hipFree(c->d_urow_of); (void)hipFree(c->d_urow_blk); (void)hipFree(c->d_upairs); (void)hipFree(c->d_unew);
-        c->d_urow_of = c->d_urow_blk = NULL; c->d_upairs = c->d_unew = NULL; c->uws_blocks = 0;
-    }
-    if (which & 2) { (void)hipFree(c->d_upiece); c->d_upiece = NULL; c->uws_pieces = 0; }
-}
-
-static void free_batch_stage(hufgpu_ctx *c)
-{
-    if (c->bstage_pending) (void)hipEventSynchronize(c->bstage_ev);
-    (void)hipHostFree(c->h_bstage); (void)hipFree(c->d_bstage);
-    c->h_bstage = c->d_bstage = NULL;
-    c->bstage_words = 0;
-    c->bstage_pending = 0;
-}
-
 extern "C" int hufgpu_ctx_destroy(hufgpu_ctx_t *ctx)
 {
     if (!ctx) return HUFE_ARGUMENT;
     (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)ws_hip_wait();
     free_batch_stage(ctx);
     if (ctx->bstage_ev) (void)hipEventDestroy(ctx->bstage_ev);
-    free_batch_ws(ctx);
-    free_range_ws(ctx);
-    free_range_scratch(ctx);
-    free_gather_ws(ctx, 3);
-    (void)hipFree(ctx->d_gtotal);
-    free_find_ws(ctx, 3);
-    (void)hipFree(ctx->d_rcounters);
-    free_sub_build_ws(ctx, 3);
-    (void)hipFree(ctx->d_sb_unbuilt);
-    free_update_ws(ctx, 3);
-    (void)hipFree(ctx->d_ucount);
-    free_encode_ws(ctx);
-    free_decode_ws(ctx);
-    free_disc_ws(ctx, 3);
-    free_big_ws(ctx, 15);
-    (void)hipFree(ctx->d_walk);
-    (void)hipFree(ctx->d_result);
-    (void)hipFree(ctx->d_zipf);
-    (void)hipHostFree(ctx->h_result);
+    ws_release_all(&WS_HIP, ctx, WS, G_COUNT);
     if (ctx->ev) {
         for (int k = 0; k < PROF_SLOTS; k++)
             for (int i = 0; i <= MAX_STAGES; i++) (void)hipEventDestroy(ctx->ev[k][i]);
         free(ctx->ev);
     }
     free(ctx);
-    return HUFE_OK;
-}
-
-static int ensure_encode_ws(hufgpu_ctx *c, uint64_t nblocks)
-{
-    if (nblocks <= c->ws_blocks) return HUFE_OK;
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    free_encode_ws(c);
-    const uint64_t cap = nblocks + nblocks / 8 + 16;
-    HIP_OK(c, hipMalloc((void **)&c->d_hist, cap * HUF_NSYM * sizeof(uint64_t)));   /* (64-bit counts for chunked blocks) */
-    HIP_OK(c, hipMalloc((void **)&c->d_codetab, cap * HUF_NSYM * sizeof(hufcode_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_treebuf, cap * HUF_TREE_STRIDE * sizeof(int16_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_meta, cap * sizeof(HufBlockMeta)));
-    HIP_OK(c, hipMalloc((void **)&c->d_offsets, (cap + 1) * sizeof(uint64_t)));
-    int rc2 = alloc_two_level(c, &c->enc_sizes, cap, false);
-    if (rc2) return rc2;
-    c->ws_blocks = cap;
-    return HUFE_OK;
-}
-
-static int ensure_chunk_ws(hufgpu_ctx *c, uint64_t nchunks)
-{
-    if (nchunks <= c->ws_chunks) return HUFE_OK;
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_chunk_hist); (void)hipFree(c->d_chunk_tot); (void)hipFree(c->d_chunk_bits);
-    c->d_chunk_hist = NULL; c->d_chunk_tot = NULL; c->d_chunk_bits = NULL; c->ws_chunks = 0;
-    const uint64_t cap = nchunks + nchunks / 8 + 16;
-    HIP_OK(c, hipMalloc((void **)&c->d_chunk_hist, cap * HUF_NSYM * sizeof(uint32_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_chunk_tot, cap * sizeof(uint64_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_chunk_bits, cap * sizeof(uint64_t)));
-    c->ws_chunks = cap;
-    return HUFE_OK;
-}
-
-static int ensure_decode_ws(hufgpu_ctx *c, uint64_t nblocks)
-{
-    if (nblocks <= c->dws_blocks) return HUFE_OK;
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    free_decode_ws(c);
-    const uint64_t cap = nblocks + nblocks / 8 + 16;
-    HIP_OK(c, hipMalloc((void **)&c->d_dmeta, cap * sizeof(HufDecodeMeta)));
-    HIP_OK(c, hipMalloc((void **)&c->d_out_offsets, (cap + 1) * sizeof(uint64_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_status, cap * sizeof(int32_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_fix_count, 2 * sizeof(uint32_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_fix_blocks, cap * sizeof(uint32_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_fix_flag, cap * sizeof(uint32_t)));
-    HIP_OK(c, hipMemset(c->d_fix_count, 0, 2 * sizeof(uint32_t)));
-    HIP_OK(c, hipMemset(c->d_fix_flag, 0, cap * sizeof(uint32_t)));
-    int rc2 = alloc_two_level(c, &c->dec_lens, cap, true);
-    if (rc2) return rc2;
-    c->dws_blocks = cap;
-    return HUFE_OK;
-}
-
-static int ensure_batch_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t nitems)
-{
-    if (nblocks <= c->bws_blocks && nitems <= c->bws_items) return HUFE_OK;
-    HIP_OK(c, hipDeviceSynchronize());
-    const uint64_t nbc = (nblocks > c->bws_blocks ? nblocks + nblocks / 8 : c->bws_blocks) + 16;
-    const uint64_t nic = (nitems > c->bws_items ? nitems + nitems / 8 : c->bws_items) + 16;
-    free_batch_ws(c);
-    HIP_OK(c, hipMalloc((void **)&c->d_bprefix, (nbc + 1) * sizeof(uint64_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_bobase, nbc * sizeof(uint64_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_bzero, (nbc / SCAN_GROUP + 2) * sizeof(uint64_t)));
-    HIP_OK(c, hipMemset(c->d_bzero, 0, (nbc / SCAN_GROUP + 2) * sizeof(uint64_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_blk_item, nbc * sizeof(uint32_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_item_fail, nic * sizeof(unsigned long long)));
-    HIP_OK(c, hipMalloc((void **)&c->d_item_res, 3 * nic * sizeof(uint64_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_bitem_offs, (nic + 1) * sizeof(uint64_t)));
-    HIP_OK(c, hipHostMalloc((void **)&c->h_item_res, 3 * nic * sizeof(uint64_t), hipHostMallocDefault));
-    HIP_OK(c, hipDeviceSynchronize());
-    c->bws_blocks = nbc;
-    c->bws_items = nic;
-    return HUFE_OK;
-}
-
-static int ensure_range_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t nranges)
-{
-    if (!c->d_rcounters) HIP_OK(c, hipMalloc((void **)&c->d_rcounters, 8 * sizeof(unsigned long long)));
-    if (nblocks <= c->rws_blocks && nranges <= c->rws_ranges) return HUFE_OK;
-    HIP_OK(c, hipDeviceSynchronize());
-    const uint64_t nbc = (nblocks > c->rws_blocks ? nblocks + nblocks / 8 : c->rws_blocks) + 16;
-    const uint64_t nrc = (nranges > c->rws_ranges ? nranges + nranges / 8 : c->rws_ranges) + 16;
-    free_range_ws(c);
-    HIP_OK(c, hipMalloc((void **)&c->d_rcover, nbc * sizeof(unsigned long long)));
-    HIP_OK(c, hipMalloc((void **)&c->d_rrel, nbc * sizeof(uint64_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_rtpairs, nbc * sizeof(unsigned long long)));
-    HIP_OK(c, hipMalloc((void **)&c->d_rplan, 4 * nrc * sizeof(uint64_t)));
-    HIP_OK(c, hipMalloc((void **)&c->d_rflag, nrc * sizeof(uint32_t)));
-    c->rws_blocks = nbc;
-    c->rws_ranges = nrc;
-    return HUFE_OK;
-}
-
-/* sized by bounds the host knows - the blocks, records x the parts a record can have - and doubled when they grow */
-static int ensure_gather_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t nparts)
-{
-    if (!c->d_gtotal) HIP_OK(c, hipMalloc((void **)&c->d_gtotal, sizeof(uint64_t)));
-    if (nblocks > c->gws_blocks) {
-        HIP_OK(c, hipDeviceSynchronize());
-        const uint64_t cap = (nblocks > 2 * c->gws_blocks ? nblocks : 2 * c->gws_blocks) + 16;
-        free_gather_ws(c, 1);
-        HIP_OK(c, hipMalloc((void **)&c->d_gcnt, 2 * cap * sizeof(uint32_t)));
-        HIP_OK(c, hipMalloc((void **)&c->d_glist, cap * sizeof(uint32_t)));
-        const int rc = alloc_two_level(c, &c->gat_scan, cap, false);
-        if (rc) return rc;
-        c->gws_blocks = cap;
-    }
-    if (nparts > c->gws_parts) {
-        HIP_OK(c, hipDeviceSynchronize());
-        const uint64_t cap = (nparts > 2 * c->gws_parts ? nparts : 2 * c->gws_parts) + 16;
-        free_gather_ws(c, 2);
-        HIP_OK(c, hipMalloc(&c->d_gparts, cap * sizeof(GatherPart)));
-        c->gws_parts = cap;
-    }
-    return HUFE_OK;
-}
-
-/* sized by the layout - mask words and tiles of all blocks - and doubled when they grow */
-static int ensure_find_ws(hufgpu_ctx *c, uint64_t nwords, uint64_t ntiles)
-{
-    if (nwords > c->fws_words) {
-        HIP_OK(c, hipDeviceSynchronize());
-        const uint64_t cap = (nwords > 2 * c->fws_words ? nwords : 2 * c->fws_words) + 16;
-        free_find_ws(c, 1);
-        HIP_OK(c, hipMalloc((void **)&c->d_fbitmap, cap * sizeof(uint32_t)));
-        c->fws_words = cap;
-    }
-    if (ntiles > c->fws_tiles) {
-        HIP_OK(c, hipDeviceSynchronize());
-        const uint64_t cap = (ntiles > 2 * c->fws_tiles ? ntiles : 2 * c->fws_tiles) + 16;
-        free_find_ws(c, 2);
-        HIP_OK(c, hipMalloc((void **)&c->d_ftcnt, cap * sizeof(uint32_t)));
-        const int rc = alloc_two_level(c, &c->find_scan, cap, false);
-        if (rc) return rc;
-        c->fws_tiles = cap;
-    }
-    return HUFE_OK;
-}
-
-static int ensure_update_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t npieces)
-{
-    if (!c->d_ucount) HIP_OK(c, hipMalloc((void **)&c->d_ucount, UPD_WORDS * sizeof(unsigned long long)));
-    if (nblocks > c->uws_blocks) {
-        HIP_OK(c, hipDeviceSynchronize());
-        free_update_ws(c, 1);
-        const uint64_t cap = nblocks + nblocks / 8 + 16;
-        HIP_OK(c, hipMalloc((void **)&c->d_urow_of, cap * sizeof(uint32_t)));
-        HIP_OK(c, hipMalloc((void **)&c->d_urow_blk, cap * sizeof(uint32_t)));
-        HIP_OK(c, hipMalloc((void **)&c->d_upairs, 2 * cap * sizeof(uint64_t)));
-        HIP_OK(c, hipMalloc((void **)&c->d_unew, (cap + 1) * sizeof(uint64_t)));
-        c->uws_blocks = cap;
-    }
-    if (npieces > c->uws_pieces) {
-        HIP_OK(c, hipDeviceSynchronize());
-        free_update_ws(c, 2);
-        const uint64_t cap = npieces + npieces / 8 + 16;
-        HIP_OK(c, hipMalloc((void **)&c->d_upiece, cap * sizeof(uint32_t)));
-        c->uws_pieces = cap;
-    }
-    return HUFE_OK;
-}
-
-static int ensure_sub_build_ws(hufgpu_ctx *c, uint64_t nblocks, uint64_t nchunks)
-{
-    if (!c->d_sb_unbuilt) HIP_OK(c, hipMalloc((void **)&c->d_sb_unbuilt, sizeof(unsigned long long)));
-    if (nblocks > c->sbws_blocks) {
-        HIP_OK(c, hipDeviceSynchronize());
-        free_sub_build_ws(c, 1);
-        const uint64_t cap = nblocks + nblocks / 8 + 16;
-        HIP_OK(c, hipMalloc((void **)&c->d_sb_state, cap * sizeof(uint32_t)));
-        HIP_OK(c, hipMalloc((void **)&c->d_sb_pay, cap * sizeof(uint64_t)));
-        c->sbws_blocks = cap;
-    }
-    if (nchunks > c->sbws_chunks) {
-        HIP_OK(c, hipDeviceSynchronize());
-        free_sub_build_ws(c, 2);
-        const uint64_t cap = nchunks + nchunks / 8 + 16;
-        HIP_OK(c, hipMalloc((void **)&c->d_sb_chunk_tot, cap * sizeof(uint64_t)));
-        HIP_OK(c, hipMalloc((void **)&c->d_sb_chunk_bits, cap * sizeof(uint64_t)));
-        c->sbws_chunks = cap;
-    }
     return HUFE_OK;
 }
 

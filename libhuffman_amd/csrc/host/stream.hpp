@@ -15,19 +15,10 @@ static int discover_chain(hufgpu_ctx_t *ctx, const uint8_t *st, uint64_t avail, 
     *m_out = 0; *resume_out = 0; *complete_out = false; *in_place_out = ~0ull;
     const uint64_t nwg = (scan_len + DISC_CHUNK - 1) / DISC_CHUNK;
     const uint64_t ngroups = (nwg + DISC_SCAN_GROUP - 1) / DISC_SCAN_GROUP;
-    if (nwg > ctx->disc_wgs) {
-        HIP_OK(ctx, hipStreamSynchronize(s));
-        free_disc_ws(ctx, 1);
-        const uint64_t cap = nwg + nwg / 8 + 16;
-        const uint64_t gcap = (cap + DISC_SCAN_GROUP - 1) / DISC_SCAN_GROUP + 1;
-        HIP_OK(ctx, hipMalloc((void **)&ctx->d_wg_counts, cap * sizeof(uint32_t)));
-        HIP_OK(ctx, hipMalloc((void **)&ctx->d_wg_base, (cap + 1 + 2 * gcap) * sizeof(uint64_t)));     /* local sums, then the groups' bases and totals */
-        HIP_OK(ctx, hipMalloc((void **)&ctx->d_disc_masks, cap * DISC_THREADS * sizeof(uint64_t)));
-        HIP_OK(ctx, hipMalloc((void **)&ctx->d_disc_slots, cap * DISC_SLOTS * sizeof(DiscSlot)));
-        ctx->disc_wgs = cap;
-    }
-    uint64_t *const group_base = ctx->d_wg_base + ctx->disc_wgs + 1;
-    uint64_t *const group_total = group_base + (ctx->disc_wgs + DISC_SCAN_GROUP - 1) / DISC_SCAN_GROUP + 1;
+    int rc = grow_ws(ctx, G_DISC_WGS, nwg);
+    if (rc) return rc;
+    uint64_t *const group_base = ctx->d_wg_base + ctx->disc_wgs + 1;     /* (the layout of d_wg_base: ctx.hpp, WS_DISC_WGS) */
+    uint64_t *const group_total = group_base + DISC_GCAP(ctx->disc_wgs);
     /* Round 6: ONE wait per call.  Everything that needs the number of candidates - the probes' launch, the sums, the links,
      * the walk - reads it on the device (ctx->d_walk, DISC_NCAND) and is launched as wide as the candidate arrays are:
      * surplus workgroups leave at once.  Only when there are no arrays yet (the context's first raw stream), or when the
@@ -43,17 +34,8 @@ static int discover_chain(hufgpu_ctx_t *ctx, const uint8_t *st, uint64_t avail, 
             HIP_OK(ctx, hipStreamSynchronize(s));
             const uint64_t found = ctx->h_result[0];
             if (found == 0 || found >= 0x7fffffffull) return HUFE_OK;
-            if (found > ctx->disc_cands) {
-                free_disc_ws(ctx, 2);
-                const uint64_t cap = found + found / 8 + 16;
-                HIP_OK(ctx, hipMalloc((void **)&ctx->d_cand, cap * sizeof(uint64_t)));
-                HIP_OK(ctx, hipMalloc((void **)&ctx->d_cand_end, cap * sizeof(uint64_t)));
-                HIP_OK(ctx, hipMalloc((void **)&ctx->d_chain, (cap + 1) * sizeof(uint64_t)));
-                HIP_OK(ctx, hipMalloc((void **)&ctx->d_cand_status, cap * sizeof(int32_t)));
-                HIP_OK(ctx, hipMalloc((void **)&ctx->d_nxt, cap * sizeof(uint32_t)));
-                HIP_OK(ctx, hipMalloc((void **)&ctx->d_spec_off, (cap + 1) * sizeof(uint64_t)));
-                ctx->disc_cands = cap;
-            }
+            rc = grow_ws(ctx, G_DISC_CANDS, found);
+            if (rc) return rc;
             /* (the count kernel clamped DISC_NCAND to the capacity it was given: all of them now; h_result[0] is pinned and not
              *  written again before this copy has run - the next one into it is behind it on the stream) */
             HIP_OK(ctx, hipMemcpyAsync(ctx->d_walk + DISC_NCAND, ctx->h_result, sizeof(uint64_t), hipMemcpyHostToDevice, s));
@@ -95,7 +77,6 @@ static int decode_big_blocks(hufgpu_ctx *ctx, const uint8_t *st, uint64_t avail,
 {
     const int max_tree = max_tree_of(flags);
     uint64_t pos = *pos_io, rawpos = *rawpos_io;
-    if (!ctx->d_big_offs) HIP_OK(ctx, hipMalloc((void **)&ctx->d_big_offs, (SPEC_WORDS + 2) * sizeof(uint64_t)));
     unsigned long long *d_status = (unsigned long long *)ctx->d_big_offs;
     uint64_t *d_offs = ctx->d_big_offs + SPEC_WORDS;
     while (pos < length && avail - pos >= HUF_HEADER_FIXED) {
@@ -115,11 +96,7 @@ static int decode_big_blocks(hufgpu_ctx *ctx, const uint8_t *st, uint64_t avail,
         const uint64_t sub_bytes = hufgpu_sub_index_bytes(block_len, block_len);
         /* (workspace that cannot be had - a block of many GiB needs a quarter of its size - is no
          * error: the general path takes the block) */
-        if (sub_bytes > ctx->big_sub_bytes) {
-            free_big_ws(ctx, 4);
-            if (hipMalloc(&ctx->d_big_sub, sub_bytes) != hipSuccess) { (void)hipGetLastError(); ctx->d_big_sub = NULL; break; }
-            ctx->big_sub_bytes = sub_bytes;
-        }
+        if (grow_ws(ctx, G_BIG_SUB, sub_bytes)) break;
         const HufSubIndex sub = sub_index_view(ctx->d_big_sub, block_len, block_len);
         uint64_t o1;
         if (leaf >= 0) {
@@ -135,24 +112,7 @@ static int decode_big_blocks(hufgpu_ctx *ctx, const uint8_t *st, uint64_t avail,
             if (max_bits > 9 * block_len + 64) max_bits = 9 * block_len + 64;
             const uint64_t nlanes = (max_bits + SPEC_LANE_BITS - 1) / SPEC_LANE_BITS;
             if (nlanes == 0) break;
-            if (nlanes > ctx->big_lanes) {
-                free_big_ws(ctx, 1);
-                const uint64_t cap = nlanes + nlanes / 8 + 16;
-                if (hipMalloc((void **)&ctx->d_big_entry, cap * sizeof(uint64_t)) != hipSuccess ||
-                    hipMalloc((void **)&ctx->d_big_exit, cap * sizeof(uint64_t)) != hipSuccess ||
-                    hipMalloc((void **)&ctx->d_big_pre, (cap + 1) * sizeof(uint64_t)) != hipSuccess ||
-                    hipMalloc((void **)&ctx->d_big_wgpre, (cap / DEC_THREADS + 4) * sizeof(uint64_t)) != hipSuccess ||
-                    hipMalloc((void **)&ctx->d_big_wgscratch, (cap / DEC_THREADS + 4) * sizeof(uint64_t)) != hipSuccess ||
-                    hipMalloc((void **)&ctx->d_big_first_pos, cap * sizeof(uint64_t)) != hipSuccess ||
-                    hipMalloc((void **)&ctx->d_big_first_g, cap * sizeof(uint64_t)) != hipSuccess ||
-                    hipMalloc((void **)&ctx->d_big_last_pos, cap * sizeof(uint64_t)) != hipSuccess ||
-                    hipMalloc((void **)&ctx->d_big_cnt, cap * sizeof(uint32_t)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    free_big_ws(ctx, 1);
-                    break;
-                }
-                ctx->big_lanes = cap;
-            }
+            if (grow_ws(ctx, G_BIG_LANES, nlanes)) break;
             SpecJob j;
             j.tree = st + pos + HUF_HEADER_FIXED;
             j.tree_len = (int)tl;

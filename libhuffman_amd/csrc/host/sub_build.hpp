@@ -96,8 +96,6 @@ extern "C" int hufgpu_sub_index_from_raw(hufgpu_ctx_t *ctx, const void *d_stream
     HIP_OK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = pick_stream(ctx, stream);
     const uint64_t nb = hufgpu_block_count(raw_size, blocksize);
-    rc = ensure_sub_build_ws(ctx, 0, 0);
-    if (rc) return rc;
     HIP_OK(ctx, hipMemsetAsync(ctx->d_sb_unbuilt, 0, sizeof(unsigned long long), s));
     rc = sub_build_enqueue(ctx, d_stream, stream_len, d_block_offsets, d_raw, raw_size, raw_size, blocksize, 0, nb, d_sub_index, flags, NULL, s);
     if (rc) return rc;
@@ -129,8 +127,6 @@ extern "C" int hufgpu_decode_build_sub(hufgpu_ctx_t *ctx, const void *d_stream, 
         return HUFE_OK;
     }
     hipStream_t s = pick_stream(ctx, stream);
-    rc = ensure_sub_build_ws(ctx, 0, 0);
-    if (rc) return rc;
     HIP_OK(ctx, hipMemsetAsync(ctx->d_sb_unbuilt, 0, sizeof(unsigned long long), s));
     /* the rows come from the output just written: a block that did not decode (d_status) is unbuilt */
     rc = sub_build_enqueue(ctx, d_stream, stream_len, d_block_offsets, d_out, out_cap < raw_size ? out_cap : raw_size, raw_size, blocksize, 0, nb,
@@ -164,8 +160,6 @@ extern "C" int hufgpu_build_sub_index(hufgpu_ctx_t *ctx, const void *d_stream, u
     if (rc == HUFE_MEMORY)
         set_err(ctx, "build_sub_index: no room for %llu decoded blocks of %llu bytes", (unsigned long long)slab_blocks,
                 (unsigned long long)blocksize);
-    if (rc) return rc;
-    rc = ensure_sub_build_ws(ctx, 0, 0);
     if (rc) return rc;
     HIP_OK(ctx, hipMemsetAsync(ctx->d_sb_unbuilt, 0, sizeof(unsigned long long), s));
     for (uint64_t b0 = 0; b0 < nb; b0 += slab_blocks) {

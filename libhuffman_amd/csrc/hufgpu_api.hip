@@ -1,7 +1,7 @@
 /*
  * hufgpu_api.hip - host side of the device-resident C ABI (include/huffman_gpu.h).
  *
- * Owns the per-device context (stream, workspace in HBM, pinned result words) and launches the
+ * Owns the per-device context (stream, workspaces in HBM, pinned result words) and launches the
  * kernels of hufgpu_kernels.hip.  No CPU implementation of the codec lives here: if HIP or a
  * gfx950 device is unavailable every entry point fails with HUF_ERROR_FATAL and says why.
  */
@@ -36,7 +36,7 @@ using namespace hufgpu;
 
 
 /* The parts, in the order the compiler reads them: each uses only what stands above it (no forward declarations). */
-#include "host/ctx.hpp"         /* the context: struct, errors, create / destroy, every workspace's ensure_* and free_* */
+#include "host/ctx.hpp"         /* the context: struct, errors, the table of its workspaces (host/workspace.hpp), create / destroy */
 #include "host/profile.hpp"     /* STAGE_BEGIN / STAGE_MARK, hufgpu_set_profiling, hufgpu_get_profile */
 #include "host/encode.hpp"      /* block and sub-index geometry, hufgpu_histogram, hufgpu_encode*, hufgpu_encode_small */
 #include "host/decode.hpp"      /* the one launcher of the indexed decoders, hufgpu_decode*, hufgpu_decode_result */
