@@ -103,9 +103,10 @@ class Result:
 
 
 def update(torch, codec, enc, ranges, patches, scatter_seed=None, old_sub=None, want_sub=False, relaxed=False, out_cap=None,
-           out_off=4, layout=None):
+           out_off=4, layout=None, idx_lead=2):
     """one call through the C ABI with guarded buffers; the new bytes at odd offsets of d_src when scatter_seed is given;
-    d_out lies 4 out_off bytes behind a 16-byte aligned address (the packer wants whole words of the destination)"""
+    d_out lies 4 out_off bytes behind a 16-byte aligned address (the packer wants whole words of the destination); the new
+    index lies idx_lead words behind one (1: the index kernel's stores go word by word)"""
     out_off *= 4
     lib = codec.lib
     nr = len(ranges)
@@ -129,7 +130,7 @@ def update(torch, codec, enc, ranges, patches, scatter_seed=None, old_sub=None, 
     big = torch.full((cap + 2 * GUARD_BYTES + out_off + 3,), GUARD, dtype=torch.uint8, device="cuda")
     out = big[GUARD_BYTES + out_off:GUARD_BYTES + out_off + cap]
     idx_big = torch.full((enc.nb + 1 + 4,), -0x5A5A5A5A5A5A5A5B, dtype=torch.int64, device="cuda")
-    idx = idx_big[2:2 + enc.nb + 1]
+    idx = idx_big[idx_lead:idx_lead + enc.nb + 1]
     n_lay, bs_lay = layout if layout is not None else (enc.n, enc.bs)
     sub_big = sub_new = None
     if want_sub:
@@ -153,7 +154,7 @@ def update(torch, codec, enc, ranges, patches, scatter_seed=None, old_sub=None, 
     lead = GUARD_BYTES + out_off
     assert np.all(hb[:lead] == GUARD) and np.all(hb[lead + cap:] == GUARD), "guard bytes around d_out"
     hi_ = idx_big.cpu().numpy()
-    assert np.all(hi_[:2] == -0x5A5A5A5A5A5A5A5B) and np.all(hi_[2 + enc.nb + 1:] == -0x5A5A5A5A5A5A5A5B), "guard words around the index"
+    assert np.all(hi_[:idx_lead] == -0x5A5A5A5A5A5A5A5B) and np.all(hi_[idx_lead + enc.nb + 1:] == -0x5A5A5A5A5A5A5A5B), "guard words around the index"
     if sub_big is not None:
         hs = sub_big.cpu().numpy()
         assert np.all(hs[:2] == 0x7B7B7B7B7B7B7B7B) and np.all(hs[-2:] == 0x7B7B7B7B7B7B7B7B), "guard words around the sub-index"
@@ -162,7 +163,7 @@ def update(torch, codec, enc, ranges, patches, scatter_seed=None, old_sub=None, 
     r.stream = r.out_all[:r.length]
     r.d_stream = out[:r.length]
     r.d_index = idx
-    r.index = hi_[2:2 + enc.nb + 1].astype(np.uint64)
+    r.index = hi_[idx_lead:idx_lead + enc.nb + 1].astype(np.uint64)
     r.sub = sub_new
     r.cap = cap
     if rc != HUFE_OK:
