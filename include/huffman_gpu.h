@@ -356,6 +356,42 @@ int hufgpu_find_bytes(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_l
                       uint32_t flags, void *stream);
 
 /*
+ * FIND PATTERN: grep for one string.  Where hufgpu_find_bytes() reports single bytes of a set, this call reports where a
+ * PATTERN of 1 to HUFGPU_FIND_PATTERN_MAX bytes starts in the original data - the lines of a compressed log that hold
+ * "ERROR" or a request id - again straight from stream, block index and sub-index, decoding every block once, only
+ * enqueueing on `stream` and never waiting.  Besides the match mask the context keeps at most 126 bytes of every tile of
+ * 2 048 (its first and last pattern_len - 1 bytes, 6 % of the data) in a workspace that hufgpu_find_bytes() never
+ * allocates; no other decoded byte reaches device memory.  There is no CPU path.
+ *
+ * Everything is hufgpu_find_bytes()' word for word - positions, d_sub_index (the caller vouches for NOTHING), d_block_errs,
+ * d_totals, d_pos untouched from d_totals[1] on, one-symbol blocks served, batch geometry, flags, nblocks = 0, workspaces
+ * doubled only when they grow, the argument errors (worded "find_pattern: ...") - but for this:
+ *
+ *   pattern       : a HOST array of pattern_len bytes, 1 <= pattern_len <= HUFGPU_FIND_PATTERN_MAX, read before the call
+ *                   returns.  A NULL pattern, a length of 0 or one above the maximum is HUF_ERROR_INVALID_ARGUMENT before
+ *                   anything is enqueued and before the context is looked at.
+ *   a match       : a position p of the original data with data[p .. p + pattern_len) == pattern.  ALL occurrences are
+ *                   reported, overlapping ones included ("aa" in "aaaa" matches at 0, 1 and 2), in ascending order, each
+ *                   at its START; it counts for the block that holds its start: d_block_counts[b] = matches that start
+ *                   in block b, wherever they end.  Nothing matches past raw_size.
+ *   blocks that are not served: a match is reported only when EVERY block it touches is served.  A start in a served
+ *                   block whose bytes run on into a block that is not served is no match and is counted nowhere;
+ *                   d_totals[2] and d_block_errs say which seams are open.  This is the ONE place where this call's
+ *                   answer for a served block depends on its neighbour: with d_totals[2] = 0 the answer is complete,
+ *                   otherwise up to pattern_len - 1 starts in front of every block that is not served are missing
+ *                   besides that block's own.
+ *   pattern_len 1 : gives exactly what hufgpu_find_bytes() gives for the set of that one value.
+ */
+#define HUFGPU_FIND_PATTERN_MAX 64
+int hufgpu_find_pattern(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                        const uint64_t *d_block_offsets, uint64_t nblocks,
+                        const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                        const uint8_t *pattern, uint32_t pattern_len,
+                        uint64_t *d_pos, uint64_t pos_cap,
+                        uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                        uint32_t flags, void *stream);
+
+/*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from
  * another rank, or encoded here by a caller that did not keep the 7 % of side data.  hufgpu_encode_sub() writes the
  * sub-index as a by-product of packing; these three rebuild exactly that - the same entries, entry for entry

@@ -409,6 +409,41 @@ class GpuCodec:
                                              relaxed=relaxed)
         return totals, errs
 
+    def find_pattern(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
+                     sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern: bytes, max_positions: int = 0,
+                     block_counts: bool = False, relaxed: bool = False, out: torch.Tensor | None = None):
+        """The positions in the original data at which `pattern` (1 to FIND_PATTERN_MAX bytes) starts, overlapping
+        occurrences included, on torch's current stream and without a synchronisation (hufgpu_find_pattern).  Returns
+        what find_bytes returns, (positions, totals, block_errs, block_counts): a match counts for the block that holds
+        its start, and it is reported only when every block it touches is served - totals[2] and block_errs say which
+        seams are open.  Raises ValueError for an empty or over-long pattern."""
+        pattern = bytes(pattern)
+        if not 1 <= len(pattern) <= _native.FIND_PATTERN_MAX:
+            raise ValueError(f"a pattern has 1 to {_native.FIND_PATTERN_MAX} bytes, not {len(pattern)}")
+        max_positions = int(max_positions)
+        pos = torch.empty(max_positions, dtype=torch.int64, device=self.tdev) if out is None else out
+        assert pos.is_cuda and pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == max_positions and pos.is_contiguous()
+        totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
+        errs = torch.empty(nblocks, dtype=torch.int32, device=self.tdev)
+        counts = torch.empty(nblocks, dtype=torch.int64, device=self.tdev) if block_counts else None
+        err = self.lib.hufgpu_find_pattern(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
+                                           offsets.data_ptr() if nblocks else None, nblocks,
+                                           sub_index.data_ptr() if nblocks else None, raw_size, blocksize, pattern,
+                                           len(pattern), pos.data_ptr() if max_positions else None, max_positions,
+                                           counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(),
+                                           errs.data_ptr() if nblocks else None,
+                                           _native.RELAXED_TREE if relaxed else _native.STRICT_TREE, self._stream())
+        self._check(err, "Failed to enqueue the search")
+        return pos, totals, errs, counts
+
+    def count_pattern(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
+                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern: bytes, relaxed: bool = False):
+        """How often `pattern` occurs in the original data: find_pattern without positions, enqueue-only.  Returns CUDA
+        tensors (totals[4], block_errs[nblocks]) as find_pattern does."""
+        _, totals, errs, _ = self.find_pattern(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
+                                               relaxed=relaxed)
+        return totals, errs
+
     # -- overwrite: bytes [lo, hi) of the original data replaced in one indexed stream ---------------
     def update_ranges(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, ranges,
                       data: torch.Tensor, src_offsets=None, sub_index: torch.Tensor | None = None, raw_size: int = 0,

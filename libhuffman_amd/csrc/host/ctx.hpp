@@ -110,10 +110,12 @@ struct hufgpu_ctx {
     void *d_gparts;
     int cus;                                  /* compute units of the device */
 
-    /* hufgpu_find_bytes (kernels/find.hpp): a match mask per group of 32 symbols, a count per tile, the scan of the counts */
-    uint64_t fws_words, fws_tiles;
+    /* hufgpu_find_bytes and hufgpu_find_pattern (kernels/find.hpp): a match mask per group of 32 symbols, a count per
+     * tile, the scan of the counts; the pattern call's edge bytes per tile, which a find_bytes call never allocates */
+    uint64_t fws_words, fws_tiles, fws_edge_tiles;
     uint32_t *d_fbitmap, *d_ftcnt;
     TwoLevel find_scan;
+    uint8_t *d_fedges;
 
     /* the sub-index builders (kernels/sub_build.hpp): what their kernels hand to one another, per block and per chunk */
     uint64_t sbws_blocks, sbws_chunks;
@@ -246,6 +248,7 @@ static const ws_buf WS_GATHER_BLOCKS[] = {DEV(d_gcnt, 2 * n * sizeof(uint32_t)),
 static const ws_buf WS_GATHER_PARTS[] = {DEV(d_gparts, n * sizeof(GatherPart))};
 static const ws_buf WS_FIND_WORDS[] = {DEV(d_fbitmap, n * sizeof(uint32_t))};
 static const ws_buf WS_FIND_TILES[] = {DEV(d_ftcnt, n * sizeof(uint32_t))};
+static const ws_buf WS_FIND_EDGES[] = {DEV(d_fedges, n * FIND_EDGE_SLOT)};
 static const ws_buf WS_SB_BLOCKS[] = {DEV(d_sb_state, n * sizeof(uint32_t)), DEV(d_sb_pay, n * sizeof(uint64_t))};
 static const ws_buf WS_SB_CHUNKS[] = {DEV(d_sb_chunk_tot, n * sizeof(uint64_t)), DEV(d_sb_chunk_bits, n * sizeof(uint64_t))};
 static const ws_buf WS_UPD_BLOCKS[] = {
@@ -259,7 +262,7 @@ static const ws_buf WS_UPD_PIECES[] = {DEV(d_upiece, n * sizeof(uint32_t))};
  * block of many MiB and the range scratch take what they are asked for (grow_range_scratch adds its own eighth).
  * Soft groups report nothing: the caller has another way, or words the error itself. */
 enum { G_FIXED, G_ENCODE, G_CHUNK, G_DECODE, G_DISC_WGS, G_DISC_CANDS, G_BIG_LANES, G_BIG_SUB, G_BSTAGE, G_BATCH, G_RANGE,
-       G_RSCRATCH, G_GATHER_BLOCKS, G_GATHER_PARTS, G_FIND_WORDS, G_FIND_TILES, G_SB_BLOCKS, G_SB_CHUNKS, G_UPD_BLOCKS,
+       G_RSCRATCH, G_GATHER_BLOCKS, G_GATHER_PARTS, G_FIND_WORDS, G_FIND_TILES, G_FIND_EDGES, G_SB_BLOCKS, G_SB_CHUNKS, G_UPD_BLOCKS,
        G_UPD_PIECES, G_COUNT };
 #define ROWS(a) a, (int)(sizeof(a) / sizeof(a[0]))
 #define CAP(member) {offsetof(hufgpu_ctx, member), WS_NO_CAP}
@@ -283,6 +286,7 @@ static const ws_group WS[G_COUNT] = {
     {"gather parts", ROWS(WS_GATHER_PARTS), CAP(gws_parts), WS_DOUBLE, false, NO_SCAN},
     {"find words", ROWS(WS_FIND_WORDS), CAP(fws_words), WS_DOUBLE, false, NO_SCAN},
     {"find tiles", ROWS(WS_FIND_TILES), CAP(fws_tiles), WS_DOUBLE, false, SCAN_AT(find_scan)},
+    {"find edges", ROWS(WS_FIND_EDGES), CAP(fws_edge_tiles), WS_DOUBLE, false, NO_SCAN},
     {"sub-build blocks", ROWS(WS_SB_BLOCKS), CAP(sbws_blocks), WS_EIGHTH, false, NO_SCAN},
     {"sub-build chunks", ROWS(WS_SB_CHUNKS), CAP(sbws_chunks), WS_EIGHTH, false, NO_SCAN},
     {"update blocks", ROWS(WS_UPD_BLOCKS), CAP(uws_blocks), WS_EIGHTH, false, NO_SCAN},

@@ -1,6 +1,7 @@
-/* find.hpp - the kernels of hufgpu_find_bytes (include/huffman_gpu.h): where in the original data the bytes of a set
-   of byte values lie, straight from stream, block index and sub-index; no decoded byte reaches device memory and the
-   host only enqueues.  Part of hufgpu_kernels.hip (one translation unit, gfx950 only).
+/* find.hpp - the kernels of hufgpu_find_bytes and hufgpu_find_pattern (include/huffman_gpu.h): where in the original
+   data the bytes of a set of byte values lie, or where a pattern of 1 to 64 bytes starts, straight from stream, block
+   index and sub-index; no decoded byte reaches device memory (the pattern call keeps at most 126 edge bytes a tile) and
+   the host only enqueues.  Part of hufgpu_kernels.hip (one translation unit, gfx950 only).
 
    Positions are the layout's, as in gather.hpp: block b holds [b B, b B + min(B, raw_size - b B)).
 
@@ -28,7 +29,20 @@
                          b B + 32 g + bit goes to d_pos[rank] for every set bit whose rank is below pos_cap.
 
    Any failed check of any chunk raises the block's status to HUF_ERROR_READ_WRITE (atomic max; the statuses are zero
-   when the first kernel starts); nothing is decided on the host. */
+   when the first kernel starts); nothing is decided on the host.
+
+   hufgpu_find_pattern: find_pat_sub -> find_seam -> find_scan -> find_finish (-> find_emit); a set bit is a match's START.
+     find_pat_sub_kernel the second instance of find_sub_kernel's body.  A lane tests the starts s among its 32 with
+                         s + pattern_len <= the tile's symbols, reading on into its neighbours' bytes of the wave's own
+                         slice: matches that lie INSIDE one tile.  The wave also stores the tile's edges: its first and
+                         its last min(symbols, pattern_len - 1) bytes, in a slot of 2 x 64 bytes a tile.
+     find_seam_kernel    one wave a tile, a lane a start among the tile's last pattern_len - 1: the matches that leave
+                         their tile.  Byte k of a candidate comes from the tile's own tail while it lies in the tile,
+                         then from the HEAD of whichever later tile holds it (it lies within pattern_len - 1 of that
+                         tile's start), walking the layout's tile lengths across chunks and blocks.  A start is dropped
+                         when it would end behind raw_size or when any block it touches is not served (the statuses
+                         are final: find_pat_sub_kernel has ended); the rest is OR-ed into the start tile's mask words
+                         and added to its count, BEFORE the scan, which with finish and emit runs unchanged. */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -60,18 +74,70 @@ struct FindArgs {
     int32_t *errs;
 };
 
+#define FIND_PAT_MAX 64                     /* = HUFGPU_FIND_PATTERN_MAX (include/huffman_gpu.h) */
+#define FIND_EDGE_SLOT 128                  /* bytes a tile: its head at 0, its tail at 64, pattern_len - 1 <= 63 bytes each */
+#define FIND_SEAM_THREADS 256
+
+struct FindPatArgs {
+    FindArgs f;
+    uint32_t pat[FIND_PAT_MAX / 4];         /* the pattern, byte k in bits 8 (k & 3) of word k >> 2; zeros behind it */
+    uint32_t plen;
+    uint8_t *edges;                         /* [ntiles][FIND_EDGE_SLOT] */
+};
+
 __device__ __forceinline__ uint64_t find_block_len(const FindArgs &a, uint64_t b)
 {
     return dmin<uint64_t>(a.s.bsize, a.s.raw_size - b * a.s.bsize);
 }
 
-/* grid nblocks * cpb */
-__global__ __launch_bounds__(FIND_THREADS) void find_sub_kernel(FindArgs a)
+/* the starts among the lane's 32 at which the pattern lies, all of it inside the tile's tsym symbols: candidates by
+ * the first byte (the lane's own words w), each verified word by word against the wave's slice; bytes behind
+ * start + plen never reach a comparison, so what is stale behind a short tile does not either */
+__device__ __forceinline__ uint32_t find_pat_lane(const uint32_t *tile_words, const uint32_t (&w)[8], const uint32_t *s_pat, uint32_t plen,
+                                                  uint32_t tsym, uint32_t lane)
+{
+    const uint32_t first = s_pat[0] & 0xffu;
+    uint32_t cand = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) cand |= (uint32_t)(((w[j] >> (8 * i)) & 0xffu) == first) << (4 * j + i);
+    }
+    const uint32_t fit = tsym >= plen ? tsym - plen + 1u : 0u;      /* starts of the tile at which the pattern fits */
+    const uint32_t mine = fit > 32u * lane ? dmin<uint32_t>(32u, fit - 32u * lane) : 0u;
+    cand = mine == 0u ? 0u : (mine < 32u ? cand & ((1u << mine) - 1u) : cand);
+    const uint32_t nw = (plen + 3u) >> 2;
+    const uint32_t last = (plen & 3u) ? (1u << (8u * (plen & 3u))) - 1u : 0xffffffffu;
+    uint32_t m = 0;
+    while (cand != 0u) {
+        const uint32_t bit = (uint32_t)__builtin_ctz(cand);
+        cand &= cand - 1u;
+        const uint32_t s = 32u * lane + bit, sh = 8u * (s & 3u);
+        uint32_t idx = s >> 2, lo = tile_words[idx];
+        bool same = true;
+        for (uint32_t k = 0; k < nw; k++) {
+            idx = dmin<uint32_t>(idx + 1u, HUF_SUB_TILE / 4 - 1u);  /* (the slice's last word again: those bytes lie behind the pattern) */
+            const uint32_t hi = tile_words[idx];
+            const uint32_t x = __builtin_amdgcn_alignbit(hi, lo, sh);
+            if (((x ^ s_pat[k]) & (k + 1u == nw ? last : 0xffffffffu)) != 0u) {
+                same = false;
+                break;
+            }
+            lo = hi;
+        }
+        m |= (uint32_t)same << bit;
+    }
+    return m;
+}
+
+/* the body of find_sub_kernel (PAT = false: p is not looked at) and of find_pat_sub_kernel; grid nblocks * cpb */
+template <bool PAT>
+__device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatArgs *p)
 {
     typedef DsubShared<FIND_THREADS> SH;
     __shared__ SH sh;
     __shared__ __attribute__((aligned(16))) uint32_t s_tile[FIND_WAVES][HUF_SUB_TILE / 4];
-    __shared__ uint32_t s_set[8];
+    __shared__ uint32_t s_set[PAT ? FIND_PAT_MAX / 4 : 8];          /* the set, or the pattern */
     const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
     const uint64_t b = blockIdx.x / a.cpb;
     const uint32_t c = blockIdx.x % a.cpb;
@@ -79,7 +145,11 @@ __global__ __launch_bounds__(FIND_THREADS) void find_sub_kernel(FindArgs a)
     const uint64_t sym0 = (uint64_t)c * DSUB_CHUNK_SYMS;
     if (sym0 >= blen) return;                                       /* (the short last block has fewer chunks) */
     const uint64_t sym1 = dmin<uint64_t>(blen, sym0 + DSUB_CHUNK_SYMS);
-    if (threadIdx.x < 8) s_set[threadIdx.x] = a.set[threadIdx.x];
+    if constexpr (PAT) {
+        if (threadIdx.x < FIND_PAT_MAX / 4) s_set[threadIdx.x] = p->pat[threadIdx.x];
+    } else {
+        if (threadIdx.x < 8) s_set[threadIdx.x] = a.set[threadIdx.x];
+    }
     __syncthreads();
     /* ---- the header - and its length must be the layout's ---- */
     BlockHeader h;
@@ -97,17 +167,42 @@ __global__ __launch_bounds__(FIND_THREADS) void find_sub_kernel(FindArgs a)
             if (threadIdx.x == 0) atomicMax(&a.errs[b], (int32_t)HUFE_RW);
             return;
         }
-        const bool match = ((s_set[(uint32_t)leaf >> 5] >> ((uint32_t)leaf & 31u)) & 1u) != 0u;
+        bool match;
+        uint32_t plen = 1;
+        if constexpr (PAT) {
+            /* the pattern is plen copies of the leaf, or it starts nowhere in this block; as for other blocks only
+             * the starts whose match stays inside its tile are set here, find_seam_kernel has the rest */
+            plen = p->plen;
+            match = true;
+            for (uint32_t k = 0; k < plen; k++) match &= ((s_set[k >> 2] >> (8u * (k & 3u))) & 0xffu) == (uint32_t)leaf;
+        } else {
+            match = ((s_set[(uint32_t)leaf >> 5] >> ((uint32_t)leaf & 31u)) & 1u) != 0u;
+        }
         bool set = false;
         for (uint64_t g = (sym0 >> 5) + threadIdx.x; 32ull * g < sym1; g += FIND_THREADS) {
-            const uint32_t nsym = (uint32_t)dmin<uint64_t>(DSUB_SPL, blen - 32ull * g);
+            uint32_t nsym = (uint32_t)dmin<uint64_t>(DSUB_SPL, blen - 32ull * g);
             uint32_t x = load_be32(v.pay, 4ull * g, v.pay_bytes);
             if (nsym < 32u) x &= 0xffffffffu << (32u - nsym);
             set |= x != 0u;
+            if constexpr (PAT) {                                    /* the starts of this group at which the pattern fits in the tile */
+                const uint64_t tend = dmin<uint64_t>(blen, (g / 64u + 1u) * HUF_SUB_TILE), s0 = 32ull * g + plen;
+                nsym = s0 > tend ? 0u : (uint32_t)dmin<uint64_t>(DSUB_SPL, tend - s0 + 1u);
+            }
             row[g] = match ? (nsym < 32u ? (1u << nsym) - 1u : 0xffffffffu) : 0u;
         }
-        for (uint64_t t = sym0 / HUF_SUB_TILE + threadIdx.x; t * HUF_SUB_TILE < sym1; t += FIND_THREADS)
-            trow[t] = match ? (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE) : 0u;
+        for (uint64_t t = sym0 / HUF_SUB_TILE + threadIdx.x; t * HUF_SUB_TILE < sym1; t += FIND_THREADS) {
+            const uint32_t tsym = (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE);
+            trow[t] = match ? (tsym >= plen ? tsym - plen + 1u : 0u) : 0u;
+        }
+        if constexpr (PAT) {                                        /* the tiles' edges: the leaf */
+            const uint64_t t0 = sym0 / HUF_SUB_TILE, nt = (sym1 - sym0 + HUF_SUB_TILE - 1) / HUF_SUB_TILE;
+            for (uint64_t i = threadIdx.x; i < nt * FIND_EDGE_SLOT; i += FIND_THREADS) {
+                const uint64_t t = t0 + i / FIND_EDGE_SLOT;
+                const uint32_t tsym = (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE);
+                if (((uint32_t)i & 63u) < dmin<uint32_t>(tsym, plen - 1u))
+                    p->edges[(b * a.tpb + t0) * FIND_EDGE_SLOT + i] = (uint8_t)leaf;
+            }
+        }
         if (set) atomicMax(&a.errs[b], (int32_t)HUFE_RW);
         return;
     }
@@ -127,25 +222,100 @@ __global__ __launch_bounds__(FIND_THREADS) void find_sub_kernel(FindArgs a)
             good = false;
             continue;
         }
+        if constexpr (PAT) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   /* the lanes' bytes are in LDS before other lanes read them */
+            __builtin_amdgcn_wave_barrier();
+        }
         /* the lane's own 32 bytes (it wrote them itself) against the set */
         const uint4 lo4 = *reinterpret_cast<const uint4 *>(tile_words + 8u * lane);
         const uint4 hi4 = *reinterpret_cast<const uint4 *>(tile_words + 8u * lane + 4u);
         const uint32_t w[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
         uint32_t m = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const uint32_t x = (w[j] >> (8 * i)) & 0xffu;
-                m |= ((s_set[x >> 5] >> (x & 31u)) & 1u) << (4 * j + i);
+        if constexpr (PAT) {
+            const uint32_t tsym = (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE), plen = p->plen;
+            m = find_pat_lane(tile_words, w, s_set, plen, tsym, lane);              /* (0 for a lane without symbols) */
+            /* the edges: the tile's first and last min(tsym, plen - 1) bytes */
+            const uint32_t ne = dmin<uint32_t>(tsym, plen - 1u);
+            uint8_t *slot = p->edges + (b * a.tpb + t) * FIND_EDGE_SLOT;
+            const uint8_t *bytes = reinterpret_cast<const uint8_t *>(tile_words);
+            if (lane < ne) {
+                slot[lane] = bytes[lane];
+                slot[64u + lane] = bytes[tsym - ne + lane];
             }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   /* ... and read before the next tile overwrites them */
+            __builtin_amdgcn_wave_barrier();
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const uint32_t x = (w[j] >> (8 * i)) & 0xffu;
+                    m |= ((s_set[x >> 5] >> (x & 31u)) & 1u) << (4 * j + i);
+                }
+            }
+            m = nsym == 0u ? 0u : (nsym < 32u ? m & ((1u << nsym) - 1u) : m);    /* (bytes behind a short group are stale) */
         }
-        m = nsym == 0u ? 0u : (nsym < 32u ? m & ((1u << nsym) - 1u) : m);        /* (bytes behind a short group are stale) */
         if (nsym != 0u) row[t * 64u + lane] = m;
         const uint32_t cnt = wave_lane_u32(wave_incl_scan_u32((uint32_t)__popc(m)), 63);
         if (lane == 0) trow[t] = cnt;
     }
     if (!good && lane == 0) atomicMax(&a.errs[b], (int32_t)HUFE_RW);
+}
+
+__global__ __launch_bounds__(FIND_THREADS) void find_sub_kernel(FindArgs a) { find_sub_body<false>(a, nullptr); }
+__global__ __launch_bounds__(FIND_THREADS) void find_pat_sub_kernel(FindPatArgs a) { find_sub_body<true>(a.f, &a); }
+
+/* tile (b, t) of the layout: its symbols */
+__device__ __forceinline__ uint32_t find_tile_syms(uint64_t blen, uint64_t t) { return (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE); }
+
+/* a wave = one tile, a lane = one of its last plen - 1 starts (launched for plen >= 2 only) */
+__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_seam_kernel(FindPatArgs pa)
+{
+    __shared__ uint32_t s_pat[FIND_PAT_MAX / 4];
+    const FindArgs &a = pa.f;
+    if (threadIdx.x < FIND_PAT_MAX / 4) s_pat[threadIdx.x] = pa.pat[threadIdx.x];
+    __syncthreads();
+    const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
+    const uint64_t i = (uint64_t)blockIdx.x * (FIND_SEAM_THREADS / 64) + wave;
+    if (i >= a.ntiles) return;
+    const uint64_t b = i / a.tpb, t = i % a.tpb;
+    const uint64_t blen = find_block_len(a, b);
+    if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK) return;  /* (a block that is not served counts nothing) */
+    const uint32_t plen = pa.plen, tsym = find_tile_syms(blen, t);
+    const uint32_t ne = dmin<uint32_t>(tsym, plen - 1u);
+    const uint32_t s = tsym - ne + lane;                            /* the lane's start in the tile */
+    const uint64_t pos = b * a.s.bsize + t * HUF_SUB_TILE + s;
+    bool same = lane < ne && pos + plen <= a.s.raw_size;
+    if (same) {
+        const uint8_t *e = pa.edges + i * FIND_EDGE_SLOT + 64u;     /* the own tail, then the heads of the tiles behind */
+        uint64_t cb = b, ct = t, cblen = blen;
+        uint32_t off = lane, csym = ne;                             /* byte k is e[off]; csym bytes there belong to this tile */
+        for (uint32_t k = 0; k < plen; k++, off++) {
+            while (off == csym) {                                   /* on into the next tile of the layout */
+                if ((ct + 1) * HUF_SUB_TILE < cblen) {
+                    ct++;
+                } else {
+                    cb++;                                           /* (pos + plen <= raw_size: there is such a block) */
+                    ct = 0;
+                    cblen = find_block_len(a, cb);
+                    if (a.errs[cb] != HUFE_OK) {
+                        same = false;
+                        break;
+                    }
+                }
+                e = pa.edges + (cb * a.tpb + ct) * FIND_EDGE_SLOT;
+                off = 0;
+                csym = find_tile_syms(cblen, ct);
+            }
+            if (!same || e[off] != ((s_pat[k >> 2] >> (8u * (k & 3u))) & 0xffu)) {
+                same = false;
+                break;
+            }
+        }
+    }
+    if (same) atomicOr(&a.bitmap[b * a.wpb + t * 64u + (s >> 5)], 1u << (s & 31u));
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(same));
+    if (lane == 0 && cnt != 0u) a.tcnt[i] += cnt;
 }
 
 /* a workgroup = one SCAN_GROUP of tiles, as gather_scan_kernel sums the part counts */
