@@ -392,6 +392,52 @@ int hufgpu_find_pattern(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream
                         uint32_t flags, void *stream);
 
 /*
+ * FIND RECORDS: grep for lines.  Where hufgpu_find_pattern() reports where a string starts, this call reports the whole
+ * RECORDS that hold it - the lines of a compressed log that say "ERROR" - as a start and a length each, every record once
+ * however many matches it has, in exactly the form hufgpu_gather() takes: find_records -> gather is a pipeline with no
+ * device op of the caller's in between and no host wait.  The stream is walked ONCE: the match mask of
+ * hufgpu_find_pattern() and a mask of the delimiters come from the same decoded tile, and the records are made from the two
+ * masks on the device (kernels/find.hpp).  Two more masks of one bit per byte and a count per tile live in workspaces that
+ * the two other find calls never allocate; no decoded byte but the pattern call's edges reaches device memory.  There is
+ * no CPU path.
+ *
+ * Everything is hufgpu_find_pattern()'s word for word - positions, d_sub_index (the caller vouches for NOTHING),
+ * d_block_errs zeroed by the first enqueued operation, one-symbol blocks served, batch geometry, flags, nblocks = 0,
+ * workspaces doubled only when they grow, enqueue-only without a host write or a wait, the argument errors (worded
+ * "find_records: ...") - but for this:
+ *
+ *   delim_set     : a HOST array of 32 bytes in hufgpu_find_bytes()' encoding, read before the call returns.  The bytes
+ *                   whose value is in it cut the original data into records.  A record is [s, e): s = 0 or byte s - 1 is a
+ *                   delimiter; e is the first delimiter at or behind s, or raw_size.  The delimiter is not part of the
+ *                   record.  Empty records exist and never match.  The empty set is valid: the data is one record.  NULL
+ *                   is HUF_ERROR_INVALID_ARGUMENT.
+ *   pattern       : as hufgpu_find_pattern()'s, 1 to HUFGPU_FIND_PATTERN_MAX bytes.  A pattern that holds a byte of
+ *                   delim_set is HUF_ERROR_INVALID_ARGUMENT, found on the host before the context is looked at: grep cannot
+ *                   match a newline either, and so every match lies inside one record.
+ *   d_rec_pos, d_rec_len, rec_cap, max_len: the records that hold at least one match, each ONCE, ascending by start:
+ *                   d_rec_pos[i] = s and d_rec_len[i] = min(e - s, clip), clip = max_len, or 2^32 - 1 when max_len = 0.
+ *                   The first min(total, rec_cap) entries are written and nothing behind them.  Both may be NULL when
+ *                   rec_cap = 0 and both are required otherwise.  (d_rec_pos, d_rec_len, max_len) go into hufgpu_gather()
+ *                   as (d_pos, d_len, max_len) unchanged.
+ *   d_totals      : [0] matching records (exact whatever rec_cap is), [1] records written, [2] blocks not served,
+ *                   [3] WRITTEN records longer than clip.
+ *   d_block_counts: optional; the reported records that START in block b, wherever they end.
+ *   blocks that are not served: a record is reported only when its extent is KNOWN: every block that holds a byte of
+ *                   [max(s - 1, 0), min(e, raw_size - 1)] - the record, the delimiter in front of it and the one that ends
+ *                   it - is served.  Any other record is reported and counted nowhere.  With d_totals[2] = 0 the answer is
+ *                   complete; otherwise the records that touch a block with a non-zero status are missing, and nothing
+ *                   else is.  This replaces hufgpu_find_pattern()'s seam rule: a match inside a known record touches served
+ *                   blocks only.
+ */
+int hufgpu_find_records(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                        const uint64_t *d_block_offsets, uint64_t nblocks,
+                        const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                        const uint8_t delim_set[32], const uint8_t *pattern, uint32_t pattern_len,
+                        uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t rec_cap, uint32_t max_len,
+                        uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                        uint32_t flags, void *stream);
+
+/*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from
  * another rank, or encoded here by a caller that did not keep the 7 % of side data.  hufgpu_encode_sub() writes the
  * sub-index as a by-product of packing; these three rebuild exactly that - the same entries, entry for entry

@@ -444,6 +444,78 @@ class GpuCodec:
                                                relaxed=relaxed)
         return totals, errs
 
+    def find_records(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
+                     sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern: bytes, delimiters=b"\n",
+                     max_records: int = 0, max_len: int = 0, block_counts: bool = False, relaxed: bool = False, out=None):
+        """The records of the original data - the pieces between the bytes of `delimiters` (an iterable of ints or a
+        `bytes`; empty: the data is one record) - that hold `pattern` at least once, each record ONCE, on torch's current
+        stream and without a synchronisation (hufgpu_find_records): one walk of the stream, no decoded byte written.
+        Returns CUDA tensors (positions[max_records] int64 - the records' starts, ascending, the first totals[1] written -,
+        lengths[max_records] int32 - their lengths without the delimiter, cut at max_len when that is not 0 (read
+        lengths above 2^31 - 1 as unsigned) -, totals[4] = matching records, records written, blocks not served, written
+        records longer than max_len; block_errs[nblocks]; block_counts[nblocks] int64 - by the block of the record's
+        start - or None).  A record is reported only when every block from the delimiter in front of it to the one that
+        ends it is served.  (positions, lengths, max_len) are what gather() takes.  `out`: a pair of contiguous buffers
+        (int64 [max_records], int32 [max_records]); made when not given.  Raises ValueError for a pattern that is empty,
+        too long or holds a delimiter."""
+        pattern = bytes(pattern)
+        if not 1 <= len(pattern) <= _native.FIND_PATTERN_MAX:
+            raise ValueError(f"a pattern has 1 to {_native.FIND_PATTERN_MAX} bytes, not {len(pattern)}")
+        st = self.byte_set(delimiters)
+        for v in pattern:
+            if st[v >> 3] >> (v & 7) & 1:
+                raise ValueError(f"byte value {v} of the pattern is a delimiter: a match lies inside one record")
+        max_records, max_len = int(max_records), int(max_len)
+        if out is None:
+            out = (torch.empty(max_records, dtype=torch.int64, device=self.tdev),
+                   torch.empty(max_records, dtype=torch.int32, device=self.tdev))
+        pos, lens = out
+        assert pos.is_cuda and pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == max_records and pos.is_contiguous()
+        assert lens.is_cuda and lens.dtype == torch.int32 and lens.dim() == 1 and lens.numel() == max_records and lens.is_contiguous()
+        totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
+        errs = torch.empty(nblocks, dtype=torch.int32, device=self.tdev)
+        counts = torch.empty(nblocks, dtype=torch.int64, device=self.tdev) if block_counts else None
+        err = self.lib.hufgpu_find_records(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
+                                           offsets.data_ptr() if nblocks else None, nblocks,
+                                           sub_index.data_ptr() if nblocks else None, raw_size, blocksize, st, pattern,
+                                           len(pattern), pos.data_ptr() if max_records else None,
+                                           lens.data_ptr() if max_records else None, max_records, max_len,
+                                           counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(),
+                                           errs.data_ptr() if nblocks else None,
+                                           _native.RELAXED_TREE if relaxed else _native.STRICT_TREE, self._stream())
+        self._check(err, "Failed to enqueue the search")
+        return pos, lens, totals, errs, counts
+
+    def count_records(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
+                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern: bytes, delimiters=b"\n",
+                      relaxed: bool = False):
+        """How many records hold `pattern` (grep -c): find_records without positions, enqueue-only.  Returns CUDA tensors
+        (totals[4], block_errs[nblocks]) as find_records does."""
+        _, _, totals, errs, _ = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
+                                                  delimiters, relaxed=relaxed)
+        return totals, errs
+
+    def grep(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, sub_index: torch.Tensor,
+             raw_size: int, blocksize: int, pattern: bytes, max_records: int, max_len: int, delimiters=b"\n",
+             relaxed: bool = False):
+        """The first `max_len` bytes of the first `max_records` records that hold `pattern`: find_records followed by
+        gather, on torch's current stream and without a synchronisation.  Returns CUDA tensors (lines uint8 [max_records,
+        max_len], raw_lens int32 [max_records] - the bytes of row i that are the record's -, errs int32 [max_records] -
+        gather's per record -, totals[4] and block_errs[nblocks] as find_records gives them).  Rows from totals[1] on are
+        records of 0 bytes at raw_size."""
+        max_records, max_len = int(max_records), int(max_len)
+        if max_len < 1:
+            raise ValueError("grep needs max_len, the bytes of a row")
+        pos, lens, totals, block_errs, _ = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
+                                                             pattern, delimiters, max_records=max_records, max_len=max_len,
+                                                             relaxed=relaxed)
+        written = torch.arange(max_records, device=self.tdev) < totals[1]
+        pos = torch.where(written, pos, raw_size)
+        lens = torch.where(written, lens, 0)
+        lines, errs, raw_lens = self.gather(stream, stream_len, offsets, nblocks, pos, lens, sub_index=sub_index, raw_size=raw_size,
+                                            blocksize=blocksize, max_len=max_len, relaxed=relaxed)
+        return lines, raw_lens, errs, totals, block_errs
+
     # -- overwrite: bytes [lo, hi) of the original data replaced in one indexed stream ---------------
     def update_ranges(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, ranges,
                       data: torch.Tensor, src_offsets=None, sub_index: torch.Tensor | None = None, raw_size: int = 0,

@@ -1,21 +1,45 @@
-/* find.hpp - hufgpu_find_bytes and hufgpu_find_pattern: where the bytes of a set of byte values lie in the original
-   data, and where a pattern of bytes starts (include/huffman_gpu.h, kernels/find.hpp), enqueue-only.  Part of
-   hufgpu_api.hip (one translation unit). */
+/* find.hpp - hufgpu_find_bytes, hufgpu_find_pattern and hufgpu_find_records: where the bytes of a set of byte values lie
+   in the original data, where a pattern of bytes starts, and which records - the pieces between delimiters - hold the
+   pattern (include/huffman_gpu.h, kernels/find.hpp), enqueue-only.  Part of hufgpu_api.hip (one translation unit). */
 #pragma once
 
 static_assert(FIND_PAT_MAX == HUFGPU_FIND_PATTERN_MAX, "kernels/find.hpp and include/huffman_gpu.h");
 
-/* Both calls: `who` words the errors, `key` is the set (plen = 0) or the pattern of plen bytes, `key_name` its name. */
+/* what hufgpu_find_records has beyond the pattern call: d_pos / pos_cap are its d_rec_pos / rec_cap */
+struct FindRecCall {
+    const uint8_t *delim_set;
+    uint32_t *d_len;
+    uint32_t max_len;
+};
+
+/* All three calls: `who` words the errors, `key` is the set (plen = 0) or the pattern of plen bytes, `key_name` its name;
+ * rec is NULL but for the records' call. */
 static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, const uint8_t *key, uint32_t plen,
                      const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets, uint64_t nblocks,
                      const void *d_sub_index, uint64_t raw_size, uint64_t blocksize, uint64_t *d_pos, uint64_t pos_cap,
-                     uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream)
+                     uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream,
+                     const FindRecCall *rec = NULL)
 {
     if (!key || !d_totals) {
         set_err(ctx, "%s: the %s and d_totals are required", who, key_name);
         return HUFE_ARGUMENT;
     }
-    if (pos_cap > 0 && !d_pos) {
+    if (rec) {
+        if (!rec->delim_set) {
+            set_err(ctx, "%s: the delim_set is required (32 zero bytes: the data is one record)", who);
+            return HUFE_ARGUMENT;
+        }
+        for (uint32_t i = 0; i < plen; i++) {
+            if ((rec->delim_set[key[i] >> 3] >> (key[i] & 7)) & 1) {
+                set_err(ctx, "%s: byte %u of the pattern (value %u) is a delimiter: a match lies inside one record", who, i, key[i]);
+                return HUFE_ARGUMENT;
+            }
+        }
+        if (pos_cap > 0 && (!d_pos || !rec->d_len)) {
+            set_err(ctx, "%s: rec_cap %llu needs d_rec_pos and d_rec_len", who, (unsigned long long)pos_cap);
+            return HUFE_ARGUMENT;
+        }
+    } else if (pos_cap > 0 && !d_pos) {
         set_err(ctx, "%s: pos_cap %llu needs d_pos", who, (unsigned long long)pos_cap);
         return HUFE_ARGUMENT;
     }
@@ -57,10 +81,12 @@ static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, c
     hipStream_t s = pick_stream(ctx, stream);
     int rc = ensure_find_ws(ctx, nblocks * wpb, nblocks * tpb);
     if (!rc && plen > 1) rc = grow_ws(ctx, G_FIND_EDGES, nblocks * tpb);    /* (one byte has no seams: no edges) */
+    if (!rc && rec) rc = grow_ws2(ctx, G_FIND_REC_WORDS, nblocks * wpb, G_FIND_REC_TILES, nblocks * tpb);
     if (rc) return rc;
 
-    FindPatArgs pa;
-    memset(&pa, 0, sizeof(pa));
+    FindRecArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    FindPatArgs &pa = ra.p;
     FindArgs &fa = pa.f;
     fa.s = sub_stream_args(d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize, flags);
     fa.cpb = (uint32_t)cpb;
@@ -85,6 +111,38 @@ static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, c
     fa.errs = d_block_errs;
     HIP_OK(ctx, hipMemsetAsync(d_block_errs, 0, nblocks * sizeof(int32_t), s));
     HIP_OK(ctx, hipMemsetAsync(d_totals, 0, 4 * sizeof(uint64_t), s));
+    if (rec) {
+        /* one walk for both masks, the seams of the matches, then from the two masks to the records' starts and their
+         * counts by tile; scan and finish take the records of a tile as they take its matches */
+        for (int i = 0; i < 32; i++) fa.set[i >> 2] |= (uint32_t)rec->delim_set[i] << (8 * (i & 3));
+        ra.dbits = ctx->d_frdbits;
+        ra.dcnt = ctx->d_frdcnt;
+        ra.rbits = ctx->d_frrbits;
+        ra.rcnt = ctx->d_frrcnt;
+        ra.dscan = ctx->frec_scan;
+        ra.dscan.total = ctx->d_frdtotal;
+        ra.len = rec->d_len;
+        ra.clip = rec->max_len ? rec->max_len : 0xffffffffu;
+        const uint64_t per = FIND_EMIT_THREADS / 64;
+        const dim3 tiles((unsigned)((fa.ntiles + per - 1) / per)), groups((unsigned)((fa.ntiles + SCAN_GROUP - 1) / SCAN_GROUP));
+        HIP_OK(ctx, hipMemsetAsync(ra.rbits, 0, nblocks * wpb * sizeof(uint32_t), s));
+        HIP_OK(ctx, hipMemsetAsync(ra.rcnt, 0, fa.ntiles * sizeof(uint32_t), s));
+        find_rec_sub_kernel<<<dim3((unsigned)(nblocks * cpb)), dim3(FIND_THREADS), 0, s>>>(ra);
+        if (plen > 1) {
+            const uint64_t sper = FIND_SEAM_THREADS / 64;
+            find_seam_kernel<<<dim3((unsigned)((fa.ntiles + sper - 1) / sper)), dim3(FIND_SEAM_THREADS), 0, s>>>(pa);
+        }
+        find_rec_dscan_kernel<<<groups, dim3(SCAN_GROUP), 0, s>>>(ra);
+        find_rec_mark_kernel<<<tiles, dim3(FIND_EMIT_THREADS), 0, s>>>(ra);
+        FindArgs fr = fa;                                           /* scan, finish and emit: the records of a tile in the place of its matches */
+        fr.tcnt = ra.rcnt;
+        ra.p.f = fr;
+        find_scan_kernel<<<groups, dim3(SCAN_GROUP), 0, s>>>(fr);
+        find_finish_kernel<<<dim3(grid256(nblocks)), dim3(256), 0, s>>>(fr);
+        if (pos_cap > 0) find_rec_emit_kernel<<<tiles, dim3(FIND_EMIT_THREADS), 0, s>>>(ra);
+        HIP_OK(ctx, hipGetLastError());
+        return HUFE_OK;
+    }
     if (plen == 0) {
         find_sub_kernel<<<dim3((unsigned)(nblocks * cpb)), dim3(FIND_THREADS), 0, s>>>(fa);
     } else {
@@ -124,4 +182,19 @@ extern "C" int hufgpu_find_pattern(hufgpu_ctx_t *ctx, const void *d_stream, uint
     }
     return find_call(ctx, "find_pattern", "pattern", pattern, pattern_len, d_stream, stream_len, d_block_offsets, nblocks,
                      d_sub_index, raw_size, blocksize, d_pos, pos_cap, d_block_counts, d_totals, d_block_errs, flags, stream);
+}
+
+extern "C" int hufgpu_find_records(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                   uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                   const uint8_t delim_set[32], const uint8_t *pattern, uint32_t pattern_len, uint64_t *d_rec_pos,
+                                   uint32_t *d_rec_len, uint64_t rec_cap, uint32_t max_len, uint64_t *d_block_counts,
+                                   uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream)
+{
+    if (pattern && (pattern_len == 0 || pattern_len > HUFGPU_FIND_PATTERN_MAX)) {
+        set_err(ctx, "find_records: pattern_len %u is not 1 to %d", pattern_len, HUFGPU_FIND_PATTERN_MAX);
+        return HUFE_ARGUMENT;
+    }
+    const FindRecCall rec = {delim_set, d_rec_len, max_len};
+    return find_call(ctx, "find_records", "pattern", pattern, pattern_len, d_stream, stream_len, d_block_offsets, nblocks,
+                     d_sub_index, raw_size, blocksize, d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs, flags, stream, &rec);
 }

@@ -16,10 +16,12 @@
  *   overwrite of byte ranges: decode_prepare_kernel -> drange_plan / drange_mark -> upd_class -> the indexed decoders on
  *            the staged blocks -> upd_overlay -> hist_*_pairs -> upd_index -> pack_pairs, update_copy_kernel
  *   served straight from stream, block index and sub-index, tile by tile (sub_tile.hpp: the one checked tile item):
- *            drange_tiles_kernel, gather_serve_kernel, find_sub_kernel, find_pat_sub_kernel
+ *            drange_tiles_kernel, gather_serve_kernel, find_sub_kernel, find_pat_sub_kernel, find_rec_sub_kernel
  *   byte values looked for (hufgpu_find_bytes): find_sub -> find_scan -> find_finish (-> find_emit), no decoded byte stored
  *   a pattern of bytes looked for (hufgpu_find_pattern): find_pat_sub (-> find_seam: the matches that leave their tile, from
  *            the tiles' edge bytes) -> find_scan -> find_finish (-> find_emit)
+ *   the records that hold a pattern (hufgpu_find_records): find_rec_sub (match and delimiter masks of one walk) (-> find_seam)
+ *            -> find_rec_dscan -> find_rec_mark -> find_scan -> find_finish (-> find_rec_emit)
  *   append / truncate in place: decode_prepare_kernel on the one block that is opened again -> app_plan -> the indexed
  *            decoders on it -> app_join -> hist_*_pairs -> app_index -> pack_pairs -> app_commit (-> app_sub_rows)
  *

@@ -1,7 +1,8 @@
-/* find.hpp - the kernels of hufgpu_find_bytes and hufgpu_find_pattern (include/huffman_gpu.h): where in the original
-   data the bytes of a set of byte values lie, or where a pattern of 1 to 64 bytes starts, straight from stream, block
-   index and sub-index; no decoded byte reaches device memory (the pattern call keeps at most 126 edge bytes a tile) and
-   the host only enqueues.  Part of hufgpu_kernels.hip (one translation unit, gfx950 only).
+/* find.hpp - the kernels of hufgpu_find_bytes, hufgpu_find_pattern and hufgpu_find_records (include/huffman_gpu.h): where
+   in the original data the bytes of a set of byte values lie, where a pattern of 1 to 64 bytes starts, or which records
+   between delimiters hold it, straight from stream, block index and sub-index; no decoded byte reaches device memory
+   (the pattern calls keep at most 126 edge bytes a tile) and the host only enqueues.  Part of hufgpu_kernels.hip (one
+   translation unit, gfx950 only).
 
    Positions are the layout's, as in gather.hpp: block b holds [b B, b B + min(B, raw_size - b B)).
 
@@ -42,7 +43,33 @@
                          tile's start), walking the layout's tile lengths across chunks and blocks.  A start is dropped
                          when it would end behind raw_size or when any block it touches is not served (the statuses
                          are final: find_pat_sub_kernel has ended); the rest is OR-ed into the start tile's mask words
-                         and added to its count, BEFORE the scan, which with finish and emit runs unchanged. */
+                         and added to its count, BEFORE the scan, which with finish and emit runs unchanged.
+
+   hufgpu_find_records: find_rec_sub -> find_seam -> find_rec_dscan -> find_rec_mark -> find_scan -> find_finish
+   (-> find_rec_emit).  ONE walk of the stream; a record is [s, e) between two delimiters (or byte 0, or
+   raw_size) and is reported once, when it holds a match and every block from the delimiter in front of it to the one that
+   ends it is served.
+     find_rec_sub_kernel   the third instance of find_sub_kernel's body: find_pat_sub_kernel's match mask, edges and counts,
+                           and next to them a DELIMITER mask word a group - the lane's 32 bytes, in registers already,
+                           against the delimiter set in LDS - and the tile's delimiter count.
+     find_seam_kernel      unchanged, on the match mask.
+     find_rec_dscan_kernel the second two-level scan: the delimiters in front of every tile.  A tile of a block that is not
+                           served counts one delimiter that is nowhere.
+     find_rec_mark_kernel  a wave a tile: every match sets the bit of its record's start in a third mask, by atomic OR -
+                           which is what makes a record with many matches one entry.  The start is the bit behind the last
+                           delimiter in front of the match: in the lane's own word, else in the tile's words (one ballot
+                           and two shuffles a lane), else - for the matches in front of the tile's first delimiter only,
+                           so once a TILE - in the nearest tile in front that has a delimiter, found by a binary search in
+                           the scanned counts: O(log tiles) reads however far away it is, then a bit scan of that tile's
+                           64 words.  Landing on a virtual delimiter says that the record's start is unknown: the record
+                           is dropped.  The end is looked for in the same way, forward, to drop the records whose end is
+                           unknown BEFORE anything is counted.  One record of 1 GiB with a match in every tile costs two
+                           binary searches a tile, not a walk back to byte 0 a match.
+                           Whoever turns a bit from 0 to 1 counts it for the tile that holds it; find_scan_kernel and
+                           find_finish_kernel run unchanged on those counts: ranks, d_totals[0..2], and d_block_counts by
+                           the block that holds the record's START.
+     find_rec_emit_kernel  find_emit_kernel with a length: the end is the first delimiter behind the start, looked for as
+                           above; pos and min(e - s, clip) go to the record's rank, the cut ones are counted. */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -83,6 +110,20 @@ struct FindPatArgs {
     uint32_t pat[FIND_PAT_MAX / 4];         /* the pattern, byte k in bits 8 (k & 3) of word k >> 2; zeros behind it */
     uint32_t plen;
     uint8_t *edges;                         /* [ntiles][FIND_EDGE_SLOT] */
+};
+
+/* hufgpu_find_records: the pattern route with a second mask.  p.f.set is the delimiter set, p.f.pos / p.f.pos_cap are the
+ * records' starts and their cap, p.f.bitmap / p.f.tcnt hold the match starts and their counts; scan, finish and emit get a
+ * copy whose tcnt is rcnt */
+struct FindRecArgs {
+    FindPatArgs p;
+    uint32_t *dbits;                        /* [nblocks][wpb] delimiter masks, one word a group */
+    uint32_t *dcnt;                         /* [nblocks][tpb] delimiters of a tile */
+    uint32_t *rbits;                        /* [nblocks][wpb] the starts of the records to report; zero when the first kernel starts */
+    uint32_t *rcnt;                         /* [nblocks][tpb] ... and how many of them a tile holds; zero as well */
+    TwoLevel dscan;                         /* of the tiles' delimiter counts, 1 for a tile of a block that is not served */
+    uint32_t *len;
+    uint32_t clip;                          /* max_len, or 2^32 - 1 */
 };
 
 __device__ __forceinline__ uint64_t find_block_len(const FindArgs &a, uint64_t b)
@@ -130,14 +171,16 @@ __device__ __forceinline__ uint32_t find_pat_lane(const uint32_t *tile_words, co
     return m;
 }
 
-/* the body of find_sub_kernel (PAT = false: p is not looked at) and of find_pat_sub_kernel; grid nblocks * cpb */
-template <bool PAT>
-__device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatArgs *p)
+/* the body of find_sub_kernel (PAT = false: p is not looked at), of find_pat_sub_kernel and of find_rec_sub_kernel (PAT
+ * and REC: the pattern's work, and r's delimiter masks and counts next to it); grid nblocks * cpb */
+template <bool PAT, bool REC = false>
+__device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatArgs *p, const FindRecArgs *r = nullptr)
 {
+    static_assert(PAT || !REC, "the records' route is the pattern's");
     typedef DsubShared<FIND_THREADS> SH;
     __shared__ SH sh;
     __shared__ __attribute__((aligned(16))) uint32_t s_tile[FIND_WAVES][HUF_SUB_TILE / 4];
-    __shared__ uint32_t s_set[PAT ? FIND_PAT_MAX / 4 : 8];          /* the set, or the pattern */
+    __shared__ uint32_t s_set[(PAT ? FIND_PAT_MAX / 4 : 8) + (REC ? 8 : 0)];     /* the set, or the pattern (and the delimiter set behind it) */
     const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
     const uint64_t b = blockIdx.x / a.cpb;
     const uint32_t c = blockIdx.x % a.cpb;
@@ -147,6 +190,9 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
     const uint64_t sym1 = dmin<uint64_t>(blen, sym0 + DSUB_CHUNK_SYMS);
     if constexpr (PAT) {
         if (threadIdx.x < FIND_PAT_MAX / 4) s_set[threadIdx.x] = p->pat[threadIdx.x];
+        if constexpr (REC) {
+            if (threadIdx.x >= 64 && threadIdx.x < 72) s_set[FIND_PAT_MAX / 4 + threadIdx.x - 64] = a.set[threadIdx.x - 64];
+        }
     } else {
         if (threadIdx.x < 8) s_set[threadIdx.x] = a.set[threadIdx.x];
     }
@@ -178,12 +224,15 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
         } else {
             match = ((s_set[(uint32_t)leaf >> 5] >> ((uint32_t)leaf & 31u)) & 1u) != 0u;
         }
+        bool delim = false;                                         /* the leaf is a delimiter (then the pattern is not its copies) */
+        if constexpr (REC) delim = ((s_set[FIND_PAT_MAX / 4 + ((uint32_t)leaf >> 5)] >> ((uint32_t)leaf & 31u)) & 1u) != 0u;
         bool set = false;
         for (uint64_t g = (sym0 >> 5) + threadIdx.x; 32ull * g < sym1; g += FIND_THREADS) {
             uint32_t nsym = (uint32_t)dmin<uint64_t>(DSUB_SPL, blen - 32ull * g);
             uint32_t x = load_be32(v.pay, 4ull * g, v.pay_bytes);
             if (nsym < 32u) x &= 0xffffffffu << (32u - nsym);
             set |= x != 0u;
+            if constexpr (REC) r->dbits[b * a.wpb + g] = delim ? (nsym < 32u ? (1u << nsym) - 1u : 0xffffffffu) : 0u;
             if constexpr (PAT) {                                    /* the starts of this group at which the pattern fits in the tile */
                 const uint64_t tend = dmin<uint64_t>(blen, (g / 64u + 1u) * HUF_SUB_TILE), s0 = 32ull * g + plen;
                 nsym = s0 > tend ? 0u : (uint32_t)dmin<uint64_t>(DSUB_SPL, tend - s0 + 1u);
@@ -193,6 +242,7 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
         for (uint64_t t = sym0 / HUF_SUB_TILE + threadIdx.x; t * HUF_SUB_TILE < sym1; t += FIND_THREADS) {
             const uint32_t tsym = (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE);
             trow[t] = match ? (tsym >= plen ? tsym - plen + 1u : 0u) : 0u;
+            if constexpr (REC) r->dcnt[b * a.tpb + t] = delim ? tsym : 0u;
         }
         if constexpr (PAT) {                                        /* the tiles' edges: the leaf */
             const uint64_t t0 = sym0 / HUF_SUB_TILE, nt = (sym1 - sym0 + HUF_SUB_TILE - 1) / HUF_SUB_TILE;
@@ -244,6 +294,21 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   /* ... and read before the next tile overwrites them */
             __builtin_amdgcn_wave_barrier();
+            if constexpr (REC) {                                    /* the lane's own 32 bytes against the delimiter set */
+                uint32_t d = 0;
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        const uint32_t x = (w[j] >> (8 * i)) & 0xffu;
+                        d |= ((s_set[FIND_PAT_MAX / 4 + (x >> 5)] >> (x & 31u)) & 1u) << (4 * j + i);
+                    }
+                }
+                d = nsym == 0u ? 0u : (nsym < 32u ? d & ((1u << nsym) - 1u) : d);
+                if (nsym != 0u) r->dbits[b * a.wpb + t * 64u + lane] = d;
+                const uint32_t dc = wave_lane_u32(wave_incl_scan_u32((uint32_t)__popc(d)), 63);
+                if (lane == 0) r->dcnt[b * a.tpb + t] = dc;
+            }
         } else {
 #pragma unroll
             for (int j = 0; j < 8; j++) {
@@ -264,6 +329,7 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
 
 __global__ __launch_bounds__(FIND_THREADS) void find_sub_kernel(FindArgs a) { find_sub_body<false>(a, nullptr); }
 __global__ __launch_bounds__(FIND_THREADS) void find_pat_sub_kernel(FindPatArgs a) { find_sub_body<true>(a.f, &a); }
+__global__ __launch_bounds__(FIND_THREADS) void find_rec_sub_kernel(FindRecArgs a) { find_sub_body<true, true>(a.p.f, &a.p, &a); }
 
 /* tile (b, t) of the layout: its symbols */
 __device__ __forceinline__ uint32_t find_tile_syms(uint64_t blen, uint64_t t) { return (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE); }
@@ -362,6 +428,211 @@ __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_emit_kernel(FindArgs a
         a.pos[r++] = base + (uint32_t)__builtin_ctz(m);
         m &= m - 1u;
     }
+}
+
+/* ---- hufgpu_find_records: from the match mask and the delimiter mask of one walk to records -------------------------- */
+
+#define FIND_REC_OPEN (~0ull)               /* a record whose start or end lies in or behind a block that is not served */
+
+/* a workgroup = one SCAN_GROUP of tiles: the tiles' delimiter counts summed as find_scan_kernel sums the matches.  A tile
+ * of a block that is not served counts ONE delimiter that is nowhere: a look-up that lands on it learns that its record
+ * is open.  (The statuses are final: find_rec_sub_kernel has ended.) */
+__global__ __launch_bounds__(SCAN_GROUP) void find_rec_dscan_kernel(FindRecArgs ra)
+{
+    __shared__ uint64_t s_part[SCAN_GROUP / 64];
+    const FindArgs &a = ra.p.f;
+    const uint64_t i = (uint64_t)blockIdx.x * SCAN_GROUP + threadIdx.x;
+    uint64_t c = 0;
+    if (i < a.ntiles) {
+        const uint64_t b = i / a.tpb, t = i % a.tpb;
+        if (t * HUF_SUB_TILE < find_block_len(a, b)) c = a.errs[b] == HUFE_OK ? ra.dcnt[i] : 1u;
+    }
+    scan_group_publish<SCAN_GROUP>(ra.dscan, i, a.ntiles, c, s_part);
+}
+
+/* the delimiters, real and virtual, of the tiles in front of tile k; k = ntiles: of all tiles */
+__device__ __forceinline__ uint64_t find_rec_before(const FindRecArgs &ra, uint64_t k)
+{
+    return k < ra.p.f.ntiles ? two_level_prefix(ra.dscan, k) : *ra.dscan.total;
+}
+
+/* the lane's delimiter word of tile (b, t); 0 behind the block's end */
+__device__ __forceinline__ uint32_t find_rec_dword(const FindRecArgs &ra, uint64_t b, uint64_t t, uint32_t lane)
+{
+    const uint64_t g = t * 64u + lane;
+    return g * DSUB_SPL < find_block_len(ra.p.f, b) ? ra.dbits[b * ra.p.f.wpb + g] : 0u;
+}
+
+/* Called by a full wave, every lane with the same i: where the record starts that is open at the start of tile i - behind
+ * the last delimiter of the tiles in front, which a binary search in the scanned counts finds (the nearest tile j < i
+ * whose count is not 0: O(log ntiles) reads whatever lies between, then one bit scan of its 64 words); byte 0 when there
+ * is none.  The start comes back as its word of a [nblocks][wpb] mask, its bit there and its tile; false when that
+ * tile's block is not served: the start is not known. */
+__device__ __forceinline__ bool find_rec_start_before(const FindRecArgs &ra, uint64_t i, uint32_t lane, uint64_t &word, uint32_t &bit,
+                                                      uint64_t &tile)
+{
+    const FindArgs &a = ra.p.f;
+    const uint64_t c = find_rec_before(ra, i);
+    word = tile = 0;
+    bit = 1u;
+    if (c == 0) return true;
+    uint64_t lo = 0, hi = i;                                        /* the first k with before(k) >= c: before(0) = 0 < c = before(i) */
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (find_rec_before(ra, mid) >= c) hi = mid;
+        else lo = mid + 1;
+    }
+    /* tile j has a delimiter, the tiles between j and i have none (32-bit and wave-uniform: there are at most 2^31 - 1 tiles) */
+    const uint32_t j = uni32((uint32_t)lo - 1u);
+    const uint64_t b = j / (uint32_t)a.tpb, t = j % (uint32_t)a.tpb;
+    if (a.errs[b] != HUFE_OK) return false;
+    const uint32_t d = find_rec_dword(ra, b, t, lane);
+    const uint64_t nz = __ballot(d != 0u);
+    if (nz == 0) return false;                                      /* (cannot be: a served tile's count is that of its words) */
+    const int top = 63 - __builtin_clzll(nz);
+    const uint32_t w = (uint32_t)__shfl((int)d, top);
+    const uint64_t rel = t * HUF_SUB_TILE + 32u * (uint32_t)top + (32u - (uint32_t)__builtin_clz(w));     /* behind it, in block b */
+    const bool next = rel >= find_block_len(a, b);                  /* it was the block's last byte: tile j + 1 opens block b + 1 */
+    word = next ? (b + 1) * a.wpb : b * a.wpb + (rel >> 5);
+    bit = next ? 1u : 1u << ((uint32_t)rel & 31u);
+    tile = next ? (b + 1) * a.tpb : b * a.tpb + rel / HUF_SUB_TILE;
+    return true;
+}
+
+/* ... and where the record ends that is open at the end of tile i: at the first delimiter of the tiles behind, raw_size
+ * when there is none, FIND_REC_OPEN when that tile's block is not served */
+__device__ __forceinline__ uint64_t find_rec_end_behind(const FindRecArgs &ra, uint64_t i, uint32_t lane)
+{
+    const FindArgs &a = ra.p.f;
+    const uint64_t c = find_rec_before(ra, i + 1);
+    if (c == find_rec_before(ra, a.ntiles)) return a.s.raw_size;
+    uint64_t lo = i + 1, hi = a.ntiles - 1;                         /* the first j > i with before(j + 1) > c */
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (find_rec_before(ra, mid + 1) > c) hi = mid;
+        else lo = mid + 1;
+    }
+    const uint32_t j = uni32((uint32_t)lo);
+    const uint64_t b = j / (uint32_t)a.tpb, t = j % (uint32_t)a.tpb;
+    if (a.errs[b] != HUFE_OK) return FIND_REC_OPEN;
+    const uint32_t d = find_rec_dword(ra, b, t, lane);
+    const uint64_t nz = __ballot(d != 0u);
+    if (nz == 0) return FIND_REC_OPEN;
+    const int first = __builtin_ctzll(nz);
+    const uint32_t w = (uint32_t)__shfl((int)d, first);
+    return b * a.s.bsize + t * HUF_SUB_TILE + 32u * (uint32_t)first + (uint32_t)__builtin_ctz(w);
+}
+
+/* what a lane knows of the delimiters of its tile around its own word d: the position in the tile of the last one in front
+ * of the word and of the first one behind it (-1: none in the tile), and the bits of the word below its first and above
+ * its last delimiter */
+struct FindRecLane {
+    int prev, next;
+    uint32_t head, tail;
+};
+__device__ __forceinline__ FindRecLane find_rec_lane(uint32_t d, uint32_t lane)
+{
+    const uint64_t nz = __ballot(d != 0u);
+    /* the lanes below and above this one with a delimiter, in halves of 32 lanes (shifts of 32-bit words only) */
+    const uint32_t lo = (uint32_t)nz, hi = (uint32_t)(nz >> 32), l = lane & 31u;
+    const uint32_t lt = (1u << l) - 1u, gt = l == 31u ? 0u : 0xffffffffu << (l + 1u);
+    const uint32_t below_lo = lane < 32u ? lo & lt : lo, below_hi = lane < 32u ? 0u : hi & lt;
+    const uint32_t above_lo = lane < 32u ? lo & gt : 0u, above_hi = lane < 32u ? hi : hi & gt;
+    const int pl = below_hi != 0u ? 63 - __builtin_clz(below_hi) : (below_lo != 0u ? 31 - __builtin_clz(below_lo) : -1);
+    const int nl = above_lo != 0u ? __builtin_ctz(above_lo) : (above_hi != 0u ? 32 + __builtin_ctz(above_hi) : -1);
+    const uint32_t dp = (uint32_t)__shfl((int)d, pl < 0 ? 0 : pl), dn = (uint32_t)__shfl((int)d, nl < 0 ? 0 : nl);
+    FindRecLane k;
+    k.prev = pl < 0 ? -1 : 32 * pl + 31 - __builtin_clz(dp);
+    k.next = nl < 0 ? -1 : 32 * nl + __builtin_ctz(dn);
+    k.head = d != 0u ? (d & (0u - d)) - 1u : 0xffffffffu;
+    const uint32_t top = d != 0u ? 31u - (uint32_t)__builtin_clz(d) : 0u;
+    k.tail = d != 0u ? (top == 31u ? 0u : 0xffffffffu << (top + 1u)) : 0xffffffffu;
+    return k;
+}
+
+/* a wave = one tile, a lane = one word of match starts and one of delimiters.  Every match sets the bit of its record's
+ * start in rbits (atomic OR: a record with many matches is one bit, and whoever sets it counts it for the tile of the
+ * start), when the record is known: its start lies behind a
+ * delimiter of a served block or at byte 0, its end at one or at raw_size.  Start and end are looked for in the lane's
+ * word, then in the tile's (two shuffles a lane), and only for the tile's first and last record beyond it: at most two
+ * look-ups a TILE, however many matches it has and however long the record is. */
+__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_mark_kernel(FindRecArgs ra)
+{
+    const FindArgs &a = ra.p.f;
+    const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
+    const uint64_t i = (uint64_t)blockIdx.x * (FIND_EMIT_THREADS / 64) + wave;
+    if (i >= a.ntiles) return;
+    const uint64_t b = i / a.tpb, t = i % a.tpb;
+    const uint64_t blen = find_block_len(a, b);
+    if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK || a.tcnt[i] == 0u) return;
+    const uint64_t g = t * 64u + lane;
+    const uint32_t m = g * DSUB_SPL < blen ? a.bitmap[b * a.wpb + g] : 0u;
+    const uint32_t d = find_rec_dword(ra, b, t, lane);
+    const FindRecLane k = find_rec_lane(d, lane);
+    const bool head = k.prev < 0 && (m & k.head) != 0u, tail = k.next < 0 && (m & k.tail) != 0u;
+    uint64_t hw = 0;                                                /* the word and the bit of the start in front of the tile; */
+    uint32_t hbit = 0;                                              /* no bit: that start is not known */
+    uint64_t htile = 0;
+    bool tail_open = false;
+    if (__ballot(head) != 0 && !find_rec_start_before(ra, i, lane, hw, hbit, htile)) hbit = 0u;
+    if (__ballot(tail) != 0) tail_open = find_rec_end_behind(ra, i, lane) == FIND_REC_OPEN;
+    uint32_t *row = ra.rbits + b * a.wpb + t * 64u;
+    uint32_t mm = m, last = ~0u, fresh = 0;                         /* last: the start set last, in the tile; 2048 = in front of it */
+    while (mm != 0u) {
+        const uint32_t bit = (uint32_t)__builtin_ctz(mm);
+        mm &= mm - 1u;
+        const uint32_t dl = d & ((1u << bit) - 1u);                 /* (the bit itself is no delimiter: the pattern holds none) */
+        const uint32_t s = dl != 0u ? 32u * lane + 32u - (uint32_t)__builtin_clz(dl) : (k.prev >= 0 ? (uint32_t)k.prev + 1u : HUF_SUB_TILE);
+        if ((d >> bit) == 0u && k.next < 0 && tail_open) continue;
+        if (s == last || (s == HUF_SUB_TILE && hbit == 0u)) continue;
+        last = s;
+        if (s == HUF_SUB_TILE) {
+            if ((atomicOr(&ra.rbits[hw], hbit) & hbit) == 0u) atomicAdd(&ra.rcnt[htile], 1u);
+        } else {
+            fresh += (atomicOr(&row[s >> 5], 1u << (s & 31u)) & (1u << (s & 31u))) == 0u;
+        }
+    }
+    const uint32_t cnt = wave_lane_u32(wave_incl_scan_u32(fresh), 63);
+    if (lane == 0 && cnt != 0u) atomicAdd(&ra.rcnt[i], cnt);
+}
+
+/* a wave = one tile, as find_emit_kernel: a set bit of rbits is a record's start s; its end is the first delimiter behind
+ * it, looked for as find_rec_mark_kernel does (one look-up a tile at most: for its last record).  pos = s and
+ * len = min(e - s, clip) go to the record's rank, the records cut by clip are counted into totals[3]. */
+__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_emit_kernel(FindRecArgs ra)
+{
+    const FindArgs &a = ra.p.f;
+    const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
+    const uint64_t i = (uint64_t)blockIdx.x * (FIND_EMIT_THREADS / 64) + wave;
+    if (i >= a.ntiles) return;
+    const uint64_t b = i / a.tpb, t = i % a.tpb;
+    const uint64_t blen = find_block_len(a, b);
+    if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK || ra.rcnt[i] == 0u) return;
+    const uint64_t rank0 = two_level_prefix(a.scan, i);
+    if (rank0 >= a.pos_cap) return;
+    const uint64_t g = t * 64u + lane;
+    uint32_t r = g * DSUB_SPL < blen ? ra.rbits[b * a.wpb + g] : 0u;
+    const uint32_t d = find_rec_dword(ra, b, t, lane);
+    const FindRecLane k = find_rec_lane(d, lane);
+    uint64_t e_tail = a.s.raw_size;
+    if (__ballot(k.next < 0 && (r & k.tail) != 0u) != 0) e_tail = find_rec_end_behind(ra, i, lane);
+    uint64_t rank = rank0 + (wave_incl_scan_u32((uint32_t)__popc(r)) - (uint32_t)__popc(r));
+    const uint64_t base = b * a.s.bsize + t * HUF_SUB_TILE;
+    uint32_t cut = 0;
+    while (r != 0u && rank < a.pos_cap) {
+        const uint32_t bit = (uint32_t)__builtin_ctz(r);
+        r &= r - 1u;
+        const uint32_t du = (d >> bit) << bit;
+        const uint64_t s = base + 32u * lane + bit;
+        const uint64_t e = du != 0u ? base + 32u * lane + (uint32_t)__builtin_ctz(du) : (k.next >= 0 ? base + (uint32_t)k.next : e_tail);
+        const uint64_t n = e - s;
+        a.pos[rank] = s;
+        ra.len[rank] = n > ra.clip ? ra.clip : (uint32_t)n;
+        cut += n > ra.clip;
+        rank++;
+    }
+    const uint32_t cuts = wave_lane_u32(wave_incl_scan_u32(cut), 63);
+    if (lane == 0 && cuts != 0u) atomicAdd((unsigned long long *)&a.totals[3], (unsigned long long)cuts);
 }
 
 }  // namespace hufgpu
