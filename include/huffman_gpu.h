@@ -438,6 +438,63 @@ int hufgpu_find_records(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream
                         uint32_t flags, void *stream);
 
 /*
+ * FIND CLASSES: grep -i, a hex digit, a don't-care byte.  The two calls above look for ONE string; in these two every
+ * position of the pattern is a SET of byte values - "error" in any case is five classes of two values, a request id is
+ * "req-" and eight classes of the sixteen hex digits, a byte that may be anything is the full class - and one call, one
+ * walk of the stream, answers what took a call per spelling before (and what hufgpu_find_records() could not answer at
+ * all without reporting a line once per spelling).  The tile walk, its checks, the seams, the scans, the records and the
+ * workspaces are those of the literal calls; the class table (2 KiB) travels with the launches' own arguments, so no
+ * workspace is added and calls back to back need no care.  There is no CPU path.
+ *
+ *   classes       : a HOST array classes[pattern_len][32], read before the call returns: class k is the 32 bytes at
+ *                   classes + 32 * k, a 256-bit set in hufgpu_find_bytes()' encoding - byte value v is in class k when bit
+ *                   v & 7 of classes[32 * k + (v >> 3)] is 1.  1 <= pattern_len <= HUFGPU_FIND_PATTERN_MAX.
+ *   a match       : a position p of the original data with data[p + k] in class k for every k < pattern_len.  ALL
+ *                   occurrences are reported, overlapping ones included, in ascending order, each at its START; a match
+ *                   counts for the block that holds its start.  Nothing matches past raw_size.
+ *
+ * hufgpu_find_classes() is hufgpu_find_pattern()'s contract word for word, with `classes` in the place of `pattern` -
+ * positions, d_sub_index (the caller vouches for NOTHING), d_block_errs zeroed by the first enqueued operation, d_pos
+ * untouched from d_totals[1] on, d_totals, d_block_counts, one-symbol blocks served (they match iff their one value is in
+ * every class), the seam rule (a match is reported only when EVERY block it touches is served), batch geometry, flags,
+ * nblocks = 0, workspaces doubled only when they grow, enqueue-only without a host write or a wait - and
+ * hufgpu_find_records_classes() is hufgpu_find_records()' in the same way: delim_set, d_rec_pos / d_rec_len / rec_cap /
+ * max_len, d_totals[3], the known-extent rule.  The argument errors are worded "find_classes: ..." and
+ * "find_records_classes: ...".  Found on the host, before anything is enqueued and before the context is looked at, and
+ * HUF_ERROR_INVALID_ARGUMENT are besides the literal calls' errors:
+ *
+ *   - a NULL `classes`, a pattern_len of 0 or above the maximum;
+ *   - an EMPTY class: it matches nothing and is a caller's mistake.  The message names the position;
+ *   - for the records call, a class that holds a byte of delim_set (the message names the position and the value): grep's
+ *     `.` does not match a newline either.  The caller subtracts the delimiters from a wide class - the full class with a
+ *     non-empty delim_set is this error, with the empty delim_set it is valid - and so every match lies inside one
+ *     record, which the record kernels rely on.
+ *
+ * Two identities:
+ *   classes of one value each give exactly what hufgpu_find_pattern() / hufgpu_find_records() give for that string;
+ *   pattern_len = 1 gives exactly what hufgpu_find_bytes() gives for that set.
+ *
+ * By construction the cost of a class call depends on pattern_len alone, not on the data and not on how wide the classes
+ * are (kernels/find.hpp: one table look-up per byte and start, 32 + pattern_len - 1 a lane of 32 bytes): a first class of
+ * [a-z], which would make nearly every start a candidate of a verify-by-candidate matcher, costs what any other class
+ * pattern of that length costs.  What a class call costs next to hufgpu_find_pattern() is measured in DESIGN.md 5.16.
+ */
+int hufgpu_find_classes(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                        const uint64_t *d_block_offsets, uint64_t nblocks,
+                        const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                        const uint8_t *classes, uint32_t pattern_len,
+                        uint64_t *d_pos, uint64_t pos_cap,
+                        uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                        uint32_t flags, void *stream);
+int hufgpu_find_records_classes(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                                const uint64_t *d_block_offsets, uint64_t nblocks,
+                                const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                const uint8_t delim_set[32], const uint8_t *classes, uint32_t pattern_len,
+                                uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t rec_cap, uint32_t max_len,
+                                uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                                uint32_t flags, void *stream);
+
+/*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from
  * another rank, or encoded here by a caller that did not keep the 7 % of side data.  hufgpu_encode_sub() writes the
  * sub-index as a by-product of packing; these three rebuild exactly that - the same entries, entry for entry

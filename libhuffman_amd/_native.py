@@ -75,7 +75,8 @@ hufgpu_ctx_device hufgpu_shard_unique_id hufgpu_shard_create hufgpu_shard_destro
 hufgpu_shard_range hufgpu_shard_plan_decode hufgpu_encode_sharded hufgpu_decode_sharded hufgpu_shard_set_timeout
 hufgpu_batch_geometry hufgpu_encode_batch hufgpu_decode_batch hufgpu_decode_ranges
 hufgpu_sub_index_from_raw hufgpu_decode_build_sub hufgpu_build_sub_index hufgpu_update_ranges
-hufgpu_append hufgpu_truncate hufgpu_ranges_counters hufgpu_gather hufgpu_find_bytes hufgpu_find_pattern hufgpu_find_records""".split()
+hufgpu_append hufgpu_truncate hufgpu_ranges_counters hufgpu_gather hufgpu_find_bytes hufgpu_find_pattern hufgpu_find_records
+hufgpu_find_classes hufgpu_find_records_classes""".split()
 
 
 def so_path() -> str:
@@ -191,6 +192,10 @@ def load() -> C.CDLL:
     L.hufgpu_find_records.restype = C.c_int
     L.hufgpu_find_records.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, vp, vp, C.c_uint32, vp, vp, u64, C.c_uint32, vp, vp, vp,
                                       C.c_uint32, vp]
+    L.hufgpu_find_classes.restype = C.c_int               # hufgpu_find_pattern's, `classes` in the place of `pattern`
+    L.hufgpu_find_classes.argtypes = list(L.hufgpu_find_pattern.argtypes)
+    L.hufgpu_find_records_classes.restype = C.c_int
+    L.hufgpu_find_records_classes.argtypes = list(L.hufgpu_find_records.argtypes)
     _LIB = L
     return L
 

@@ -10,6 +10,8 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
+
 import torch
 
 from . import _native
@@ -409,27 +411,71 @@ class GpuCodec:
                                              relaxed=relaxed)
         return totals, errs
 
+    ANY = bytes(range(256))         # the full class of byte_classes: a position that may hold any byte
+
+    @staticmethod
+    def byte_classes(pattern, ignore_case: bool = False) -> np.ndarray:
+        """The classes of hufgpu_find_classes, uint8 [len(pattern)][32]: row k is the byte_set of the values that
+        position k may hold.  A `bytes` / `bytearray` gives one value a position - with `ignore_case` both cases of an
+        ASCII letter and nothing else; a `list` / `tuple` gives one class an item: an int, a `bytes` of the allowed values
+        or an iterable of ints (GpuCodec.ANY: every value; `ignore_case` adds the other case of every letter of a class).
+        Raises ValueError for a length outside 1 to FIND_PATTERN_MAX and for an empty class."""
+        if isinstance(pattern, (list, tuple)):
+            items = [[int(c)] if isinstance(c, (int, np.integer)) else list(bytes(c)) if isinstance(c, (bytes, bytearray, memoryview))
+                     else [int(v) for v in c] for c in pattern]
+        elif isinstance(pattern, str):
+            raise TypeError("a pattern is a bytes-like object or a list / tuple of classes, not a str")
+        else:
+            items = [[v] for v in bytes(pattern)]            # any bytes-like object, as the literal route takes it
+        if not 1 <= len(items) <= _native.FIND_PATTERN_MAX:
+            raise ValueError(f"a pattern has 1 to {_native.FIND_PATTERN_MAX} positions, not {len(items)}")
+        out = np.zeros((len(items), 32), np.uint8)
+        for k, values in enumerate(items):
+            if ignore_case:
+                values = values + [v ^ 0x20 for v in values if 0x41 <= (v & ~0x20) <= 0x5a and v < 128]
+            if not values:
+                raise ValueError(f"class {k} of the pattern is empty: it matches nothing")
+            out[k] = np.frombuffer(GpuCodec.byte_set(values), np.uint8)
+        return out
+
+    @staticmethod
+    def _classes(pattern, ignore_case):
+        """None for the literal route - a bytes-like pattern as it is -, else the classes of the class route"""
+        if isinstance(pattern, (list, tuple)) or ignore_case:
+            return GpuCodec.byte_classes(pattern, ignore_case)
+        return None
+
     def find_pattern(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
-                     sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern: bytes, max_positions: int = 0,
-                     block_counts: bool = False, relaxed: bool = False, out: torch.Tensor | None = None):
+                     sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, max_positions: int = 0,
+                     block_counts: bool = False, relaxed: bool = False, out: torch.Tensor | None = None,
+                     ignore_case: bool = False):
         """The positions in the original data at which `pattern` (1 to FIND_PATTERN_MAX bytes) starts, overlapping
         occurrences included, on torch's current stream and without a synchronisation (hufgpu_find_pattern).  Returns
         what find_bytes returns, (positions, totals, block_errs, block_counts): a match counts for the block that holds
         its start, and it is reported only when every block it touches is served - totals[2] and block_errs say which
-        seams are open.  Raises ValueError for an empty or over-long pattern."""
-        pattern = bytes(pattern)
-        if not 1 <= len(pattern) <= _native.FIND_PATTERN_MAX:
-            raise ValueError(f"a pattern has 1 to {_native.FIND_PATTERN_MAX} bytes, not {len(pattern)}")
+        seams are open.  Raises ValueError for an empty or over-long pattern.
+        A `list` / `tuple` pattern is one of CLASSES, a set of byte values a position as byte_classes takes them, and
+        `ignore_case` makes classes of a literal's letters (hufgpu_find_classes): a match is a start p with data[p + k] in
+        class k for every k.  A bytes-like pattern without `ignore_case` makes the literal call."""
+        classes = self._classes(pattern, ignore_case)       # (byte_classes raises for a class pattern of a wrong length)
+        if classes is None:
+            pattern = bytes(pattern)
+            plen = len(pattern)
+            if not 1 <= plen <= _native.FIND_PATTERN_MAX:
+                raise ValueError(f"a pattern has 1 to {_native.FIND_PATTERN_MAX} bytes, not {plen}")
+        else:
+            pattern, plen = classes.tobytes(), len(classes)
         max_positions = int(max_positions)
         pos = torch.empty(max_positions, dtype=torch.int64, device=self.tdev) if out is None else out
         assert pos.is_cuda and pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == max_positions and pos.is_contiguous()
         totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
         errs = torch.empty(nblocks, dtype=torch.int32, device=self.tdev)
         counts = torch.empty(nblocks, dtype=torch.int64, device=self.tdev) if block_counts else None
-        err = self.lib.hufgpu_find_pattern(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
+        call = self.lib.hufgpu_find_pattern if classes is None else self.lib.hufgpu_find_classes
+        err = call(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
                                            offsets.data_ptr() if nblocks else None, nblocks,
                                            sub_index.data_ptr() if nblocks else None, raw_size, blocksize, pattern,
-                                           len(pattern), pos.data_ptr() if max_positions else None, max_positions,
+                                           plen, pos.data_ptr() if max_positions else None, max_positions,
                                            counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(),
                                            errs.data_ptr() if nblocks else None,
                                            _native.RELAXED_TREE if relaxed else _native.STRICT_TREE, self._stream())
@@ -437,16 +483,18 @@ class GpuCodec:
         return pos, totals, errs, counts
 
     def count_pattern(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
-                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern: bytes, relaxed: bool = False):
+                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, relaxed: bool = False,
+                      ignore_case: bool = False):
         """How often `pattern` occurs in the original data: find_pattern without positions, enqueue-only.  Returns CUDA
         tensors (totals[4], block_errs[nblocks]) as find_pattern does."""
         _, totals, errs, _ = self.find_pattern(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
-                                               relaxed=relaxed)
+                                               relaxed=relaxed, ignore_case=ignore_case)
         return totals, errs
 
     def find_records(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
-                     sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern: bytes, delimiters=b"\n",
-                     max_records: int = 0, max_len: int = 0, block_counts: bool = False, relaxed: bool = False, out=None):
+                     sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, delimiters=b"\n",
+                     max_records: int = 0, max_len: int = 0, block_counts: bool = False, relaxed: bool = False, out=None,
+                     ignore_case: bool = False):
         """The records of the original data - the pieces between the bytes of `delimiters` (an iterable of ints or a
         `bytes`; empty: the data is one record) - that hold `pattern` at least once, each record ONCE, on torch's current
         stream and without a synchronisation (hufgpu_find_records): one walk of the stream, no decoded byte written.
@@ -457,14 +505,27 @@ class GpuCodec:
         start - or None).  A record is reported only when every block from the delimiter in front of it to the one that
         ends it is served.  (positions, lengths, max_len) are what gather() takes.  `out`: a pair of contiguous buffers
         (int64 [max_records], int32 [max_records]); made when not given.  Raises ValueError for a pattern that is empty,
-        too long or holds a delimiter."""
-        pattern = bytes(pattern)
-        if not 1 <= len(pattern) <= _native.FIND_PATTERN_MAX:
-            raise ValueError(f"a pattern has 1 to {_native.FIND_PATTERN_MAX} bytes, not {len(pattern)}")
+        too long or holds a delimiter.
+        A `list` / `tuple` pattern is one of classes and `ignore_case` makes classes of a literal's letters, as for
+        find_pattern (hufgpu_find_records_classes); a class that holds a delimiter is a ValueError that names its position:
+        subtract the delimiters from a wide class."""
+        classes = self._classes(pattern, ignore_case)
         st = self.byte_set(delimiters)
-        for v in pattern:
-            if st[v >> 3] >> (v & 7) & 1:
-                raise ValueError(f"byte value {v} of the pattern is a delimiter: a match lies inside one record")
+        if classes is None:
+            pattern = bytes(pattern)
+            plen = len(pattern)
+            if not 1 <= plen <= _native.FIND_PATTERN_MAX:
+                raise ValueError(f"a pattern has 1 to {_native.FIND_PATTERN_MAX} bytes, not {plen}")
+            for v in pattern:
+                if st[v >> 3] >> (v & 7) & 1:
+                    raise ValueError(f"byte value {v} of the pattern is a delimiter: a match lies inside one record")
+        else:
+            both = classes & np.frombuffer(st, np.uint8)
+            if both.any():
+                k = int(np.flatnonzero(both.any(axis=1))[0])
+                v = int(np.flatnonzero(np.unpackbits(both[k], bitorder="little"))[0])
+                raise ValueError(f"class {k} of the pattern holds a delimiter (value {v}): a match lies inside one record")
+            pattern, plen = classes.tobytes(), len(classes)
         max_records, max_len = int(max_records), int(max_len)
         if out is None:
             out = (torch.empty(max_records, dtype=torch.int64, device=self.tdev),
@@ -475,10 +536,11 @@ class GpuCodec:
         totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
         errs = torch.empty(nblocks, dtype=torch.int32, device=self.tdev)
         counts = torch.empty(nblocks, dtype=torch.int64, device=self.tdev) if block_counts else None
-        err = self.lib.hufgpu_find_records(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
+        call = self.lib.hufgpu_find_records if classes is None else self.lib.hufgpu_find_records_classes
+        err = call(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
                                            offsets.data_ptr() if nblocks else None, nblocks,
                                            sub_index.data_ptr() if nblocks else None, raw_size, blocksize, st, pattern,
-                                           len(pattern), pos.data_ptr() if max_records else None,
+                                           plen, pos.data_ptr() if max_records else None,
                                            lens.data_ptr() if max_records else None, max_records, max_len,
                                            counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(),
                                            errs.data_ptr() if nblocks else None,
@@ -487,17 +549,17 @@ class GpuCodec:
         return pos, lens, totals, errs, counts
 
     def count_records(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
-                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern: bytes, delimiters=b"\n",
-                      relaxed: bool = False):
+                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, delimiters=b"\n",
+                      relaxed: bool = False, ignore_case: bool = False):
         """How many records hold `pattern` (grep -c): find_records without positions, enqueue-only.  Returns CUDA tensors
         (totals[4], block_errs[nblocks]) as find_records does."""
         _, _, totals, errs, _ = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
-                                                  delimiters, relaxed=relaxed)
+                                                  delimiters, relaxed=relaxed, ignore_case=ignore_case)
         return totals, errs
 
     def grep(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, sub_index: torch.Tensor,
-             raw_size: int, blocksize: int, pattern: bytes, max_records: int, max_len: int, delimiters=b"\n",
-             relaxed: bool = False):
+             raw_size: int, blocksize: int, pattern, max_records: int, max_len: int, delimiters=b"\n",
+             relaxed: bool = False, ignore_case: bool = False):
         """The first `max_len` bytes of the first `max_records` records that hold `pattern`: find_records followed by
         gather, on torch's current stream and without a synchronisation.  Returns CUDA tensors (lines uint8 [max_records,
         max_len], raw_lens int32 [max_records] - the bytes of row i that are the record's -, errs int32 [max_records] -
@@ -508,7 +570,7 @@ class GpuCodec:
             raise ValueError("grep needs max_len, the bytes of a row")
         pos, lens, totals, block_errs, _ = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
                                                              pattern, delimiters, max_records=max_records, max_len=max_len,
-                                                             relaxed=relaxed)
+                                                             relaxed=relaxed, ignore_case=ignore_case)
         written = torch.arange(max_records, device=self.tdev) < totals[1]
         pos = torch.where(written, pos, raw_size)
         lens = torch.where(written, lens, 0)

@@ -1,6 +1,7 @@
 /* find.hpp - hufgpu_find_bytes, hufgpu_find_pattern and hufgpu_find_records: where the bytes of a set of byte values lie
    in the original data, where a pattern of bytes starts, and which records - the pieces between delimiters - hold the
-   pattern (include/huffman_gpu.h, kernels/find.hpp), enqueue-only.  Part of hufgpu_api.hip (one translation unit). */
+   pattern; hufgpu_find_classes and hufgpu_find_records_classes: the same for a pattern whose every position is a set of
+   byte values (include/huffman_gpu.h, kernels/find.hpp), enqueue-only.  Part of hufgpu_api.hip (one translation unit). */
 #pragma once
 
 static_assert(FIND_PAT_MAX == HUFGPU_FIND_PATTERN_MAX, "kernels/find.hpp and include/huffman_gpu.h");
@@ -12,13 +13,15 @@ struct FindRecCall {
     uint32_t max_len;
 };
 
-/* All three calls: `who` words the errors, `key` is the set (plen = 0) or the pattern of plen bytes, `key_name` its name;
- * rec is NULL but for the records' call. */
+/* All five calls: `who` words the errors, `key` is the set (plen = 0) or the pattern of plen bytes, `key_name` its name;
+ * rec is NULL but for the records' calls.  cls is NULL but for the class calls: then `key` is the caller's array of plen
+ * classes, which this function only checks for NULL and never reads - its wrapper has read it -, and cls is the table made
+ * from it. */
 static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, const uint8_t *key, uint32_t plen,
                      const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets, uint64_t nblocks,
                      const void *d_sub_index, uint64_t raw_size, uint64_t blocksize, uint64_t *d_pos, uint64_t pos_cap,
                      uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream,
-                     const FindRecCall *rec = NULL)
+                     const FindRecCall *rec = NULL, const FindClsTable *cls = NULL)
 {
     if (!key || !d_totals) {
         set_err(ctx, "%s: the %s and d_totals are required", who, key_name);
@@ -29,10 +32,12 @@ static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, c
             set_err(ctx, "%s: the delim_set is required (32 zero bytes: the data is one record)", who);
             return HUFE_ARGUMENT;
         }
-        for (uint32_t i = 0; i < plen; i++) {
-            if ((rec->delim_set[key[i] >> 3] >> (key[i] & 7)) & 1) {
-                set_err(ctx, "%s: byte %u of the pattern (value %u) is a delimiter: a match lies inside one record", who, i, key[i]);
-                return HUFE_ARGUMENT;
+        if (!cls) {                                                 /* (the classes' wrapper has looked at its classes) */
+            for (uint32_t i = 0; i < plen; i++) {
+                if ((rec->delim_set[key[i] >> 3] >> (key[i] & 7)) & 1) {
+                    set_err(ctx, "%s: byte %u of the pattern (value %u) is a delimiter: a match lies inside one record", who, i, key[i]);
+                    return HUFE_ARGUMENT;
+                }
             }
         }
         if (pos_cap > 0 && (!d_pos || !rec->d_len)) {
@@ -93,7 +98,9 @@ static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, c
     if (plen == 0) {
         for (int i = 0; i < 32; i++) fa.set[i >> 2] |= (uint32_t)key[i] << (8 * (i & 3));
     } else {
-        for (uint32_t i = 0; i < plen; i++) pa.pat[i >> 2] |= (uint32_t)key[i] << (8 * (i & 3));
+        if (!cls) {
+            for (uint32_t i = 0; i < plen; i++) pa.pat[i >> 2] |= (uint32_t)key[i] << (8 * (i & 3));
+        }
         pa.plen = plen;
         pa.edges = ctx->d_fedges;
     }
@@ -127,10 +134,15 @@ static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, c
         const dim3 tiles((unsigned)((fa.ntiles + per - 1) / per)), groups((unsigned)((fa.ntiles + SCAN_GROUP - 1) / SCAN_GROUP));
         HIP_OK(ctx, hipMemsetAsync(ra.rbits, 0, nblocks * wpb * sizeof(uint32_t), s));
         HIP_OK(ctx, hipMemsetAsync(ra.rcnt, 0, fa.ntiles * sizeof(uint32_t), s));
-        find_rec_sub_kernel<<<dim3((unsigned)(nblocks * cpb)), dim3(FIND_THREADS), 0, s>>>(ra);
-        if (plen > 1) {
-            const uint64_t sper = FIND_SEAM_THREADS / 64;
-            find_seam_kernel<<<dim3((unsigned)((fa.ntiles + sper - 1) / sper)), dim3(FIND_SEAM_THREADS), 0, s>>>(pa);
+        const uint64_t sper = FIND_SEAM_THREADS / 64;
+        const dim3 seams((unsigned)((fa.ntiles + sper - 1) / sper));
+        if (cls) {                                                  /* the table goes with the launches' own arguments */
+            const FindClsArgs ca = {ra, *cls};
+            find_rec_cls_sub_kernel<<<dim3((unsigned)(nblocks * cpb)), dim3(FIND_THREADS), 0, s>>>(ca);
+            if (plen > 1) find_cls_seam_kernel<<<seams, dim3(FIND_SEAM_THREADS), 0, s>>>(ca);
+        } else {
+            find_rec_sub_kernel<<<dim3((unsigned)(nblocks * cpb)), dim3(FIND_THREADS), 0, s>>>(ra);
+            if (plen > 1) find_seam_kernel<<<seams, dim3(FIND_SEAM_THREADS), 0, s>>>(pa);
         }
         find_rec_dscan_kernel<<<groups, dim3(SCAN_GROUP), 0, s>>>(ra);
         find_rec_mark_kernel<<<tiles, dim3(FIND_EMIT_THREADS), 0, s>>>(ra);
@@ -145,6 +157,11 @@ static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, c
     }
     if (plen == 0) {
         find_sub_kernel<<<dim3((unsigned)(nblocks * cpb)), dim3(FIND_THREADS), 0, s>>>(fa);
+    } else if (cls) {
+        const FindClsArgs ca = {ra, *cls};
+        const uint64_t per = FIND_SEAM_THREADS / 64;
+        find_cls_sub_kernel<<<dim3((unsigned)(nblocks * cpb)), dim3(FIND_THREADS), 0, s>>>(ca);
+        if (plen > 1) find_cls_seam_kernel<<<dim3((unsigned)((fa.ntiles + per - 1) / per)), dim3(FIND_SEAM_THREADS), 0, s>>>(ca);
     } else {
         find_pat_sub_kernel<<<dim3((unsigned)(nblocks * cpb)), dim3(FIND_THREADS), 0, s>>>(pa);
         if (plen > 1) {
@@ -197,4 +214,66 @@ extern "C" int hufgpu_find_records(hufgpu_ctx_t *ctx, const void *d_stream, uint
     const FindRecCall rec = {delim_set, d_rec_len, max_len};
     return find_call(ctx, "find_records", "pattern", pattern, pattern_len, d_stream, stream_len, d_block_offsets, nblocks,
                      d_sub_index, raw_size, blocksize, d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs, flags, stream, &rec);
+}
+
+/* The class calls' own checks - the length, no empty class, no class that holds a delimiter - and the transposed table
+ * (kernels/find.hpp: position k at bit 63 - k of m[v]).  `classes` is not NULL; a NULL delim_set is find_call's to word. */
+static int find_cls_table(hufgpu_ctx_t *ctx, const char *who, const uint8_t *classes, uint32_t plen, const uint8_t *delim_set,
+                          FindClsTable *t)
+{
+    if (plen == 0 || plen > HUFGPU_FIND_PATTERN_MAX) {
+        set_err(ctx, "%s: pattern_len %u is not 1 to %d", who, plen, HUFGPU_FIND_PATTERN_MAX);
+        return HUFE_ARGUMENT;
+    }
+    memset(t, 0, sizeof(*t));
+    for (uint32_t k = 0; k < plen; k++) {
+        const uint8_t *cl = classes + 32u * k;
+        bool any = false;
+        for (uint32_t v = 0; v < 256; v++) {
+            if (!((cl[v >> 3] >> (v & 7)) & 1)) continue;
+            if (delim_set && ((delim_set[v >> 3] >> (v & 7)) & 1)) {
+                set_err(ctx, "%s: class %u of the pattern holds a delimiter (value %u): a match lies inside one record", who, k, v);
+                return HUFE_ARGUMENT;
+            }
+            any = true;
+            t->m[v][k < 32 ? 1 : 0] |= 1u << (31u - (k & 31u));
+        }
+        if (!any) {
+            set_err(ctx, "%s: class %u of the pattern is empty: it matches nothing", who, k);
+            return HUFE_ARGUMENT;
+        }
+        t->full[k < 32 ? 1 : 0] |= 1u << (31u - (k & 31u));
+    }
+    t->first[plen <= 32 ? 1 : 0] = 1u << (31u - ((plen - 1u) & 31u));
+    return HUFE_OK;
+}
+
+extern "C" int hufgpu_find_classes(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                   uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                   const uint8_t *classes, uint32_t pattern_len, uint64_t *d_pos, uint64_t pos_cap,
+                                   uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream)
+{
+    FindClsTable t;
+    if (classes) {
+        const int rc = find_cls_table(ctx, "find_classes", classes, pattern_len, NULL, &t);
+        if (rc) return rc;
+    }
+    return find_call(ctx, "find_classes", "classes", classes, pattern_len, d_stream, stream_len, d_block_offsets, nblocks,
+                     d_sub_index, raw_size, blocksize, d_pos, pos_cap, d_block_counts, d_totals, d_block_errs, flags, stream, NULL, &t);
+}
+
+extern "C" int hufgpu_find_records_classes(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                           uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                           const uint8_t delim_set[32], const uint8_t *classes, uint32_t pattern_len,
+                                           uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t rec_cap, uint32_t max_len,
+                                           uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream)
+{
+    FindClsTable t;
+    if (classes) {
+        const int rc = find_cls_table(ctx, "find_records_classes", classes, pattern_len, delim_set, &t);
+        if (rc) return rc;
+    }
+    const FindRecCall rec = {delim_set, d_rec_len, max_len};
+    return find_call(ctx, "find_records_classes", "classes", classes, pattern_len, d_stream, stream_len, d_block_offsets, nblocks,
+                     d_sub_index, raw_size, blocksize, d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs, flags, stream, &rec, &t);
 }

@@ -1,8 +1,8 @@
-/* find.hpp - the kernels of hufgpu_find_bytes, hufgpu_find_pattern and hufgpu_find_records (include/huffman_gpu.h): where
-   in the original data the bytes of a set of byte values lie, where a pattern of 1 to 64 bytes starts, or which records
-   between delimiters hold it, straight from stream, block index and sub-index; no decoded byte reaches device memory
-   (the pattern calls keep at most 126 edge bytes a tile) and the host only enqueues.  Part of hufgpu_kernels.hip (one
-   translation unit, gfx950 only).
+/* find.hpp - the kernels of hufgpu_find_bytes, hufgpu_find_pattern, hufgpu_find_records and of the two class calls
+   (include/huffman_gpu.h): where in the original data the bytes of a set of byte values lie, where a pattern of 1 to 64
+   bytes - or of 1 to 64 sets of byte values - starts, or which records between delimiters hold it, straight from stream,
+   block index and sub-index; no decoded byte reaches device memory (the pattern calls keep at most 126 edge bytes a tile)
+   and the host only enqueues.  Part of hufgpu_kernels.hip (one translation unit, gfx950 only).
 
    Positions are the layout's, as in gather.hpp: block b holds [b B, b B + min(B, raw_size - b B)).
 
@@ -69,7 +69,17 @@
                            find_finish_kernel run unchanged on those counts: ranks, d_totals[0..2], and d_block_counts by
                            the block that holds the record's START.
      find_rec_emit_kernel  find_emit_kernel with a length: the end is the first delimiter behind the start, looked for as
-                           above; pos and min(e - s, clip) go to the record's rank, the cut ones are counted. */
+                           above; pos and min(e - s, clip) go to the record's rank, the cut ones are counted.
+
+   hufgpu_find_classes / hufgpu_find_records_classes: the two routes above with every position of the pattern a SET of
+   byte values; find_scan, find_finish, find_emit, find_rec_dscan, find_rec_mark and find_rec_emit run unchanged.
+     find_cls_sub_kernel, find_rec_cls_sub_kernel
+                           two more instances of find_sub_kernel's body: the same walk, checks, edges, delimiter mask and
+                           counts; the 2 KiB class table (FindClsTable, transposed: a 64-bit set of positions a byte value)
+                           lies in LDS in the place of the 64 pattern bytes, and the lane matcher is a Shift-And automaton
+                           over the reversed pattern (find_cls_lane): one table look-up a byte, 32 + pattern_len - 1 (+ 3)
+                           a lane, whatever the data and however wide the classes.
+     find_cls_seam_kernel  the second instance of find_seam_kernel's body: byte k against class k. */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -171,16 +181,76 @@ __device__ __forceinline__ uint32_t find_pat_lane(const uint32_t *tile_words, co
     return m;
 }
 
+/* hufgpu_find_classes / hufgpu_find_records_classes: every position k of the pattern is a SET of byte values.  The table
+ * is transposed: m[v] holds the positions that byte value v may take, position k at bit 63 - k, as two 32-bit halves
+ * (m[v][0] the low one).  `full` has the bits 63 ... 64 - plen of all positions, `first` the lowest of them - that of the
+ * pattern's LAST position, where the automaton of find_cls_lane starts.  2 KiB, carried in the kernels' arguments. */
+struct FindClsTable {
+    uint32_t first[2], full[2];
+    uint32_t m[256][2];
+};
+struct FindClsArgs {
+    FindRecArgs r;                          /* r.p.pat is not looked at; the pattern call leaves r's own members 0 */
+    FindClsTable t;
+};
+static_assert(sizeof(FindClsArgs) <= 4096, "a kernel's arguments end at 4 KiB");
+
+#define FIND_CLS_WORDS 512                  /* the table's words in LDS: m[v] at words 2 v and 2 v + 1 */
+
+/* one byte of the Shift-And automaton that runs over the REVERSED pattern, from high addresses to low ones: bit 63 - k of
+ * the state says that the bytes read so far, the last one being byte i, end with positions k ... plen - 1 of the pattern
+ * at i; bit 63 - the sign of `hi` - that the pattern STARTS at i.  Shifts by constants, 32 bits at a time. */
+__device__ __forceinline__ void find_cls_step(uint32_t &lo, uint32_t &hi, const uint32_t *s_m, uint32_t first_lo, uint32_t first_hi, uint32_t x)
+{
+    const uint2 mv = *reinterpret_cast<const uint2 *>(s_m + 2u * x);
+    hi = ((hi << 1) | (lo >> 31) | first_hi) & mv.y;
+    lo = ((lo << 1) | first_lo) & mv.x;
+}
+
+/* find_pat_lane for classes: the starts among the lane's 32 at which every byte is in its position's class, all of it
+ * inside the tile's tsym symbols.  The lane warms the automaton up on the (plen - 1 rounded up to words) bytes behind
+ * its 32 - its neighbours' bytes of the wave's slice, read from the far end - and then takes its own 32 from the last to
+ * the first, so that a match is seen AT its start and every lane writes its own word only: 32 + plen - 1 (+ 3) table
+ * look-ups a lane whatever the data and the classes are.  Bit 63 of the state depends on the plen bytes from the start on
+ * and on nothing else, and the starts with start + plen > tsym are masked: what is stale behind a short tile - or the
+ * slice's last word read again behind the tile's end - reaches no decision. */
+__device__ __forceinline__ uint32_t find_cls_lane(const uint32_t *tile_words, const uint32_t (&w)[8], const uint32_t *s_m, uint32_t first_lo,
+                                                  uint32_t first_hi, uint32_t plen, uint32_t tsym, uint32_t lane)
+{
+    uint32_t lo = 0, hi = 0;
+    for (uint32_t k = (plen + 2u) >> 2; k-- > 0u;) {                /* the words that hold the plen - 1 bytes behind the lane's */
+        const uint32_t x = tile_words[dmin<uint32_t>(8u * lane + 8u + k, HUF_SUB_TILE / 4 - 1u)];
+#pragma unroll
+        for (int i = 3; i >= 0; i--) find_cls_step(lo, hi, s_m, first_lo, first_hi, (x >> (8 * i)) & 0xffu);
+    }
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 7; j >= 0; j--) {
+#pragma unroll
+        for (int i = 3; i >= 0; i--) {
+            find_cls_step(lo, hi, s_m, first_lo, first_hi, (w[j] >> (8 * i)) & 0xffu);
+            m |= (hi >> 31) << (4 * j + i);
+        }
+    }
+    const uint32_t fit = tsym >= plen ? tsym - plen + 1u : 0u;      /* starts of the tile at which the pattern fits */
+    const uint32_t mine = fit > 32u * lane ? dmin<uint32_t>(32u, fit - 32u * lane) : 0u;
+    return mine == 0u ? 0u : (mine < 32u ? m & ((1u << mine) - 1u) : m);
+}
+
 /* the body of find_sub_kernel (PAT = false: p is not looked at), of find_pat_sub_kernel and of find_rec_sub_kernel (PAT
- * and REC: the pattern's work, and r's delimiter masks and counts next to it); grid nblocks * cpb */
-template <bool PAT, bool REC = false>
-__device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatArgs *p, const FindRecArgs *r = nullptr)
+ * and REC: the pattern's work, and r's delimiter masks and counts next to it), and with CLS of find_cls_sub_kernel and
+ * find_rec_cls_sub_kernel: the same walk, checks, edges, delimiter masks and counts with the class table ct in the place of
+ * the pattern's bytes; grid nblocks * cpb */
+template <bool PAT, bool REC = false, bool CLS = false>
+__device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatArgs *p, const FindRecArgs *r = nullptr, const FindClsTable *ct = nullptr)
 {
     static_assert(PAT || !REC, "the records' route is the pattern's");
+    static_assert(PAT || !CLS, "the classes' route is the pattern's");
+    constexpr uint32_t KEY_WORDS = CLS ? FIND_CLS_WORDS : (PAT ? FIND_PAT_MAX / 4 : 8);      /* the delimiter set lies behind them */
     typedef DsubShared<FIND_THREADS> SH;
     __shared__ SH sh;
     __shared__ __attribute__((aligned(16))) uint32_t s_tile[FIND_WAVES][HUF_SUB_TILE / 4];
-    __shared__ uint32_t s_set[(PAT ? FIND_PAT_MAX / 4 : 8) + (REC ? 8 : 0)];     /* the set, or the pattern (and the delimiter set behind it) */
+    __shared__ alignas(CLS ? 8 : 4) uint32_t s_set[KEY_WORDS + (REC ? 8 : 0)];  /* the set, the pattern or the class table (and the delimiter set behind it) */
     const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
     const uint64_t b = blockIdx.x / a.cpb;
     const uint32_t c = blockIdx.x % a.cpb;
@@ -189,9 +259,14 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
     if (sym0 >= blen) return;                                       /* (the short last block has fewer chunks) */
     const uint64_t sym1 = dmin<uint64_t>(blen, sym0 + DSUB_CHUNK_SYMS);
     if constexpr (PAT) {
-        if (threadIdx.x < FIND_PAT_MAX / 4) s_set[threadIdx.x] = p->pat[threadIdx.x];
+        if constexpr (CLS) {
+            static_assert(FIND_THREADS == FIND_CLS_WORDS, "a thread a word of the table");
+            s_set[threadIdx.x] = ct->m[threadIdx.x >> 1][threadIdx.x & 1u];
+        } else {
+            if (threadIdx.x < FIND_PAT_MAX / 4) s_set[threadIdx.x] = p->pat[threadIdx.x];
+        }
         if constexpr (REC) {
-            if (threadIdx.x >= 64 && threadIdx.x < 72) s_set[FIND_PAT_MAX / 4 + threadIdx.x - 64] = a.set[threadIdx.x - 64];
+            if (threadIdx.x >= 64 && threadIdx.x < 72) s_set[KEY_WORDS + threadIdx.x - 64] = a.set[threadIdx.x - 64];
         }
     } else {
         if (threadIdx.x < 8) s_set[threadIdx.x] = a.set[threadIdx.x];
@@ -219,13 +294,17 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
             /* the pattern is plen copies of the leaf, or it starts nowhere in this block; as for other blocks only
              * the starts whose match stays inside its tile are set here, find_seam_kernel has the rest */
             plen = p->plen;
-            match = true;
-            for (uint32_t k = 0; k < plen; k++) match &= ((s_set[k >> 2] >> (8u * (k & 3u))) & 0xffu) == (uint32_t)leaf;
+            if constexpr (CLS) {                                    /* ... the leaf is in every class, or there is no start */
+                match = (s_set[2u * (uint32_t)leaf] & ct->full[0]) == ct->full[0] && (s_set[2u * (uint32_t)leaf + 1u] & ct->full[1]) == ct->full[1];
+            } else {
+                match = true;
+                for (uint32_t k = 0; k < plen; k++) match &= ((s_set[k >> 2] >> (8u * (k & 3u))) & 0xffu) == (uint32_t)leaf;
+            }
         } else {
             match = ((s_set[(uint32_t)leaf >> 5] >> ((uint32_t)leaf & 31u)) & 1u) != 0u;
         }
         bool delim = false;                                         /* the leaf is a delimiter (then the pattern is not its copies) */
-        if constexpr (REC) delim = ((s_set[FIND_PAT_MAX / 4 + ((uint32_t)leaf >> 5)] >> ((uint32_t)leaf & 31u)) & 1u) != 0u;
+        if constexpr (REC) delim = ((s_set[KEY_WORDS + ((uint32_t)leaf >> 5)] >> ((uint32_t)leaf & 31u)) & 1u) != 0u;
         bool set = false;
         for (uint64_t g = (sym0 >> 5) + threadIdx.x; 32ull * g < sym1; g += FIND_THREADS) {
             uint32_t nsym = (uint32_t)dmin<uint64_t>(DSUB_SPL, blen - 32ull * g);
@@ -283,7 +362,8 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
         uint32_t m = 0;
         if constexpr (PAT) {
             const uint32_t tsym = (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE), plen = p->plen;
-            m = find_pat_lane(tile_words, w, s_set, plen, tsym, lane);              /* (0 for a lane without symbols) */
+            if constexpr (CLS) m = find_cls_lane(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane);
+            else m = find_pat_lane(tile_words, w, s_set, plen, tsym, lane);         /* (0 for a lane without symbols) */
             /* the edges: the tile's first and last min(tsym, plen - 1) bytes */
             const uint32_t ne = dmin<uint32_t>(tsym, plen - 1u);
             uint8_t *slot = p->edges + (b * a.tpb + t) * FIND_EDGE_SLOT;
@@ -301,7 +381,7 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
 #pragma unroll
                     for (int i = 0; i < 4; i++) {
                         const uint32_t x = (w[j] >> (8 * i)) & 0xffu;
-                        d |= ((s_set[FIND_PAT_MAX / 4 + (x >> 5)] >> (x & 31u)) & 1u) << (4 * j + i);
+                        d |= ((s_set[KEY_WORDS + (x >> 5)] >> (x & 31u)) & 1u) << (4 * j + i);
                     }
                 }
                 d = nsym == 0u ? 0u : (nsym < 32u ? d & ((1u << nsym) - 1u) : d);
@@ -330,16 +410,24 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
 __global__ __launch_bounds__(FIND_THREADS) void find_sub_kernel(FindArgs a) { find_sub_body<false>(a, nullptr); }
 __global__ __launch_bounds__(FIND_THREADS) void find_pat_sub_kernel(FindPatArgs a) { find_sub_body<true>(a.f, &a); }
 __global__ __launch_bounds__(FIND_THREADS) void find_rec_sub_kernel(FindRecArgs a) { find_sub_body<true, true>(a.p.f, &a.p, &a); }
+__global__ __launch_bounds__(FIND_THREADS) void find_cls_sub_kernel(FindClsArgs a) { find_sub_body<true, false, true>(a.r.p.f, &a.r.p, nullptr, &a.t); }
+__global__ __launch_bounds__(FIND_THREADS) void find_rec_cls_sub_kernel(FindClsArgs a) { find_sub_body<true, true, true>(a.r.p.f, &a.r.p, &a.r, &a.t); }
 
 /* tile (b, t) of the layout: its symbols */
 __device__ __forceinline__ uint32_t find_tile_syms(uint64_t blen, uint64_t t) { return (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE); }
 
-/* a wave = one tile, a lane = one of its last plen - 1 starts (launched for plen >= 2 only) */
-__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_seam_kernel(FindPatArgs pa)
+/* a wave = one tile, a lane = one of its last plen - 1 starts (launched for plen >= 2 only); CLS: byte k is tested
+ * against class k - bit 63 - k of its entry of the table c - and not against the pattern's byte k */
+template <bool CLS>
+__device__ __forceinline__ void find_seam_body(const FindPatArgs &pa, const FindClsTable *c = nullptr)
 {
-    __shared__ uint32_t s_pat[FIND_PAT_MAX / 4];
+    __shared__ uint32_t s_pat[CLS ? FIND_CLS_WORDS : FIND_PAT_MAX / 4];
     const FindArgs &a = pa.f;
-    if (threadIdx.x < FIND_PAT_MAX / 4) s_pat[threadIdx.x] = pa.pat[threadIdx.x];
+    if constexpr (CLS) {
+        for (uint32_t i = threadIdx.x; i < FIND_CLS_WORDS; i += FIND_SEAM_THREADS) s_pat[i] = c->m[i >> 1][i & 1u];
+    } else {
+        if (threadIdx.x < FIND_PAT_MAX / 4) s_pat[threadIdx.x] = pa.pat[threadIdx.x];
+    }
     __syncthreads();
     const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
     const uint64_t i = (uint64_t)blockIdx.x * (FIND_SEAM_THREADS / 64) + wave;
@@ -356,6 +444,7 @@ __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_seam_kernel(FindPatArg
         const uint8_t *e = pa.edges + i * FIND_EDGE_SLOT + 64u;     /* the own tail, then the heads of the tiles behind */
         uint64_t cb = b, ct = t, cblen = blen;
         uint32_t off = lane, csym = ne;                             /* byte k is e[off]; csym bytes there belong to this tile */
+        [[maybe_unused]] uint32_t kbit = 0x80000000u, khalf = 1u;   /* CLS: class k is bit kbit of half khalf of a table entry */
         for (uint32_t k = 0; k < plen; k++, off++) {
             while (off == csym) {                                   /* on into the next tile of the layout */
                 if ((ct + 1) * HUF_SUB_TILE < cblen) {
@@ -373,9 +462,19 @@ __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_seam_kernel(FindPatArg
                 off = 0;
                 csym = find_tile_syms(cblen, ct);
             }
-            if (!same || e[off] != ((s_pat[k >> 2] >> (8u * (k & 3u))) & 0xffu)) {
+            bool fits;
+            if constexpr (CLS) fits = same && (s_pat[2u * e[off] + khalf] & kbit) != 0u;
+            else fits = same && e[off] == ((s_pat[k >> 2] >> (8u * (k & 3u))) & 0xffu);
+            if (!fits) {
                 same = false;
                 break;
+            }
+            if constexpr (CLS) {                                    /* class k + 1: the next bit down, shifted by a constant */
+                kbit >>= 1;
+                if (kbit == 0u) {
+                    kbit = 0x80000000u;
+                    khalf = 0u;
+                }
             }
         }
     }
@@ -383,6 +482,9 @@ __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_seam_kernel(FindPatArg
     const uint32_t cnt = (uint32_t)__popcll(__ballot(same));
     if (lane == 0 && cnt != 0u) a.tcnt[i] += cnt;
 }
+
+__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_seam_kernel(FindPatArgs pa) { find_seam_body<false>(pa); }
+__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_cls_seam_kernel(FindClsArgs a) { find_seam_body<true>(a.r.p, &a.t); }
 
 /* a workgroup = one SCAN_GROUP of tiles, as gather_scan_kernel sums the part counts */
 __global__ __launch_bounds__(SCAN_GROUP) void find_scan_kernel(FindArgs a)
