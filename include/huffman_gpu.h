@@ -495,6 +495,70 @@ int hufgpu_find_records_classes(hufgpu_ctx_t *ctx, const void *d_stream, uint64_
                                 uint32_t flags, void *stream);
 
 /*
+ * FIND ANY: grep -e ERROR -e FATAL -e panic, grep -F -f words.txt, grep -E 'timeout|refused|reset'.  The two calls above
+ * look for ONE class pattern; these two look for ANY of several - ALTERNATIVES - in one walk of the stream.  With a call per
+ * alternative the positions cost a walk each and a merge of the position lists, and the records cannot be had at all
+ * without a line that holds two alternatives coming back twice.  The tile walk, its checks, the seams, the scans, the
+ * records and the workspaces are those of the class calls - an any-of call grows what a class call of the LONGEST
+ * alternative's length grows, no workspace is added -, and the table travels with the launches' own arguments.  There is no
+ * CPU path.
+ *
+ *   an alternative: what hufgpu_find_classes() calls a pattern: 1 to HUFGPU_FIND_PATTERN_MAX positions, each a set of byte
+ *                   values.  A literal is classes of one value each, `-i` classes of two.
+ *   n_alts        : how many there are, n_alts >= 1.  Their lengths sum to at most HUFGPU_FIND_PATTERN_MAX (so n_alts is
+ *                   at most that as well): the alternatives share the 64 bits of one matcher state.
+ *   alt_lens      : a HOST array of n_alts lengths, read before the call returns.
+ *   classes       : a HOST array classes[alt_lens[0] + alt_lens[1] + ...][32], read before the call returns: the classes
+ *                   of alternative 0 in hufgpu_find_classes()' encoding, then those of alternative 1, and so on.
+ *   a match       : a position p of the original data at which AT LEAST ONE alternative j lies: data[p + k] is in class k
+ *                   of j for every k < len_j, p + len_j <= raw_size, and every block that [p, p + len_j) touches is
+ *                   served.  A start is reported ONCE however many alternatives lie there ("ab" and "abc"), in ascending
+ *                   order; it counts for the block that holds p.  Each alternative has its own seam rule: when the longer
+ *                   of two reaches into a block that is not served and the shorter does not, the start is reported.
+ *   WHICH alternative lies at a reported start is NOT reported: the kernels behind the matcher see one bit a start.  A
+ *                   caller who needs it reads the bytes with hufgpu_gather() and looks.
+ *
+ * hufgpu_find_any() is hufgpu_find_pattern()'s contract word for word with this meaning of a match - d_sub_index (the
+ * caller vouches for NOTHING), d_block_errs zeroed by the first enqueued operation, d_pos untouched from d_totals[1] on,
+ * d_totals[0..3], d_block_counts, pos_cap, one-symbol blocks served (an alternative lies there iff the one value is in each
+ * of its classes), batch geometry, flags, nblocks = 0, enqueue-only without a host write or a wait - and
+ * hufgpu_find_records_any() is hufgpu_find_records()' with "holds a match" meaning "holds a match of any alternative":
+ * each record is reported once, delim_set, d_rec_pos / d_rec_len / rec_cap / max_len, d_totals[3] and the known-extent
+ * rule are the same.  The argument errors are worded "find_any: ..." and "find_records_any: ...".  Found on the host, before
+ * anything is enqueued and before the context is looked at, and HUF_ERROR_INVALID_ARGUMENT are besides the older calls'
+ * errors:
+ *
+ *   - a NULL `classes` or `alt_lens`; an n_alts of 0 or above HUFGPU_FIND_PATTERN_MAX;
+ *   - an alternative of length 0 (the message names the alternative): it would lie everywhere;
+ *   - lengths that sum to more than HUFGPU_FIND_PATTERN_MAX (the message names the total); `classes` is not read then;
+ *   - an EMPTY class (the message names the alternative and the position in it);
+ *   - for the records call, a class that holds a byte of delim_set (alternative, position and value are named): every
+ *     match lies inside one record, which the record kernels rely on.
+ *
+ * Identities: ONE alternative gives exactly what hufgpu_find_classes() / hufgpu_find_records_classes() give for it; n
+ * alternatives of one position give what hufgpu_find_bytes() gives for the union of their sets; K alternatives give the
+ * sorted union, without duplicates, of what K class calls give.
+ *
+ * The cost follows the LONGEST alternative's length as a class call's follows pattern_len, plus a few vector operations a
+ * byte for the test of the start bits; it does not depend on the data, on how wide the classes are or - but for the seam
+ * kernel's few starts a tile - on how many alternatives there are.  Measured in DESIGN.md 5.17.
+ */
+int hufgpu_find_any(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                    const uint64_t *d_block_offsets, uint64_t nblocks,
+                    const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                    const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                    uint64_t *d_pos, uint64_t pos_cap,
+                    uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                    uint32_t flags, void *stream);
+int hufgpu_find_records_any(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                            const uint64_t *d_block_offsets, uint64_t nblocks,
+                            const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                            const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                            uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t rec_cap, uint32_t max_len,
+                            uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                            uint32_t flags, void *stream);
+
+/*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from
  * another rank, or encoded here by a caller that did not keep the 7 % of side data.  hufgpu_encode_sub() writes the
  * sub-index as a by-product of packing; these three rebuild exactly that - the same entries, entry for entry

@@ -76,7 +76,7 @@ hufgpu_shard_range hufgpu_shard_plan_decode hufgpu_encode_sharded hufgpu_decode_
 hufgpu_batch_geometry hufgpu_encode_batch hufgpu_decode_batch hufgpu_decode_ranges
 hufgpu_sub_index_from_raw hufgpu_decode_build_sub hufgpu_build_sub_index hufgpu_update_ranges
 hufgpu_append hufgpu_truncate hufgpu_ranges_counters hufgpu_gather hufgpu_find_bytes hufgpu_find_pattern hufgpu_find_records
-hufgpu_find_classes hufgpu_find_records_classes""".split()
+hufgpu_find_classes hufgpu_find_records_classes hufgpu_find_any hufgpu_find_records_any""".split()
 
 
 def so_path() -> str:
@@ -196,6 +196,11 @@ def load() -> C.CDLL:
     L.hufgpu_find_classes.argtypes = list(L.hufgpu_find_pattern.argtypes)
     L.hufgpu_find_records_classes.restype = C.c_int
     L.hufgpu_find_records_classes.argtypes = list(L.hufgpu_find_records.argtypes)
+    L.hufgpu_find_any.restype = C.c_int                   # hufgpu_find_classes', (classes, alt_lens, n_alts) in the place of (classes, pattern_len)
+    L.hufgpu_find_any.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, vp, vp, C.c_uint32, vp, u64, vp, vp, vp, C.c_uint32, vp]
+    L.hufgpu_find_records_any.restype = C.c_int
+    L.hufgpu_find_records_any.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, vp, vp, vp, C.c_uint32, vp, vp, u64, C.c_uint32, vp, vp, vp,
+                                          C.c_uint32, vp]
     _LIB = L
     return L
 

@@ -438,6 +438,52 @@ class GpuCodec:
             out[k] = np.frombuffer(GpuCodec.byte_set(values), np.uint8)
         return out
 
+    class AnyOf:
+        """Several ALTERNATIVES for the `pattern` of find_pattern / count_pattern / find_records / count_records / grep
+        (grep -e A -e B, grep -F -f words, grep -E 'A|B'): a match is a start at which at least one of them lies, and
+        one call - one walk of the stream - looks for all of them (hufgpu_find_any / hufgpu_find_records_any).  Each
+        alternative is what byte_classes takes: a bytes-like literal or a list / tuple of classes.  1 to FIND_PATTERN_MAX
+        alternatives whose lengths sum to at most FIND_PATTERN_MAX (alt_classes checks that)."""
+        __slots__ = ("alternatives",)
+
+        def __init__(self, *alternatives):
+            self.alternatives = tuple(alternatives)
+
+        def __len__(self):
+            return len(self.alternatives)
+
+        def __iter__(self):
+            return iter(self.alternatives)
+
+        def __repr__(self):
+            return "AnyOf(" + ", ".join(repr(a) for a in self.alternatives) + ")"
+
+    @staticmethod
+    def alt_classes(anyof, ignore_case: bool = False):
+        """The two host arrays of hufgpu_find_any for an AnyOf: (classes uint8 [total][32] - the alternatives' byte_classes
+        one behind the other -, alt_lens uint32 [n]).  `ignore_case` applies to every alternative.  Raises ValueError for
+        no alternative or more than FIND_PATTERN_MAX, for an alternative of length 0, for lengths that sum to more than
+        FIND_PATTERN_MAX and for an empty class (the message names the alternative)."""
+        if not isinstance(anyof, GpuCodec.AnyOf):
+            raise TypeError("alt_classes takes a GpuCodec.AnyOf")
+        n = len(anyof)
+        if not 1 <= n <= _native.FIND_PATTERN_MAX:
+            raise ValueError(f"an AnyOf has 1 to {_native.FIND_PATTERN_MAX} alternatives, not {n}")
+        rows = []
+        for j, alt in enumerate(anyof):
+            if isinstance(alt, str):
+                raise TypeError("an alternative is a bytes-like object or a list / tuple of classes, not a str")
+            if len(alt) == 0:
+                raise ValueError(f"alternative {j} has length 0: it would match everywhere")
+            try:
+                rows.append(GpuCodec.byte_classes(alt, ignore_case))
+            except ValueError as e:
+                raise ValueError(f"alternative {j}: {e}") from None
+        total = sum(len(r) for r in rows)
+        if total > _native.FIND_PATTERN_MAX:
+            raise ValueError(f"the alternatives' lengths sum to {total}, above {_native.FIND_PATTERN_MAX}")
+        return np.concatenate(rows), np.array([len(r) for r in rows], np.uint32)
+
     @staticmethod
     def _classes(pattern, ignore_case):
         """None for the literal route - a bytes-like pattern as it is -, else the classes of the class route"""
@@ -456,26 +502,33 @@ class GpuCodec:
         seams are open.  Raises ValueError for an empty or over-long pattern.
         A `list` / `tuple` pattern is one of CLASSES, a set of byte values a position as byte_classes takes them, and
         `ignore_case` makes classes of a literal's letters (hufgpu_find_classes): a match is a start p with data[p + k] in
-        class k for every k.  A bytes-like pattern without `ignore_case` makes the literal call."""
-        classes = self._classes(pattern, ignore_case)       # (byte_classes raises for a class pattern of a wrong length)
-        if classes is None:
+        class k for every k.  A bytes-like pattern without `ignore_case` makes the literal call.
+        A GpuCodec.AnyOf pattern looks for SEVERAL alternatives in the one walk (hufgpu_find_any): a start at which at least
+        one of them lies is reported once; which one is not reported.  `ignore_case` applies to every alternative."""
+        alts = self.alt_classes(pattern, ignore_case) if isinstance(pattern, GpuCodec.AnyOf) else None
+        classes = None if alts is not None else self._classes(pattern, ignore_case)     # (byte_classes raises for a wrong length)
+        if alts is not None:
+            key = (alts[0].tobytes(), alts[1].tobytes(), len(alts[1]))
+        elif classes is None:
             pattern = bytes(pattern)
             plen = len(pattern)
             if not 1 <= plen <= _native.FIND_PATTERN_MAX:
                 raise ValueError(f"a pattern has 1 to {_native.FIND_PATTERN_MAX} bytes, not {plen}")
+            key = (pattern, plen)
         else:
-            pattern, plen = classes.tobytes(), len(classes)
+            key = (classes.tobytes(), len(classes))
         max_positions = int(max_positions)
         pos = torch.empty(max_positions, dtype=torch.int64, device=self.tdev) if out is None else out
         assert pos.is_cuda and pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == max_positions and pos.is_contiguous()
         totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
         errs = torch.empty(nblocks, dtype=torch.int32, device=self.tdev)
         counts = torch.empty(nblocks, dtype=torch.int64, device=self.tdev) if block_counts else None
-        call = self.lib.hufgpu_find_pattern if classes is None else self.lib.hufgpu_find_classes
+        call = (self.lib.hufgpu_find_any if alts is not None else
+                self.lib.hufgpu_find_pattern if classes is None else self.lib.hufgpu_find_classes)
         err = call(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
                                            offsets.data_ptr() if nblocks else None, nblocks,
-                                           sub_index.data_ptr() if nblocks else None, raw_size, blocksize, pattern,
-                                           plen, pos.data_ptr() if max_positions else None, max_positions,
+                                           sub_index.data_ptr() if nblocks else None, raw_size, blocksize, *key,
+                                           pos.data_ptr() if max_positions else None, max_positions,
                                            counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(),
                                            errs.data_ptr() if nblocks else None,
                                            _native.RELAXED_TREE if relaxed else _native.STRICT_TREE, self._stream())
@@ -508,10 +561,22 @@ class GpuCodec:
         too long or holds a delimiter.
         A `list` / `tuple` pattern is one of classes and `ignore_case` makes classes of a literal's letters, as for
         find_pattern (hufgpu_find_records_classes); a class that holds a delimiter is a ValueError that names its position:
-        subtract the delimiters from a wide class."""
-        classes = self._classes(pattern, ignore_case)
+        subtract the delimiters from a wide class.
+        A GpuCodec.AnyOf pattern reports the records that hold at least one of its alternatives, each record once
+        (hufgpu_find_records_any): grep -e A -e B.  No class of any alternative may hold a delimiter."""
+        alts = self.alt_classes(pattern, ignore_case) if isinstance(pattern, GpuCodec.AnyOf) else None
+        classes = None if alts is not None else self._classes(pattern, ignore_case)
         st = self.byte_set(delimiters)
-        if classes is None:
+        if alts is not None:
+            both = alts[0] & np.frombuffer(st, np.uint8)
+            if both.any():
+                row = int(np.flatnonzero(both.any(axis=1))[0])
+                j = int(np.searchsorted(np.cumsum(alts[1]), row, side="right"))
+                k = row - int(alts[1][:j].sum())
+                v = int(np.flatnonzero(np.unpackbits(both[row], bitorder="little"))[0])
+                raise ValueError(f"class {k} of alternative {j} holds a delimiter (value {v}): a match lies inside one record")
+            key = (alts[0].tobytes(), alts[1].tobytes(), len(alts[1]))
+        elif classes is None:
             pattern = bytes(pattern)
             plen = len(pattern)
             if not 1 <= plen <= _native.FIND_PATTERN_MAX:
@@ -519,13 +584,14 @@ class GpuCodec:
             for v in pattern:
                 if st[v >> 3] >> (v & 7) & 1:
                     raise ValueError(f"byte value {v} of the pattern is a delimiter: a match lies inside one record")
+            key = (pattern, plen)
         else:
             both = classes & np.frombuffer(st, np.uint8)
             if both.any():
                 k = int(np.flatnonzero(both.any(axis=1))[0])
                 v = int(np.flatnonzero(np.unpackbits(both[k], bitorder="little"))[0])
                 raise ValueError(f"class {k} of the pattern holds a delimiter (value {v}): a match lies inside one record")
-            pattern, plen = classes.tobytes(), len(classes)
+            key = (classes.tobytes(), len(classes))
         max_records, max_len = int(max_records), int(max_len)
         if out is None:
             out = (torch.empty(max_records, dtype=torch.int64, device=self.tdev),
@@ -536,11 +602,12 @@ class GpuCodec:
         totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
         errs = torch.empty(nblocks, dtype=torch.int32, device=self.tdev)
         counts = torch.empty(nblocks, dtype=torch.int64, device=self.tdev) if block_counts else None
-        call = self.lib.hufgpu_find_records if classes is None else self.lib.hufgpu_find_records_classes
+        call = (self.lib.hufgpu_find_records_any if alts is not None else
+                self.lib.hufgpu_find_records if classes is None else self.lib.hufgpu_find_records_classes)
         err = call(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
                                            offsets.data_ptr() if nblocks else None, nblocks,
-                                           sub_index.data_ptr() if nblocks else None, raw_size, blocksize, st, pattern,
-                                           plen, pos.data_ptr() if max_records else None,
+                                           sub_index.data_ptr() if nblocks else None, raw_size, blocksize, st, *key,
+                                           pos.data_ptr() if max_records else None,
                                            lens.data_ptr() if max_records else None, max_records, max_len,
                                            counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(),
                                            errs.data_ptr() if nblocks else None,

@@ -1,7 +1,8 @@
 /* find.hpp - hufgpu_find_bytes, hufgpu_find_pattern and hufgpu_find_records: where the bytes of a set of byte values lie
    in the original data, where a pattern of bytes starts, and which records - the pieces between delimiters - hold the
    pattern; hufgpu_find_classes and hufgpu_find_records_classes: the same for a pattern whose every position is a set of
-   byte values (include/huffman_gpu.h, kernels/find.hpp), enqueue-only.  Part of hufgpu_api.hip (one translation unit). */
+   byte values; hufgpu_find_any and hufgpu_find_records_any: the same for ANY of several such patterns, in the one walk
+   (include/huffman_gpu.h, kernels/find.hpp), enqueue-only.  Part of hufgpu_api.hip (one translation unit). */
 #pragma once
 
 static_assert(FIND_PAT_MAX == HUFGPU_FIND_PATTERN_MAX, "kernels/find.hpp and include/huffman_gpu.h");
@@ -13,15 +14,16 @@ struct FindRecCall {
     uint32_t max_len;
 };
 
-/* All five calls: `who` words the errors, `key` is the set (plen = 0) or the pattern of plen bytes, `key_name` its name;
+/* All seven calls: `who` words the errors, `key` is the set (plen = 0) or the pattern of plen bytes, `key_name` its name;
  * rec is NULL but for the records' calls.  cls is NULL but for the class calls: then `key` is the caller's array of plen
  * classes, which this function only checks for NULL and never reads - its wrapper has read it -, and cls is the table made
- * from it. */
+ * from it.  alt is NULL but for the any-of calls: then cls is alt's table (several alternatives in its 64 bits), plen is the
+ * LONGEST alternative's length - what the edges workspace and the seam launch follow - and alt goes to the kernels. */
 static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, const uint8_t *key, uint32_t plen,
                      const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets, uint64_t nblocks,
                      const void *d_sub_index, uint64_t raw_size, uint64_t blocksize, uint64_t *d_pos, uint64_t pos_cap,
                      uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream,
-                     const FindRecCall *rec = NULL, const FindClsTable *cls = NULL)
+                     const FindRecCall *rec = NULL, const FindClsTable *cls = NULL, FindAltArgs *alt = NULL)
 {
     if (!key || !d_totals) {
         set_err(ctx, "%s: the %s and d_totals are required", who, key_name);
@@ -136,7 +138,11 @@ static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, c
         HIP_OK(ctx, hipMemsetAsync(ra.rcnt, 0, fa.ntiles * sizeof(uint32_t), s));
         const uint64_t sper = FIND_SEAM_THREADS / 64;
         const dim3 seams((unsigned)((fa.ntiles + sper - 1) / sper));
-        if (cls) {                                                  /* the table goes with the launches' own arguments */
+        if (alt) {                                                  /* the table goes with the launches' own arguments */
+            alt->r = ra;
+            find_rec_alt_sub_kernel<<<dim3((unsigned)(nblocks * cpb)), dim3(FIND_THREADS), 0, s>>>(*alt);
+            if (plen > 1) find_alt_seam_kernel<<<seams, dim3(FIND_SEAM_THREADS), 0, s>>>(*alt);
+        } else if (cls) {
             const FindClsArgs ca = {ra, *cls};
             find_rec_cls_sub_kernel<<<dim3((unsigned)(nblocks * cpb)), dim3(FIND_THREADS), 0, s>>>(ca);
             if (plen > 1) find_cls_seam_kernel<<<seams, dim3(FIND_SEAM_THREADS), 0, s>>>(ca);
@@ -157,6 +163,11 @@ static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, c
     }
     if (plen == 0) {
         find_sub_kernel<<<dim3((unsigned)(nblocks * cpb)), dim3(FIND_THREADS), 0, s>>>(fa);
+    } else if (alt) {
+        const uint64_t per = FIND_SEAM_THREADS / 64;
+        alt->r = ra;
+        find_alt_sub_kernel<<<dim3((unsigned)(nblocks * cpb)), dim3(FIND_THREADS), 0, s>>>(*alt);
+        if (plen > 1) find_alt_seam_kernel<<<dim3((unsigned)((fa.ntiles + per - 1) / per)), dim3(FIND_SEAM_THREADS), 0, s>>>(*alt);
     } else if (cls) {
         const FindClsArgs ca = {ra, *cls};
         const uint64_t per = FIND_SEAM_THREADS / 64;
@@ -276,4 +287,98 @@ extern "C" int hufgpu_find_records_classes(hufgpu_ctx_t *ctx, const void *d_stre
     const FindRecCall rec = {delim_set, d_rec_len, max_len};
     return find_call(ctx, "find_records_classes", "classes", classes, pattern_len, d_stream, stream_len, d_block_offsets, nblocks,
                      d_sub_index, raw_size, blocksize, d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs, flags, stream, &rec, &t);
+}
+
+/* The any-of calls' own checks - 1 to 64 alternatives, none of length 0, lengths that sum to at most 64, no empty class, no
+ * class that holds a delimiter - and their table (kernels/find.hpp, FindAltArgs: alternative 0 at the bits 63 ... 64 - len_0,
+ * alternative 1 below it, position k of alternative j at bit hi_j - k).  `classes` and `alt_lens` are not NULL; the total is
+ * looked at before `classes` is read.  *maxlen: the longest alternative's length. */
+static int find_alt_table(hufgpu_ctx_t *ctx, const char *who, const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                          const uint8_t *delim_set, FindAltArgs *t, uint32_t *maxlen)
+{
+    if (n_alts == 0 || n_alts > HUFGPU_FIND_PATTERN_MAX) {
+        set_err(ctx, "%s: n_alts %u is not 1 to %d", who, n_alts, HUFGPU_FIND_PATTERN_MAX);
+        return HUFE_ARGUMENT;
+    }
+    uint64_t total = 0;
+    for (uint32_t j = 0; j < n_alts; j++) {
+        if (alt_lens[j] == 0) {
+            set_err(ctx, "%s: alternative %u has length 0: it would match everywhere", who, j);
+            return HUFE_ARGUMENT;
+        }
+        total += alt_lens[j];
+    }
+    if (total > HUFGPU_FIND_PATTERN_MAX) {
+        set_err(ctx, "%s: the lengths of the %u alternatives sum to %llu, above %d", who, n_alts, (unsigned long long)total,
+                HUFGPU_FIND_PATTERN_MAX);
+        return HUFE_ARGUMENT;
+    }
+    memset(t, 0, sizeof(*t));
+    t->n_alts = n_alts;
+    *maxlen = 0;
+    uint32_t hi = 63;
+    const uint8_t *cl = classes;
+    for (uint32_t j = 0; j < n_alts; j++) {
+        const uint32_t len = alt_lens[j];
+        for (uint32_t k = 0; k < len; k++, cl += 32) {
+            const uint32_t bit = hi - k;
+            bool any = false;
+            for (uint32_t v = 0; v < 256; v++) {
+                if (!((cl[v >> 3] >> (v & 7)) & 1)) continue;
+                if (delim_set && ((delim_set[v >> 3] >> (v & 7)) & 1)) {
+                    set_err(ctx, "%s: class %u of alternative %u holds a delimiter (value %u): a match lies inside one record", who, k, j, v);
+                    return HUFE_ARGUMENT;
+                }
+                any = true;
+                t->t.m[v][bit >> 5] |= 1u << (bit & 31u);
+            }
+            if (!any) {
+                set_err(ctx, "%s: class %u of alternative %u is empty: it matches nothing", who, k, j);
+                return HUFE_ARGUMENT;
+            }
+            t->t.full[bit >> 5] |= 1u << (bit & 31u);
+        }
+        const uint32_t last = hi - (len - 1u);
+        t->starts[hi >> 5] |= 1u << (hi & 31u);
+        t->t.first[last >> 5] |= 1u << (last & 31u);
+        t->hl[j] = (uint16_t)(hi | (len << 8));
+        if (len > *maxlen) *maxlen = len;
+        hi -= len;                                                  /* (wraps behind the last alternative of a total of 64: not used again) */
+    }
+    return HUFE_OK;
+}
+
+extern "C" int hufgpu_find_any(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                               uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                               const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts, uint64_t *d_pos, uint64_t pos_cap,
+                               uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream)
+{
+    FindAltArgs t;
+    uint32_t maxlen = 0;
+    const bool both = classes && alt_lens;
+    if (both) {
+        const int rc = find_alt_table(ctx, "find_any", classes, alt_lens, n_alts, NULL, &t, &maxlen);
+        if (rc) return rc;
+    }
+    return find_call(ctx, "find_any", "classes, alt_lens", both ? classes : NULL, maxlen, d_stream, stream_len, d_block_offsets, nblocks,
+                     d_sub_index, raw_size, blocksize, d_pos, pos_cap, d_block_counts, d_totals, d_block_errs, flags, stream, NULL, &t.t, &t);
+}
+
+extern "C" int hufgpu_find_records_any(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                       uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                       const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                                       uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t rec_cap, uint32_t max_len,
+                                       uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream)
+{
+    FindAltArgs t;
+    uint32_t maxlen = 0;
+    const bool both = classes && alt_lens;
+    if (both) {
+        const int rc = find_alt_table(ctx, "find_records_any", classes, alt_lens, n_alts, delim_set, &t, &maxlen);
+        if (rc) return rc;
+    }
+    const FindRecCall rec = {delim_set, d_rec_len, max_len};
+    return find_call(ctx, "find_records_any", "classes, alt_lens", both ? classes : NULL, maxlen, d_stream, stream_len, d_block_offsets,
+                     nblocks, d_sub_index, raw_size, blocksize, d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs, flags, stream,
+                     &rec, &t.t, &t);
 }

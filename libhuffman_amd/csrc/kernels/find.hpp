@@ -1,6 +1,7 @@
-/* find.hpp - the kernels of hufgpu_find_bytes, hufgpu_find_pattern, hufgpu_find_records and of the two class calls
-   (include/huffman_gpu.h): where in the original data the bytes of a set of byte values lie, where a pattern of 1 to 64
-   bytes - or of 1 to 64 sets of byte values - starts, or which records between delimiters hold it, straight from stream,
+/* find.hpp - the kernels of hufgpu_find_bytes, hufgpu_find_pattern, hufgpu_find_records, of the two class calls and of the
+   two any-of calls (include/huffman_gpu.h): where in the original data the bytes of a set of byte values lie, where a pattern
+   of 1 to 64 bytes - or of 1 to 64 sets of byte values, or any of several such patterns - starts, or which records between
+   delimiters hold it, straight from stream,
    block index and sub-index; no decoded byte reaches device memory (the pattern calls keep at most 126 edge bytes a tile)
    and the host only enqueues.  Part of hufgpu_kernels.hip (one translation unit, gfx950 only).
 
@@ -79,7 +80,18 @@
                            lies in LDS in the place of the 64 pattern bytes, and the lane matcher is a Shift-And automaton
                            over the reversed pattern (find_cls_lane): one table look-up a byte, 32 + pattern_len - 1 (+ 3)
                            a lane, whatever the data and however wide the classes.
-     find_cls_seam_kernel  the second instance of find_seam_kernel's body: byte k against class k. */
+     find_cls_seam_kernel  the second instance of find_seam_kernel's body: byte k against class k.
+
+   hufgpu_find_any / hufgpu_find_records_any: the class routes with SEVERAL class patterns - alternatives, grep -e A -e B -
+   in the one walk; a set bit is a start at which at least one of them lies.  Everything behind the seam kernel runs unchanged.
+     find_alt_sub_kernel, find_rec_alt_sub_kernel
+                           the sixth and seventh instance of find_sub_kernel's body.  The alternatives lie one below the other
+                           in the 64 bits of the same table (FindAltArgs) and the automaton's step is the class step; a start
+                           is a byte at which the start bit of ANY alternative is set.  A lane warms up over the longest
+                           alternative's length - 1 bytes, the edges are that many, and the walk sets the starts at which
+                           the LONGEST alternative fits in the tile, whichever alternative lies there.
+     find_alt_seam_kernel  the tile's last (longest length - 1) starts, for every alternative, a short one that ends inside
+                           the tile included: one bit and one count a start however many alternatives lie there. */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -195,6 +207,23 @@ struct FindClsArgs {
 };
 static_assert(sizeof(FindClsArgs) <= 4096, "a kernel's arguments end at 4 KiB");
 
+/* hufgpu_find_any / hufgpu_find_records_any: SEVERAL class patterns - alternatives - share the 64 bits of the automaton's
+ * state.  Alternative 0 takes the bits 63 ... 64 - len_0 of the table, alternative 1 the next len_1 bits down, and so on:
+ * position k of alternative j is bit hi_j - k.  `starts` has bit hi_j of every alternative (a match of j starts at this
+ * byte), t.first holds the bits of all the alternatives' LAST positions, where the automaton starts them: the bit that
+ * the shift moves out of alternative j's start lands on alternative j - 1's last position, which is set there anyway, so
+ * no bits are needed between two alternatives.  r.p.plen is the LONGEST alternative's length: the edge bytes a tile
+ * keeps, a lane's warm-up and the split of the starts between the walk and the seam kernel follow it.  hl[j] is
+ * hi_j | len_j << 8, for the seam kernel. */
+struct FindAltArgs {
+    FindRecArgs r;
+    FindClsTable t;                         /* t.first: the last positions' bits; t.full: every used bit */
+    uint32_t starts[2];                     /* ([0] the low half) */
+    uint32_t n_alts;
+    uint16_t hl[FIND_PAT_MAX];
+};
+static_assert(sizeof(FindAltArgs) <= 4096, "a kernel's arguments end at 4 KiB");
+
 #define FIND_CLS_WORDS 512                  /* the table's words in LDS: m[v] at words 2 v and 2 v + 1 */
 
 /* one byte of the Shift-And automaton that runs over the REVERSED pattern, from high addresses to low ones: bit 63 - k of
@@ -213,9 +242,15 @@ __device__ __forceinline__ void find_cls_step(uint32_t &lo, uint32_t &hi, const 
  * the first, so that a match is seen AT its start and every lane writes its own word only: 32 + plen - 1 (+ 3) table
  * look-ups a lane whatever the data and the classes are.  Bit 63 of the state depends on the plen bytes from the start on
  * and on nothing else, and the starts with start + plen > tsym are masked: what is stale behind a short tile - or the
- * slice's last word read again behind the tile's end - reaches no decision. */
+ * slice's last word read again behind the tile's end - reaches no decision.
+ * ALT (hufgpu_find_any): the state holds several alternatives, plen is the longest one's length, and a start is a byte at
+ * which ANY bit of `starts` is set.  Alternative j's start bit depends on the len_j <= plen bytes from the start on and on
+ * nothing else, so the same mask of the starts serves: the walk sets the starts with start + plen <= tsym, whichever
+ * alternative lies there, and find_alt_seam_kernel has the tile's last plen - 1 starts for every alternative. */
+template <bool ALT = false>
 __device__ __forceinline__ uint32_t find_cls_lane(const uint32_t *tile_words, const uint32_t (&w)[8], const uint32_t *s_m, uint32_t first_lo,
-                                                  uint32_t first_hi, uint32_t plen, uint32_t tsym, uint32_t lane)
+                                                  uint32_t first_hi, uint32_t plen, uint32_t tsym, uint32_t lane,
+                                                  [[maybe_unused]] uint32_t starts_lo = 0, [[maybe_unused]] uint32_t starts_hi = 0)
 {
     uint32_t lo = 0, hi = 0;
     for (uint32_t k = (plen + 2u) >> 2; k-- > 0u;) {                /* the words that hold the plen - 1 bytes behind the lane's */
@@ -229,7 +264,10 @@ __device__ __forceinline__ uint32_t find_cls_lane(const uint32_t *tile_words, co
 #pragma unroll
         for (int i = 3; i >= 0; i--) {
             find_cls_step(lo, hi, s_m, first_lo, first_hi, (w[j] >> (8 * i)) & 0xffu);
-            m |= (hi >> 31) << (4 * j + i);
+            /* (the bytes come last first: the mask is shifted up under each new bit - a bit set by its own constant would
+             * keep 25 constants and 32 partial masks in registers, 34 VGPRs more) */
+            if constexpr (ALT) m = (m << 1) | dmin<uint32_t>((hi & starts_hi) | (lo & starts_lo), 1u);
+            else m |= (hi >> 31) << (4 * j + i);
         }
     }
     const uint32_t fit = tsym >= plen ? tsym - plen + 1u : 0u;      /* starts of the tile at which the pattern fits */
@@ -240,12 +278,15 @@ __device__ __forceinline__ uint32_t find_cls_lane(const uint32_t *tile_words, co
 /* the body of find_sub_kernel (PAT = false: p is not looked at), of find_pat_sub_kernel and of find_rec_sub_kernel (PAT
  * and REC: the pattern's work, and r's delimiter masks and counts next to it), and with CLS of find_cls_sub_kernel and
  * find_rec_cls_sub_kernel: the same walk, checks, edges, delimiter masks and counts with the class table ct in the place of
- * the pattern's bytes; grid nblocks * cpb */
-template <bool PAT, bool REC = false, bool CLS = false>
-__device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatArgs *p, const FindRecArgs *r = nullptr, const FindClsTable *ct = nullptr)
+ * the pattern's bytes; with ALT of find_alt_sub_kernel and find_rec_alt_sub_kernel: ct holds several alternatives, alt
+ * says where they start, and p->plen is the longest one's length; grid nblocks * cpb */
+template <bool PAT, bool REC = false, bool CLS = false, bool ALT = false>
+__device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatArgs *p, const FindRecArgs *r = nullptr, const FindClsTable *ct = nullptr,
+                                              [[maybe_unused]] const FindAltArgs *alt = nullptr)
 {
     static_assert(PAT || !REC, "the records' route is the pattern's");
     static_assert(PAT || !CLS, "the classes' route is the pattern's");
+    static_assert(CLS || !ALT, "the alternatives' route is the classes'");
     constexpr uint32_t KEY_WORDS = CLS ? FIND_CLS_WORDS : (PAT ? FIND_PAT_MAX / 4 : 8);      /* the delimiter set lies behind them */
     typedef DsubShared<FIND_THREADS> SH;
     __shared__ SH sh;
@@ -294,7 +335,16 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
             /* the pattern is plen copies of the leaf, or it starts nowhere in this block; as for other blocks only
              * the starts whose match stays inside its tile are set here, find_seam_kernel has the rest */
             plen = p->plen;
-            if constexpr (CLS) {                                    /* ... the leaf is in every class, or there is no start */
+            if constexpr (ALT) {
+                /* ... the leaf is in every class of at least ONE alternative: m[leaf] has all of that alternative's bits,
+                 * which is what the automaton's start bits say after plen copies of the leaf (after len_j of them
+                 * alternative j's start bit is set iff the leaf is in all its classes, and it stays as it is from then on).
+                 * The starts of a tile at which the LONGEST alternative fits are set here, as in other blocks;
+                 * find_alt_seam_kernel has the rest, alternative by alternative. */
+                uint32_t lo = 0, hi = 0;
+                for (uint32_t k = 0; k < plen; k++) find_cls_step(lo, hi, s_set, ct->first[0], ct->first[1], (uint32_t)leaf);
+                match = ((hi & alt->starts[1]) | (lo & alt->starts[0])) != 0u;
+            } else if constexpr (CLS) {                             /* ... the leaf is in every class, or there is no start */
                 match = (s_set[2u * (uint32_t)leaf] & ct->full[0]) == ct->full[0] && (s_set[2u * (uint32_t)leaf + 1u] & ct->full[1]) == ct->full[1];
             } else {
                 match = true;
@@ -362,7 +412,8 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
         uint32_t m = 0;
         if constexpr (PAT) {
             const uint32_t tsym = (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE), plen = p->plen;
-            if constexpr (CLS) m = find_cls_lane(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane);
+            if constexpr (ALT) m = find_cls_lane<true>(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane, alt->starts[0], alt->starts[1]);
+            else if constexpr (CLS) m = find_cls_lane(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane);
             else m = find_pat_lane(tile_words, w, s_set, plen, tsym, lane);         /* (0 for a lane without symbols) */
             /* the edges: the tile's first and last min(tsym, plen - 1) bytes */
             const uint32_t ne = dmin<uint32_t>(tsym, plen - 1u);
@@ -412,6 +463,8 @@ __global__ __launch_bounds__(FIND_THREADS) void find_pat_sub_kernel(FindPatArgs 
 __global__ __launch_bounds__(FIND_THREADS) void find_rec_sub_kernel(FindRecArgs a) { find_sub_body<true, true>(a.p.f, &a.p, &a); }
 __global__ __launch_bounds__(FIND_THREADS) void find_cls_sub_kernel(FindClsArgs a) { find_sub_body<true, false, true>(a.r.p.f, &a.r.p, nullptr, &a.t); }
 __global__ __launch_bounds__(FIND_THREADS) void find_rec_cls_sub_kernel(FindClsArgs a) { find_sub_body<true, true, true>(a.r.p.f, &a.r.p, &a.r, &a.t); }
+__global__ __launch_bounds__(FIND_THREADS) void find_alt_sub_kernel(FindAltArgs a) { find_sub_body<true, false, true, true>(a.r.p.f, &a.r.p, nullptr, &a.t, &a); }
+__global__ __launch_bounds__(FIND_THREADS) void find_rec_alt_sub_kernel(FindAltArgs a) { find_sub_body<true, true, true, true>(a.r.p.f, &a.r.p, &a.r, &a.t, &a); }
 
 /* tile (b, t) of the layout: its symbols */
 __device__ __forceinline__ uint32_t find_tile_syms(uint64_t blen, uint64_t t) { return (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE); }
@@ -485,6 +538,79 @@ __device__ __forceinline__ void find_seam_body(const FindPatArgs &pa, const Find
 
 __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_seam_kernel(FindPatArgs pa) { find_seam_body<false>(pa); }
 __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_cls_seam_kernel(FindClsArgs a) { find_seam_body<true>(a.r.p, &a.t); }
+
+/* hufgpu_find_any: a wave = one tile, a lane = one of its last plen - 1 starts, plen the LONGEST alternative's length
+ * (launched for plen >= 2 only), as find_seam_body - and these starts are this kernel's for EVERY alternative, a short one
+ * that ends inside the tile included: the tile's tail slot holds all the bytes it needs.  The wave goes through the
+ * alternatives together (hi_j and len_j are the wave's, in scalar registers: class k of alternative j is bit hi_j - k, a
+ * mask that walks down by a constant shift); a lane takes part until one alternative fits, each with its own
+ * pos + len_j <= raw_size and its own walk over served blocks, and then sets ONE bit and counts ONE match. */
+__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_alt_seam_kernel(FindAltArgs aa)
+{
+    __shared__ uint32_t s_pat[FIND_CLS_WORDS];
+    __shared__ uint32_t s_hl[FIND_PAT_MAX];
+    const FindPatArgs &pa = aa.r.p;
+    const FindArgs &a = pa.f;
+    for (uint32_t i = threadIdx.x; i < FIND_CLS_WORDS; i += FIND_SEAM_THREADS) s_pat[i] = aa.t.m[i >> 1][i & 1u];
+    if (threadIdx.x < FIND_PAT_MAX) s_hl[threadIdx.x] = aa.hl[threadIdx.x];
+    __syncthreads();
+    const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
+    const uint64_t i = (uint64_t)blockIdx.x * (FIND_SEAM_THREADS / 64) + wave;
+    if (i >= a.ntiles) return;
+    const uint64_t b = i / a.tpb, t = i % a.tpb;
+    const uint64_t blen = find_block_len(a, b);
+    if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK) return;  /* (a block that is not served counts nothing) */
+    const uint32_t plen = pa.plen, tsym = find_tile_syms(blen, t);
+    const uint32_t ne = dmin<uint32_t>(tsym, plen - 1u);
+    const uint32_t s = tsym - ne + lane;                            /* the lane's start in the tile */
+    const uint64_t pos = b * a.s.bsize + t * HUF_SUB_TILE + s;
+    /* the byte AT the start, read once: an alternative whose first class does not hold it starts no walk, so a lane
+     * that no alternative can start at - nearly every lane - costs this one load however many alternatives there are */
+    const uint32_t at = lane < ne ? pa.edges[i * FIND_EDGE_SLOT + 64u + lane] : 0u;
+    const uint32_t m0 = s_pat[2u * at], m1 = s_pat[2u * at + 1u];
+    bool hit = false;
+    for (uint32_t j = 0; j < aa.n_alts; j++) {
+        const uint32_t hl = uni32(s_hl[j]), len = hl >> 8;
+        uint32_t kbit = 1u << (hl & 31u), khalf = (hl >> 5) & 1u;   /* class k is bit kbit of half khalf of a table entry */
+        bool same = lane < ne && !hit && ((khalf ? m1 : m0) & kbit) != 0u && pos + len <= a.s.raw_size;
+        if (same) {
+            const uint8_t *e = pa.edges + i * FIND_EDGE_SLOT + 64u; /* the own tail, then the heads of the tiles behind */
+            uint64_t cb = b, ct = t, cblen = blen;
+            uint32_t off = lane, csym = ne;                         /* byte k is e[off]; csym bytes there belong to this tile */
+            for (uint32_t k = 0; k < len; k++, off++) {
+                while (off == csym) {                               /* on into the next tile of the layout */
+                    if ((ct + 1) * HUF_SUB_TILE < cblen) {
+                        ct++;
+                    } else {
+                        cb++;                                       /* (pos + len <= raw_size: there is such a block) */
+                        ct = 0;
+                        cblen = find_block_len(a, cb);
+                        if (a.errs[cb] != HUFE_OK) {
+                            same = false;
+                            break;
+                        }
+                    }
+                    e = pa.edges + (cb * a.tpb + ct) * FIND_EDGE_SLOT;
+                    off = 0;
+                    csym = find_tile_syms(cblen, ct);
+                }
+                if (!same || (s_pat[2u * e[off] + khalf] & kbit) == 0u) {
+                    same = false;
+                    break;
+                }
+                kbit >>= 1;                                         /* class k + 1: the next bit down */
+                if (kbit == 0u) {
+                    kbit = 0x80000000u;
+                    khalf = 0u;
+                }
+            }
+        }
+        hit |= same;
+    }
+    if (hit) atomicOr(&a.bitmap[b * a.wpb + t * 64u + (s >> 5)], 1u << (s & 31u));
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(hit));
+    if (lane == 0 && cnt != 0u) a.tcnt[i] += cnt;
+}
 
 /* a workgroup = one SCAN_GROUP of tiles, as gather_scan_kernel sums the part counts */
 __global__ __launch_bounds__(SCAN_GROUP) void find_scan_kernel(FindArgs a)
