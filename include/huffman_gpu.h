@@ -559,6 +559,53 @@ int hufgpu_find_records_any(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t st
                             uint32_t flags, void *stream);
 
 /*
+ * FIND RECORDS, SELECTED: grep -v and grep -n.  hufgpu_find_records_any() reports the records that hold a match; this call
+ * can report the records that hold NONE (grep -v DEBUG, grep -v -e heartbeat -e healthz) and, for either answer, WHICH
+ * record each one is: the number of delimiters in front of it (grep -n prints that plus 1).  Both come from the two masks
+ * that the one walk writes anyway - match starts and delimiters -; there is no second walk and no other matcher, and what
+ * comes back goes into hufgpu_gather() unchanged.  The pattern arguments are the any-of form: one alternative of one-value
+ * classes is a literal, one alternative is a class pattern.  There is no CPU path.
+ *
+ * The contract is hufgpu_find_records_any()'s word for word - delim_set, classes / alt_lens / n_alts, d_sub_index (the
+ * caller vouches for NOTHING), d_block_errs, d_rec_pos / d_rec_len / rec_cap / max_len, d_totals[0..3], d_block_counts,
+ * the known-extent rule, batch geometry, flags, nblocks = 0, enqueue-only without a host write or a wait, every argument
+ * error (worded "find_records_select: ...") - but for this:
+ *
+ *   select        : 0 or HUFGPU_SELECT_INVERT.  Any other bit is HUF_ERROR_INVALID_ARGUMENT, found on the host before the
+ *                   context is looked at; the message names the value.
+ *   HUFGPU_SELECT_INVERT: the call reports the NON-EMPTY records [s, e), e > s, that hold no match of any alternative, each
+ *                   once, ascending.  A record is reported only when its extent is KNOWN by hufgpu_find_records()' own rule:
+ *                   every block that holds a byte of [max(s - 1, 0), min(e, raw_size - 1)] is served.  Inside a known record
+ *                   every match is known, so a record whose extent is known lies in exactly ONE of the two answers, the
+ *                   plain one or the inverted one, and a record whose extent is not known lies in neither.  EMPTY records
+ *                   are never reported - grep -v prints empty lines, this call does not: an empty record has no byte of
+ *                   its own, a final delimiter starts no record, and hufgpu_gather() has nothing to fetch for it.
+ *                   d_totals[0..3], d_block_counts, rec_cap and max_len mean for the selected records what they mean for
+ *                   the matching ones.
+ *   d_rec_no      : optional, NULL or rec_cap entries (it may be NULL with rec_cap > 0, and is not looked at with
+ *                   rec_cap = 0); written as d_rec_pos is: the first d_totals[1] entries and nothing behind them.
+ *                   d_rec_no[i] is the number of delimiter bytes in [0, d_rec_pos[i]) - empty records count -, exact when
+ *                   every block in front of the block that holds d_rec_pos[i] is served, and HUFGPU_REC_NO_UNKNOWN
+ *                   otherwise: a block that is not served hides its delimiters.  The record itself is still reported.
+ *                   With and without HUFGPU_SELECT_INVERT.
+ *
+ * The identity: select = 0 and d_rec_no = NULL give exactly what hufgpu_find_records_any() gives, by the same launches.
+ * HUFGPU_SELECT_INVERT adds one kernel over the record masks (at most one look-up of O(log tiles) a tile, whatever the
+ * data), d_rec_no one word of workspace, a kernel of a thread a block and a second instance of the last kernel; the seven
+ * older calls launch what they always did.  Measured in DESIGN.md 5.18.
+ */
+#define HUFGPU_SELECT_INVERT   1u
+#define HUFGPU_REC_NO_UNKNOWN  (~(uint64_t)0)
+int hufgpu_find_records_select(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                               const uint64_t *d_block_offsets, uint64_t nblocks,
+                               const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                               const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                               uint32_t select,
+                               uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no, uint64_t rec_cap, uint32_t max_len,
+                               uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                               uint32_t flags, void *stream);
+
+/*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from
  * another rank, or encoded here by a caller that did not keep the 7 % of side data.  hufgpu_encode_sub() writes the
  * sub-index as a by-product of packing; these three rebuild exactly that - the same entries, entry for entry

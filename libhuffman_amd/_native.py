@@ -38,6 +38,7 @@ STRICT_TREE = 0
 RELAXED_TREE = 1
 SEQUENTIAL = 2                  # hufgpu_decode_stream only
 RANGES_TILES = 4                # hufgpu_decode_ranges only: cut blocks by the sub-index tile (include/huffman_gpu.h, TILES)
+SELECT_INVERT = 1               # HUFGPU_SELECT_INVERT: hufgpu_find_records_select reports the records WITHOUT a match
 FIND_PATTERN_MAX = 64           # HUFGPU_FIND_PATTERN_MAX: the bytes of a hufgpu_find_pattern pattern
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -76,7 +77,8 @@ hufgpu_shard_range hufgpu_shard_plan_decode hufgpu_encode_sharded hufgpu_decode_
 hufgpu_batch_geometry hufgpu_encode_batch hufgpu_decode_batch hufgpu_decode_ranges
 hufgpu_sub_index_from_raw hufgpu_decode_build_sub hufgpu_build_sub_index hufgpu_update_ranges
 hufgpu_append hufgpu_truncate hufgpu_ranges_counters hufgpu_gather hufgpu_find_bytes hufgpu_find_pattern hufgpu_find_records
-hufgpu_find_classes hufgpu_find_records_classes hufgpu_find_any hufgpu_find_records_any""".split()
+hufgpu_find_classes hufgpu_find_records_classes hufgpu_find_any hufgpu_find_records_any
+hufgpu_find_records_select""".split()
 
 
 def so_path() -> str:
@@ -201,6 +203,9 @@ def load() -> C.CDLL:
     L.hufgpu_find_records_any.restype = C.c_int
     L.hufgpu_find_records_any.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, vp, vp, vp, C.c_uint32, vp, vp, u64, C.c_uint32, vp, vp, vp,
                                           C.c_uint32, vp]
+    L.hufgpu_find_records_select.restype = C.c_int        # hufgpu_find_records_any's with `select` and `d_rec_no`
+    L.hufgpu_find_records_select.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, u64,
+                                             C.c_uint32, vp, vp, vp, C.c_uint32, vp]
     _LIB = L
     return L
 

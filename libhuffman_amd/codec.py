@@ -547,7 +547,7 @@ class GpuCodec:
     def find_records(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, delimiters=b"\n",
                      max_records: int = 0, max_len: int = 0, block_counts: bool = False, relaxed: bool = False, out=None,
-                     ignore_case: bool = False):
+                     ignore_case: bool = False, invert: bool = False, line_numbers: bool = False):
         """The records of the original data - the pieces between the bytes of `delimiters` (an iterable of ints or a
         `bytes`; empty: the data is one record) - that hold `pattern` at least once, each record ONCE, on torch's current
         stream and without a synchronisation (hufgpu_find_records): one walk of the stream, no decoded byte written.
@@ -563,7 +563,18 @@ class GpuCodec:
         find_pattern (hufgpu_find_records_classes); a class that holds a delimiter is a ValueError that names its position:
         subtract the delimiters from a wide class.
         A GpuCodec.AnyOf pattern reports the records that hold at least one of its alternatives, each record once
-        (hufgpu_find_records_any): grep -e A -e B.  No class of any alternative may hold a delimiter."""
+        (hufgpu_find_records_any): grep -e A -e B.  No class of any alternative may hold a delimiter.
+        `invert` reports the NON-EMPTY records that hold NO match (grep -v, but for the empty lines): a record whose extent
+        is known lies in exactly one of the two answers.  `line_numbers` appends one tensor to the returned tuple,
+        numbers[max_records] int64: the delimiters in front of each written record, 0-based (grep -n prints it plus 1), -1
+        when a block in front of the record's is not served.  Either makes the call hufgpu_find_records_select, a `bytes` or
+        `list` pattern being its one alternative; with both False the call and what it returns are what they always were.
+        `out` may then hold a third buffer, contiguous int64 [max_records], for the numbers."""
+        select = bool(invert) or bool(line_numbers)
+        if select and not isinstance(pattern, GpuCodec.AnyOf):
+            if isinstance(pattern, str):
+                raise TypeError("a pattern is a bytes-like object or a list / tuple of classes, not a str")
+            pattern = GpuCodec.AnyOf(pattern)
         alts = self.alt_classes(pattern, ignore_case) if isinstance(pattern, GpuCodec.AnyOf) else None
         classes = None if alts is not None else self._classes(pattern, ignore_case)
         st = self.byte_set(delimiters)
@@ -596,12 +607,27 @@ class GpuCodec:
         if out is None:
             out = (torch.empty(max_records, dtype=torch.int64, device=self.tdev),
                    torch.empty(max_records, dtype=torch.int32, device=self.tdev))
-        pos, lens = out
+        numbers = None
+        if line_numbers:
+            numbers = out[2] if len(out) > 2 else torch.empty(max_records, dtype=torch.int64, device=self.tdev)
+            assert (numbers.is_cuda and numbers.dtype == torch.int64 and numbers.dim() == 1 and numbers.numel() == max_records
+                    and numbers.is_contiguous())
+        pos, lens = out[0], out[1]
         assert pos.is_cuda and pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == max_records and pos.is_contiguous()
         assert lens.is_cuda and lens.dtype == torch.int32 and lens.dim() == 1 and lens.numel() == max_records and lens.is_contiguous()
         totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
         errs = torch.empty(nblocks, dtype=torch.int32, device=self.tdev)
         counts = torch.empty(nblocks, dtype=torch.int64, device=self.tdev) if block_counts else None
+        if select:
+            err = self.lib.hufgpu_find_records_select(
+                self._ctx, stream.data_ptr() if stream.numel() else None, stream_len, offsets.data_ptr() if nblocks else None, nblocks,
+                sub_index.data_ptr() if nblocks else None, raw_size, blocksize, st, *key,
+                _native.SELECT_INVERT if invert else 0, pos.data_ptr() if max_records else None,
+                lens.data_ptr() if max_records else None, numbers.data_ptr() if line_numbers and max_records else None,
+                max_records, max_len, counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(),
+                errs.data_ptr() if nblocks else None, _native.RELAXED_TREE if relaxed else _native.STRICT_TREE, self._stream())
+            self._check(err, "Failed to enqueue the search")
+            return (pos, lens, totals, errs, counts) + ((numbers,) if line_numbers else ())
         call = (self.lib.hufgpu_find_records_any if alts is not None else
                 self.lib.hufgpu_find_records if classes is None else self.lib.hufgpu_find_records_classes)
         err = call(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
@@ -617,32 +643,37 @@ class GpuCodec:
 
     def count_records(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                       sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, delimiters=b"\n",
-                      relaxed: bool = False, ignore_case: bool = False):
-        """How many records hold `pattern` (grep -c): find_records without positions, enqueue-only.  Returns CUDA tensors
-        (totals[4], block_errs[nblocks]) as find_records does."""
-        _, _, totals, errs, _ = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
-                                                  delimiters, relaxed=relaxed, ignore_case=ignore_case)
-        return totals, errs
+                      relaxed: bool = False, ignore_case: bool = False, invert: bool = False, line_numbers: bool = False):
+        """How many records hold `pattern` (grep -c; with `invert` grep -v -c, but for the empty lines): find_records
+        without positions, enqueue-only.  Returns CUDA tensors (totals[4], block_errs[nblocks]) as find_records does, and
+        with `line_numbers` the empty tensor of numbers behind them."""
+        res = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
+                                delimiters, relaxed=relaxed, ignore_case=ignore_case, invert=invert, line_numbers=line_numbers)
+        return (res[2], res[3]) + tuple(res[5:])
 
     def grep(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, sub_index: torch.Tensor,
              raw_size: int, blocksize: int, pattern, max_records: int, max_len: int, delimiters=b"\n",
-             relaxed: bool = False, ignore_case: bool = False):
+             relaxed: bool = False, ignore_case: bool = False, invert: bool = False, line_numbers: bool = False):
         """The first `max_len` bytes of the first `max_records` records that hold `pattern`: find_records followed by
         gather, on torch's current stream and without a synchronisation.  Returns CUDA tensors (lines uint8 [max_records,
         max_len], raw_lens int32 [max_records] - the bytes of row i that are the record's -, errs int32 [max_records] -
         gather's per record -, totals[4] and block_errs[nblocks] as find_records gives them).  Rows from totals[1] on are
-        records of 0 bytes at raw_size."""
+        records of 0 bytes at raw_size.  `invert`: the non-empty records that do NOT hold it (grep -v); `line_numbers`: one
+        more tensor at the end, numbers int64 [max_records] as find_records gives them, -1 from row totals[1] on."""
         max_records, max_len = int(max_records), int(max_len)
         if max_len < 1:
             raise ValueError("grep needs max_len, the bytes of a row")
-        pos, lens, totals, block_errs, _ = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
-                                                             pattern, delimiters, max_records=max_records, max_len=max_len,
-                                                             relaxed=relaxed, ignore_case=ignore_case)
+        found = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
+                                  pattern, delimiters, max_records=max_records, max_len=max_len,
+                                  relaxed=relaxed, ignore_case=ignore_case, invert=invert, line_numbers=line_numbers)
+        pos, lens, totals, block_errs = found[:4]
         written = torch.arange(max_records, device=self.tdev) < totals[1]
         pos = torch.where(written, pos, raw_size)
         lens = torch.where(written, lens, 0)
         lines, errs, raw_lens = self.gather(stream, stream_len, offsets, nblocks, pos, lens, sub_index=sub_index, raw_size=raw_size,
                                             blocksize=blocksize, max_len=max_len, relaxed=relaxed)
+        if line_numbers:
+            return lines, raw_lens, errs, totals, block_errs, torch.where(written, found[5], -1)
         return lines, raw_lens, errs, totals, block_errs
 
     # -- overwrite: bytes [lo, hi) of the original data replaced in one indexed stream ---------------

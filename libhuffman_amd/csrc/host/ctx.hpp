@@ -122,6 +122,9 @@ struct hufgpu_ctx {
     uint32_t *d_frdbits, *d_frrbits, *d_frdcnt, *d_frrcnt;
     TwoLevel frec_scan;
     uint64_t *d_frdtotal;
+    /* hufgpu_find_records_select with d_rec_no: the first block that is not served; no other call allocates it */
+    uint64_t fsel_ws;
+    uint64_t *d_fsel_first;
 
     /* the sub-index builders (kernels/sub_build.hpp): what their kernels hand to one another, per block and per chunk */
     uint64_t sbws_blocks, sbws_chunks;
@@ -257,6 +260,7 @@ static const ws_buf WS_FIND_TILES[] = {DEV(d_ftcnt, n * sizeof(uint32_t))};
 static const ws_buf WS_FIND_EDGES[] = {DEV(d_fedges, n * FIND_EDGE_SLOT)};
 static const ws_buf WS_FIND_REC_WORDS[] = {DEV(d_frdbits, n * sizeof(uint32_t)), DEV(d_frrbits, n * sizeof(uint32_t))};
 static const ws_buf WS_FIND_REC_TILES[] = {DEV(d_frdcnt, n * sizeof(uint32_t)), DEV(d_frrcnt, n * sizeof(uint32_t)), DEV(d_frdtotal, sizeof(uint64_t))};
+static const ws_buf WS_FIND_SEL[] = {DEV(d_fsel_first, n * sizeof(uint64_t))};
 static const ws_buf WS_SB_BLOCKS[] = {DEV(d_sb_state, n * sizeof(uint32_t)), DEV(d_sb_pay, n * sizeof(uint64_t))};
 static const ws_buf WS_SB_CHUNKS[] = {DEV(d_sb_chunk_tot, n * sizeof(uint64_t)), DEV(d_sb_chunk_bits, n * sizeof(uint64_t))};
 static const ws_buf WS_UPD_BLOCKS[] = {
@@ -270,7 +274,7 @@ static const ws_buf WS_UPD_PIECES[] = {DEV(d_upiece, n * sizeof(uint32_t))};
  * block of many MiB and the range scratch take what they are asked for (grow_range_scratch adds its own eighth).
  * Soft groups report nothing: the caller has another way, or words the error itself. */
 enum { G_FIXED, G_ENCODE, G_CHUNK, G_DECODE, G_DISC_WGS, G_DISC_CANDS, G_BIG_LANES, G_BIG_SUB, G_BSTAGE, G_BATCH, G_RANGE,
-       G_RSCRATCH, G_GATHER_BLOCKS, G_GATHER_PARTS, G_FIND_WORDS, G_FIND_TILES, G_FIND_EDGES, G_FIND_REC_WORDS, G_FIND_REC_TILES, G_SB_BLOCKS, G_SB_CHUNKS, G_UPD_BLOCKS,
+       G_RSCRATCH, G_GATHER_BLOCKS, G_GATHER_PARTS, G_FIND_WORDS, G_FIND_TILES, G_FIND_EDGES, G_FIND_REC_WORDS, G_FIND_REC_TILES, G_FIND_SEL, G_SB_BLOCKS, G_SB_CHUNKS, G_UPD_BLOCKS,
        G_UPD_PIECES, G_COUNT };
 #define ROWS(a) a, (int)(sizeof(a) / sizeof(a[0]))
 #define CAP(member) {offsetof(hufgpu_ctx, member), WS_NO_CAP}
@@ -297,6 +301,7 @@ static const ws_group WS[G_COUNT] = {
     {"find edges", ROWS(WS_FIND_EDGES), CAP(fws_edge_tiles), WS_DOUBLE, false, NO_SCAN},
     {"find record words", ROWS(WS_FIND_REC_WORDS), CAP(frws_words), WS_DOUBLE, false, NO_SCAN},
     {"find record tiles", ROWS(WS_FIND_REC_TILES), CAP(frws_tiles), WS_DOUBLE, false, SCAN_AT(frec_scan)},
+    {"find select", ROWS(WS_FIND_SEL), CAP(fsel_ws), WS_EXACT, false, NO_SCAN},
     {"sub-build blocks", ROWS(WS_SB_BLOCKS), CAP(sbws_blocks), WS_EIGHTH, false, NO_SCAN},
     {"sub-build chunks", ROWS(WS_SB_CHUNKS), CAP(sbws_chunks), WS_EIGHTH, false, NO_SCAN},
     {"update blocks", ROWS(WS_UPD_BLOCKS), CAP(uws_blocks), WS_EIGHTH, false, NO_SCAN},

@@ -2,10 +2,12 @@
    in the original data, where a pattern of bytes starts, and which records - the pieces between delimiters - hold the
    pattern; hufgpu_find_classes and hufgpu_find_records_classes: the same for a pattern whose every position is a set of
    byte values; hufgpu_find_any and hufgpu_find_records_any: the same for ANY of several such patterns, in the one walk
-   (include/huffman_gpu.h, kernels/find.hpp), enqueue-only.  Part of hufgpu_api.hip (one translation unit). */
+   (include/huffman_gpu.h, kernels/find.hpp); hufgpu_find_records_select: the records WITHOUT a match of any alternative,
+   and the records' numbers.  All enqueue-only.  Part of hufgpu_api.hip (one translation unit). */
 #pragma once
 
 static_assert(FIND_PAT_MAX == HUFGPU_FIND_PATTERN_MAX, "kernels/find.hpp and include/huffman_gpu.h");
+static_assert(FIND_REC_NO_UNKNOWN == HUFGPU_REC_NO_UNKNOWN, "kernels/find.hpp and include/huffman_gpu.h");
 
 /* what hufgpu_find_records has beyond the pattern call: d_pos / pos_cap are its d_rec_pos / rec_cap */
 struct FindRecCall {
@@ -14,16 +16,25 @@ struct FindRecCall {
     uint32_t max_len;
 };
 
-/* All seven calls: `who` words the errors, `key` is the set (plen = 0) or the pattern of plen bytes, `key_name` its name;
+/* what hufgpu_find_records_select has beyond the any-of records' call */
+struct FindSelCall {
+    uint32_t select;                        /* checked by the wrapper */
+    uint64_t *d_rec_no;                     /* optional */
+};
+
+/* All eight calls: `who` words the errors, `key` is the set (plen = 0) or the pattern of plen bytes, `key_name` its name;
  * rec is NULL but for the records' calls.  cls is NULL but for the class calls: then `key` is the caller's array of plen
  * classes, which this function only checks for NULL and never reads - its wrapper has read it -, and cls is the table made
  * from it.  alt is NULL but for the any-of calls: then cls is alt's table (several alternatives in its 64 bits), plen is the
- * LONGEST alternative's length - what the edges workspace and the seam launch follow - and alt goes to the kernels. */
+ * LONGEST alternative's length - what the edges workspace and the seam launch follow - and alt goes to the kernels.
+ * sel is NULL but for the select call, which is the any-of records' call with up to three launches more: the seven other
+ * calls enqueue what they always did. */
 static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, const uint8_t *key, uint32_t plen,
                      const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets, uint64_t nblocks,
                      const void *d_sub_index, uint64_t raw_size, uint64_t blocksize, uint64_t *d_pos, uint64_t pos_cap,
                      uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream,
-                     const FindRecCall *rec = NULL, const FindClsTable *cls = NULL, FindAltArgs *alt = NULL)
+                     const FindRecCall *rec = NULL, const FindClsTable *cls = NULL, FindAltArgs *alt = NULL,
+                     const FindSelCall *sel = NULL)
 {
     if (!key || !d_totals) {
         set_err(ctx, "%s: the %s and d_totals are required", who, key_name);
@@ -89,6 +100,8 @@ static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, c
     int rc = ensure_find_ws(ctx, nblocks * wpb, nblocks * tpb);
     if (!rc && plen > 1) rc = grow_ws(ctx, G_FIND_EDGES, nblocks * tpb);    /* (one byte has no seams: no edges) */
     if (!rc && rec) rc = grow_ws2(ctx, G_FIND_REC_WORDS, nblocks * wpb, G_FIND_REC_TILES, nblocks * tpb);
+    const bool invert = sel && (sel->select & HUFGPU_SELECT_INVERT), numbers = sel && sel->d_rec_no && pos_cap > 0;
+    if (!rc && numbers) rc = grow_ws(ctx, G_FIND_SEL, 1);
     if (rc) return rc;
 
     FindRecArgs ra;
@@ -152,12 +165,20 @@ static int find_call(hufgpu_ctx_t *ctx, const char *who, const char *key_name, c
         }
         find_rec_dscan_kernel<<<groups, dim3(SCAN_GROUP), 0, s>>>(ra);
         find_rec_mark_kernel<<<tiles, dim3(FIND_EMIT_THREADS), 0, s>>>(ra);
+        if (invert) find_rec_invert_kernel<<<tiles, dim3(FIND_EMIT_THREADS), 0, s>>>(ra);   /* over mark's words and counts */
         FindArgs fr = fa;                                           /* scan, finish and emit: the records of a tile in the place of its matches */
         fr.tcnt = ra.rcnt;
         ra.p.f = fr;
         find_scan_kernel<<<groups, dim3(SCAN_GROUP), 0, s>>>(fr);
         find_finish_kernel<<<dim3(grid256(nblocks)), dim3(256), 0, s>>>(fr);
-        if (pos_cap > 0) find_rec_emit_kernel<<<tiles, dim3(FIND_EMIT_THREADS), 0, s>>>(ra);
+        if (numbers) {                                              /* the numbers need the first block that is not served */
+            const FindSelArgs sa = {ra, sel->d_rec_no, ctx->d_fsel_first};
+            HIP_OK(ctx, hipMemsetAsync(sa.first_bad, 0xff, sizeof(uint64_t), s));
+            find_rec_first_bad_kernel<<<dim3(grid256(nblocks)), dim3(256), 0, s>>>(sa);
+            find_rec_emit_no_kernel<<<tiles, dim3(FIND_EMIT_THREADS), 0, s>>>(sa);
+        } else if (pos_cap > 0) {
+            find_rec_emit_kernel<<<tiles, dim3(FIND_EMIT_THREADS), 0, s>>>(ra);
+        }
         HIP_OK(ctx, hipGetLastError());
         return HUFE_OK;
     }
@@ -381,4 +402,29 @@ extern "C" int hufgpu_find_records_any(hufgpu_ctx_t *ctx, const void *d_stream, 
     return find_call(ctx, "find_records_any", "classes, alt_lens", both ? classes : NULL, maxlen, d_stream, stream_len, d_block_offsets,
                      nblocks, d_sub_index, raw_size, blocksize, d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs, flags, stream,
                      &rec, &t.t, &t);
+}
+
+extern "C" int hufgpu_find_records_select(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                          uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                          const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                                          uint32_t select, uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no, uint64_t rec_cap,
+                                          uint32_t max_len, uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                                          uint32_t flags, void *stream)
+{
+    if (select & ~HUFGPU_SELECT_INVERT) {
+        set_err(ctx, "find_records_select: select 0x%x has a bit other than HUFGPU_SELECT_INVERT", select);
+        return HUFE_ARGUMENT;
+    }
+    FindAltArgs t;
+    uint32_t maxlen = 0;
+    const bool both = classes && alt_lens;
+    if (both) {
+        const int rc = find_alt_table(ctx, "find_records_select", classes, alt_lens, n_alts, delim_set, &t, &maxlen);
+        if (rc) return rc;
+    }
+    const FindRecCall rec = {delim_set, d_rec_len, max_len};
+    const FindSelCall sel = {select, d_rec_no};
+    return find_call(ctx, "find_records_select", "classes, alt_lens", both ? classes : NULL, maxlen, d_stream, stream_len, d_block_offsets,
+                     nblocks, d_sub_index, raw_size, blocksize, d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs, flags, stream,
+                     &rec, &t.t, &t, &sel);
 }

@@ -824,10 +824,90 @@ __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_mark_kernel(FindRe
     if (lane == 0 && cnt != 0u) atomicAdd(&ra.rcnt[i], cnt);
 }
 
+/* hufgpu_find_records_select: the records' route with two more answers.  r is the any-of call's; no is d_rec_no, or NULL;
+ * first_bad is one word of the find workspace: the first block that is not served, ~0 when every block is */
+struct FindSelArgs {
+    FindRecArgs r;
+    uint64_t *no;
+    uint64_t *first_bad;
+};
+
+#define FIND_REC_NO_UNKNOWN (~0ull)         /* = HUFGPU_REC_NO_UNKNOWN (include/huffman_gpu.h) */
+
+/* one thread per block (the statuses are final: the walk has ended; *first_bad is ~0 when this kernel starts).  The lanes'
+ * blocks ascend, so a wave's lowest lane with a block that is not served speaks for it: no atomic while all are served. */
+__global__ __launch_bounds__(256) void find_rec_first_bad_kernel(FindSelArgs sa)
+{
+    const FindArgs &a = sa.r.p.f;
+    const uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool bad = b < a.s.nblocks && a.errs[b] != HUFE_OK;
+    const uint64_t any = __ballot(bad);
+    if (any != 0 && (uint32_t)lane_id() == (uint32_t)__builtin_ctzll(any)) atomicMin((unsigned long long *)sa.first_bad, (unsigned long long)b);
+}
+
+/* HUFGPU_SELECT_INVERT, behind find_rec_mark_kernel: a wave = one tile, a lane = one word.  When mark has ended rbits holds
+ * the start of every known record with a match - in the START's tile, wherever the match lies - so this kernel is local to
+ * its tile: the candidates are the bytes behind a delimiter that are none themselves (byte 0 is one; nothing behind the
+ * block's end is), the byte in front of the lane's word coming from the lane below and, for lane 0, from the last word of
+ * the tile in front - the last, maybe short tile of block b - 1 for a block's first tile, and no candidate when that block
+ * is not served: the start is not known.  Every candidate but the tile's last ends inside the tile, at a real delimiter of
+ * a served block; the last one (no delimiter behind it in the tile) costs ONE look-up a tile, as in find_rec_emit_kernel,
+ * and is dropped when its end is open.  What is left is the non-empty records whose extent is known; those without a match
+ * are candidates & ~rbits.  Plain stores over mark's words and counts: scan, finish and emit then run as they are.  A tile of
+ * a block that is not served reports nothing. */
+__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_invert_kernel(FindRecArgs ra)
+{
+    const FindArgs &a = ra.p.f;
+    const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
+    const uint64_t i = (uint64_t)blockIdx.x * (FIND_EMIT_THREADS / 64) + wave;
+    if (i >= a.ntiles) return;
+    const uint64_t b = i / a.tpb, t = i % a.tpb;
+    const uint64_t blen = find_block_len(a, b);
+    if (t * HUF_SUB_TILE >= blen) return;
+    const uint64_t g = t * 64u + lane;
+    const bool inside = g * DSUB_SPL < blen;
+    uint32_t *word = ra.rbits + b * a.wpb + g;
+    if (a.errs[b] != HUFE_OK) {
+        if (inside) *word = 0u;
+        if (lane == 0) ra.rcnt[i] = 0u;
+        return;
+    }
+    const uint32_t d = find_rec_dword(ra, b, t, lane);
+    const uint32_t r = inside ? *word : 0u;
+    uint32_t c0;                                                    /* is the byte in front of the tile a delimiter (the wave's) */
+    if (i == 0) {
+        c0 = 1u;
+    } else if (t != 0) {
+        c0 = ra.dbits[b * a.wpb + t * 64u - 1u] >> 31;              /* (the tile in front is a full one) */
+    } else if (a.errs[b - 1] != HUFE_OK) {
+        c0 = 0u;
+    } else {
+        const uint64_t last = a.s.bsize - 1u;                       /* (a block with a block behind it is a full one) */
+        c0 = (ra.dbits[(b - 1) * a.wpb + (last >> 5)] >> ((uint32_t)last & 31u)) & 1u;
+    }
+    const uint32_t below = wave_up1_u32(d);                         /* (by every lane: a lane that sits out of a DPP move is not read) */
+    const uint32_t carry = lane == 0 ? c0 : below >> 31;
+    const uint64_t left = inside ? blen - g * DSUB_SPL : 0u;
+    const uint32_t valid = left >= 32u ? 0xffffffffu : (1u << (uint32_t)left) - 1u;
+    uint32_t cand = ((d << 1) | carry) & ~d & valid;
+    const FindRecLane k = find_rec_lane(d, lane);
+    const bool tail = k.next < 0 && (cand & k.tail) != 0u;
+    if (__ballot(tail) != 0 && find_rec_end_behind(ra, i, lane) == FIND_REC_OPEN && tail) cand &= ~k.tail;
+    const uint32_t n = cand & ~r;
+    if (inside) *word = n;
+    const uint32_t cnt = wave_lane_u32(wave_incl_scan_u32((uint32_t)__popc(n)), 63);
+    if (lane == 0) ra.rcnt[i] = cnt;
+}
+
 /* a wave = one tile, as find_emit_kernel: a set bit of rbits is a record's start s; its end is the first delimiter behind
  * it, looked for as find_rec_mark_kernel does (one look-up a tile at most: for its last record).  pos = s and
- * len = min(e - s, clip) go to the record's rank, the records cut by clip are counted into totals[3]. */
-__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_emit_kernel(FindRecArgs ra)
+ * len = min(e - s, clip) go to the record's rank, the records cut by clip are counted into totals[3].
+ * NO (find_rec_emit_no_kernel): the record's number goes to its rank as well - the delimiters in front of the tile, which
+ * find_rec_dscan_kernel has scanned, plus those of the tile below s: a wave prefix over the words' popcounts and the bits
+ * below s in the lane's own word.  The scan counts a delimiter that is nowhere for every tile of a block that is not served,
+ * so the number is known only while no block in front of b is one of those: FIND_REC_NO_UNKNOWN otherwise. */
+template <bool NO>
+__device__ __forceinline__ void find_rec_emit_body(const FindRecArgs &ra, [[maybe_unused]] const FindSelArgs *sa = nullptr)
 {
     const FindArgs &a = ra.p.f;
     const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
@@ -846,6 +926,12 @@ __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_emit_kernel(FindRe
     if (__ballot(k.next < 0 && (r & k.tail) != 0u) != 0) e_tail = find_rec_end_behind(ra, i, lane);
     uint64_t rank = rank0 + (wave_incl_scan_u32((uint32_t)__popc(r)) - (uint32_t)__popc(r));
     const uint64_t base = b * a.s.bsize + t * HUF_SUB_TILE;
+    [[maybe_unused]] uint64_t no0 = 0;                              /* the delimiters in front of the lane's word */
+    [[maybe_unused]] bool known = false;
+    if constexpr (NO) {
+        no0 = find_rec_before(ra, i) + (wave_incl_scan_u32((uint32_t)__popc(d)) - (uint32_t)__popc(d));
+        known = *sa->first_bad >= b;
+    }
     uint32_t cut = 0;
     while (r != 0u && rank < a.pos_cap) {
         const uint32_t bit = (uint32_t)__builtin_ctz(r);
@@ -856,11 +942,15 @@ __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_emit_kernel(FindRe
         const uint64_t n = e - s;
         a.pos[rank] = s;
         ra.len[rank] = n > ra.clip ? ra.clip : (uint32_t)n;
+        if constexpr (NO) sa->no[rank] = known ? no0 + (uint32_t)__popc(d & ((1u << bit) - 1u)) : FIND_REC_NO_UNKNOWN;
         cut += n > ra.clip;
         rank++;
     }
     const uint32_t cuts = wave_lane_u32(wave_incl_scan_u32(cut), 63);
     if (lane == 0 && cuts != 0u) atomicAdd((unsigned long long *)&a.totals[3], (unsigned long long)cuts);
 }
+
+__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_emit_kernel(FindRecArgs ra) { find_rec_emit_body<false>(ra); }
+__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_emit_no_kernel(FindSelArgs sa) { find_rec_emit_body<true>(sa.r, &sa); }
 
 }  // namespace hufgpu
