@@ -376,6 +376,24 @@ class GpuCodec:
             s[v >> 3] |= 1 << (v & 7)
         return bytes(s)
 
+    def _find_buffer(self, given, n: int, dtype):
+        """An output buffer of `n` items: `given` - contiguous, [n], of that dtype, on the device - or a new one"""
+        buf = torch.empty(n, dtype=dtype, device=self.tdev) if given is None else given
+        assert buf.is_cuda and buf.dtype == dtype and buf.dim() == 1 and buf.numel() == n and buf.is_contiguous()
+        return buf
+
+    def _find_args(self, stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, block_counts, relaxed):
+        """What every find call's C argument list starts and ends with, around the call's own part, and the tensors the
+        end points to: (head, tail, totals, errs, counts)"""
+        totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
+        errs = torch.empty(nblocks, dtype=torch.int32, device=self.tdev)
+        counts = torch.empty(nblocks, dtype=torch.int64, device=self.tdev) if block_counts else None
+        head = (self._ctx, stream.data_ptr() if stream.numel() else None, stream_len, offsets.data_ptr() if nblocks else None,
+                nblocks, sub_index.data_ptr() if nblocks else None, raw_size, blocksize)
+        tail = (counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(), errs.data_ptr() if nblocks else None,
+                _native.RELAXED_TREE if relaxed else _native.STRICT_TREE, self._stream())
+        return head, tail, totals, errs, counts
+
     def find_bytes(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                    sub_index: torch.Tensor, raw_size: int, blocksize: int, values, max_positions: int = 0,
                    block_counts: bool = False, relaxed: bool = False, out: torch.Tensor | None = None):
@@ -388,18 +406,10 @@ class GpuCodec:
         contiguous int64 [max_positions]; made when not given."""
         st = self.byte_set(values)
         max_positions = int(max_positions)
-        pos = torch.empty(max_positions, dtype=torch.int64, device=self.tdev) if out is None else out
-        assert pos.is_cuda and pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == max_positions and pos.is_contiguous()
-        totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
-        errs = torch.empty(nblocks, dtype=torch.int32, device=self.tdev)
-        counts = torch.empty(nblocks, dtype=torch.int64, device=self.tdev) if block_counts else None
-        err = self.lib.hufgpu_find_bytes(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
-                                         offsets.data_ptr() if nblocks else None, nblocks,
-                                         sub_index.data_ptr() if nblocks else None, raw_size, blocksize, st,
-                                         pos.data_ptr() if max_positions else None, max_positions,
-                                         counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(),
-                                         errs.data_ptr() if nblocks else None,
-                                         _native.RELAXED_TREE if relaxed else _native.STRICT_TREE, self._stream())
+        pos = self._find_buffer(out, max_positions, torch.int64)
+        head, tail, totals, errs, counts = self._find_args(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
+                                                           block_counts, relaxed)
+        err = self.lib.hufgpu_find_bytes(*head, st, pos.data_ptr() if max_positions else None, max_positions, *tail)
         self._check(err, "Failed to enqueue the search")
         return pos, totals, errs, counts
 
@@ -484,12 +494,51 @@ class GpuCodec:
             raise ValueError(f"the alternatives' lengths sum to {total}, above {_native.FIND_PATTERN_MAX}")
         return np.concatenate(rows), np.array([len(r) for r in rows], np.uint32)
 
+    _NO_RECORDS = object()          # _find_route's `delimiters` of the calls that have none
+
+    # route -> the C call that gives positions, the one that gives records
+    _FIND_CALLS = {"literal": ("hufgpu_find_pattern", "hufgpu_find_records"),
+                   "classes": ("hufgpu_find_classes", "hufgpu_find_records_classes"),
+                   "any": ("hufgpu_find_any", "hufgpu_find_records_any")}
+
     @staticmethod
-    def _classes(pattern, ignore_case):
-        """None for the literal route - a bytes-like pattern as it is -, else the classes of the class route"""
-        if isinstance(pattern, (list, tuple)) or ignore_case:
-            return GpuCodec.byte_classes(pattern, ignore_case)
-        return None
+    def _find_route(pattern, ignore_case, delimiters=_NO_RECORDS, select=False):
+        """(route, key, st): which of _FIND_CALLS serves `pattern` - "any" for an AnyOf (and, with `select`, for every
+        pattern: it is the one alternative), "classes" for a list / tuple or with `ignore_case`, else "literal" -, the
+        pattern's part of the C argument list, and the delimiters' byte_set (None when no `delimiters` are given: no records).
+        Raises what find_pattern and find_records raise for a pattern."""
+        if select and not isinstance(pattern, GpuCodec.AnyOf):
+            if isinstance(pattern, str):
+                raise TypeError("a pattern is a bytes-like object or a list / tuple of classes, not a str")
+            pattern = GpuCodec.AnyOf(pattern)
+        alts = classes = None
+        if isinstance(pattern, GpuCodec.AnyOf):
+            alts = GpuCodec.alt_classes(pattern, ignore_case)
+        elif isinstance(pattern, (list, tuple)) or ignore_case:
+            classes = GpuCodec.byte_classes(pattern, ignore_case)      # (raises for a wrong length)
+        st = None if delimiters is GpuCodec._NO_RECORDS else GpuCodec.byte_set(delimiters)
+        if alts is None and classes is None:
+            pattern = bytes(pattern)
+            plen = len(pattern)
+            if not 1 <= plen <= _native.FIND_PATTERN_MAX:
+                raise ValueError(f"a pattern has 1 to {_native.FIND_PATTERN_MAX} bytes, not {plen}")
+            for v in pattern if st is not None else ():
+                if st[v >> 3] >> (v & 7) & 1:
+                    raise ValueError(f"byte value {v} of the pattern is a delimiter: a match lies inside one record")
+            return "literal", (pattern, plen), st
+        rows = classes if alts is None else alts[0]
+        both = rows & np.frombuffer(st, np.uint8) if st is not None else None
+        if both is not None and both.any():
+            row = int(np.flatnonzero(both.any(axis=1))[0])
+            v = int(np.flatnonzero(np.unpackbits(both[row], bitorder="little"))[0])
+            where = f"class {row} of the pattern"
+            if alts is not None:
+                j = int(np.searchsorted(np.cumsum(alts[1]), row, side="right"))
+                where = f"class {row - int(alts[1][:j].sum())} of alternative {j}"
+            raise ValueError(f"{where} holds a delimiter (value {v}): a match lies inside one record")
+        if alts is None:
+            return "classes", (classes.tobytes(), len(classes)), st
+        return "any", (alts[0].tobytes(), alts[1].tobytes(), len(alts[1])), st
 
     def find_pattern(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, max_positions: int = 0,
@@ -505,33 +554,13 @@ class GpuCodec:
         class k for every k.  A bytes-like pattern without `ignore_case` makes the literal call.
         A GpuCodec.AnyOf pattern looks for SEVERAL alternatives in the one walk (hufgpu_find_any): a start at which at least
         one of them lies is reported once; which one is not reported.  `ignore_case` applies to every alternative."""
-        alts = self.alt_classes(pattern, ignore_case) if isinstance(pattern, GpuCodec.AnyOf) else None
-        classes = None if alts is not None else self._classes(pattern, ignore_case)     # (byte_classes raises for a wrong length)
-        if alts is not None:
-            key = (alts[0].tobytes(), alts[1].tobytes(), len(alts[1]))
-        elif classes is None:
-            pattern = bytes(pattern)
-            plen = len(pattern)
-            if not 1 <= plen <= _native.FIND_PATTERN_MAX:
-                raise ValueError(f"a pattern has 1 to {_native.FIND_PATTERN_MAX} bytes, not {plen}")
-            key = (pattern, plen)
-        else:
-            key = (classes.tobytes(), len(classes))
+        route, key, _ = self._find_route(pattern, ignore_case)
         max_positions = int(max_positions)
-        pos = torch.empty(max_positions, dtype=torch.int64, device=self.tdev) if out is None else out
-        assert pos.is_cuda and pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == max_positions and pos.is_contiguous()
-        totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
-        errs = torch.empty(nblocks, dtype=torch.int32, device=self.tdev)
-        counts = torch.empty(nblocks, dtype=torch.int64, device=self.tdev) if block_counts else None
-        call = (self.lib.hufgpu_find_any if alts is not None else
-                self.lib.hufgpu_find_pattern if classes is None else self.lib.hufgpu_find_classes)
-        err = call(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
-                                           offsets.data_ptr() if nblocks else None, nblocks,
-                                           sub_index.data_ptr() if nblocks else None, raw_size, blocksize, *key,
-                                           pos.data_ptr() if max_positions else None, max_positions,
-                                           counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(),
-                                           errs.data_ptr() if nblocks else None,
-                                           _native.RELAXED_TREE if relaxed else _native.STRICT_TREE, self._stream())
+        pos = self._find_buffer(out, max_positions, torch.int64)
+        head, tail, totals, errs, counts = self._find_args(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
+                                                           block_counts, relaxed)
+        call = getattr(self.lib, self._FIND_CALLS[route][0])
+        err = call(*head, *key, pos.data_ptr() if max_positions else None, max_positions, *tail)
         self._check(err, "Failed to enqueue the search")
         return pos, totals, errs, counts
 
@@ -571,75 +600,23 @@ class GpuCodec:
         `list` pattern being its one alternative; with both False the call and what it returns are what they always were.
         `out` may then hold a third buffer, contiguous int64 [max_records], for the numbers."""
         select = bool(invert) or bool(line_numbers)
-        if select and not isinstance(pattern, GpuCodec.AnyOf):
-            if isinstance(pattern, str):
-                raise TypeError("a pattern is a bytes-like object or a list / tuple of classes, not a str")
-            pattern = GpuCodec.AnyOf(pattern)
-        alts = self.alt_classes(pattern, ignore_case) if isinstance(pattern, GpuCodec.AnyOf) else None
-        classes = None if alts is not None else self._classes(pattern, ignore_case)
-        st = self.byte_set(delimiters)
-        if alts is not None:
-            both = alts[0] & np.frombuffer(st, np.uint8)
-            if both.any():
-                row = int(np.flatnonzero(both.any(axis=1))[0])
-                j = int(np.searchsorted(np.cumsum(alts[1]), row, side="right"))
-                k = row - int(alts[1][:j].sum())
-                v = int(np.flatnonzero(np.unpackbits(both[row], bitorder="little"))[0])
-                raise ValueError(f"class {k} of alternative {j} holds a delimiter (value {v}): a match lies inside one record")
-            key = (alts[0].tobytes(), alts[1].tobytes(), len(alts[1]))
-        elif classes is None:
-            pattern = bytes(pattern)
-            plen = len(pattern)
-            if not 1 <= plen <= _native.FIND_PATTERN_MAX:
-                raise ValueError(f"a pattern has 1 to {_native.FIND_PATTERN_MAX} bytes, not {plen}")
-            for v in pattern:
-                if st[v >> 3] >> (v & 7) & 1:
-                    raise ValueError(f"byte value {v} of the pattern is a delimiter: a match lies inside one record")
-            key = (pattern, plen)
-        else:
-            both = classes & np.frombuffer(st, np.uint8)
-            if both.any():
-                k = int(np.flatnonzero(both.any(axis=1))[0])
-                v = int(np.flatnonzero(np.unpackbits(both[k], bitorder="little"))[0])
-                raise ValueError(f"class {k} of the pattern holds a delimiter (value {v}): a match lies inside one record")
-            key = (classes.tobytes(), len(classes))
+        route, key, st = self._find_route(pattern, ignore_case, delimiters, select)
         max_records, max_len = int(max_records), int(max_len)
-        if out is None:
-            out = (torch.empty(max_records, dtype=torch.int64, device=self.tdev),
-                   torch.empty(max_records, dtype=torch.int32, device=self.tdev))
-        numbers = None
-        if line_numbers:
-            numbers = out[2] if len(out) > 2 else torch.empty(max_records, dtype=torch.int64, device=self.tdev)
-            assert (numbers.is_cuda and numbers.dtype == torch.int64 and numbers.dim() == 1 and numbers.numel() == max_records
-                    and numbers.is_contiguous())
-        pos, lens = out[0], out[1]
-        assert pos.is_cuda and pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == max_records and pos.is_contiguous()
-        assert lens.is_cuda and lens.dtype == torch.int32 and lens.dim() == 1 and lens.numel() == max_records and lens.is_contiguous()
-        totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
-        errs = torch.empty(nblocks, dtype=torch.int32, device=self.tdev)
-        counts = torch.empty(nblocks, dtype=torch.int64, device=self.tdev) if block_counts else None
+        out = tuple(out) if out is not None else (None, None)
+        numbers = self._find_buffer(out[2] if len(out) > 2 else None, max_records, torch.int64) if line_numbers else None
+        pos = self._find_buffer(out[0], max_records, torch.int64)
+        lens = self._find_buffer(out[1], max_records, torch.int32)
+        head, tail, totals, errs, counts = self._find_args(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
+                                                           block_counts, relaxed)
+        ptrs = (pos.data_ptr() if max_records else None, lens.data_ptr() if max_records else None)
         if select:
-            err = self.lib.hufgpu_find_records_select(
-                self._ctx, stream.data_ptr() if stream.numel() else None, stream_len, offsets.data_ptr() if nblocks else None, nblocks,
-                sub_index.data_ptr() if nblocks else None, raw_size, blocksize, st, *key,
-                _native.SELECT_INVERT if invert else 0, pos.data_ptr() if max_records else None,
-                lens.data_ptr() if max_records else None, numbers.data_ptr() if line_numbers and max_records else None,
-                max_records, max_len, counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(),
-                errs.data_ptr() if nblocks else None, _native.RELAXED_TREE if relaxed else _native.STRICT_TREE, self._stream())
-            self._check(err, "Failed to enqueue the search")
-            return (pos, lens, totals, errs, counts) + ((numbers,) if line_numbers else ())
-        call = (self.lib.hufgpu_find_records_any if alts is not None else
-                self.lib.hufgpu_find_records if classes is None else self.lib.hufgpu_find_records_classes)
-        err = call(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
-                                           offsets.data_ptr() if nblocks else None, nblocks,
-                                           sub_index.data_ptr() if nblocks else None, raw_size, blocksize, st, *key,
-                                           pos.data_ptr() if max_records else None,
-                                           lens.data_ptr() if max_records else None, max_records, max_len,
-                                           counts.data_ptr() if block_counts and nblocks else None, totals.data_ptr(),
-                                           errs.data_ptr() if nblocks else None,
-                                           _native.RELAXED_TREE if relaxed else _native.STRICT_TREE, self._stream())
+            err = self.lib.hufgpu_find_records_select(*head, st, *key, _native.SELECT_INVERT if invert else 0, *ptrs,
+                                                      numbers.data_ptr() if line_numbers and max_records else None,
+                                                      max_records, max_len, *tail)
+        else:
+            err = getattr(self.lib, self._FIND_CALLS[route][1])(*head, st, *key, *ptrs, max_records, max_len, *tail)
         self._check(err, "Failed to enqueue the search")
-        return pos, lens, totals, errs, counts
+        return (pos, lens, totals, errs, counts) + ((numbers,) if line_numbers else ())
 
     def count_records(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                       sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, delimiters=b"\n",

@@ -1,97 +1,97 @@
-/* find.hpp - the kernels of hufgpu_find_bytes, hufgpu_find_pattern, hufgpu_find_records, of the two class calls and of the
-   two any-of calls (include/huffman_gpu.h): where in the original data the bytes of a set of byte values lie, where a pattern
-   of 1 to 64 bytes - or of 1 to 64 sets of byte values, or any of several such patterns - starts, or which records between
-   delimiters hold it, straight from stream,
-   block index and sub-index; no decoded byte reaches device memory (the pattern calls keep at most 126 edge bytes a tile)
-   and the host only enqueues.  Part of hufgpu_kernels.hip (one translation unit, gfx950 only).
+/* find.hpp - the kernels of the search family (include/huffman_gpu.h): where in the original data the bytes of a set of
+   byte values lie, where a pattern of 1 to 64 bytes - or of 1 to 64 sets of byte values, or any of several such patterns -
+   starts, or which records between delimiters hold it (or do not), straight from stream, block index and sub-index.  No
+   decoded byte reaches device memory (the pattern calls keep at most 126 edge bytes a tile) and the host only enqueues.
+   Part of hufgpu_kernels.hip (one translation unit, gfx950 only).
 
-   Positions are the layout's, as in gather.hpp: block b holds [b B, b B + min(B, raw_size - b B)).
+   Positions are the layout's: block b holds [b B, b B + min(B, raw_size - b B)).  Tile: 2048 symbols; group: a lane's 32.
+   call                            chain of kernels ([..]: only when positions / records are asked for)
+   hufgpu_find_bytes               find_sub                        -> find_scan -> find_finish [-> find_emit]
+   hufgpu_find_pattern             find_pat_sub     -> find_seam     -> find_scan -> find_finish [-> find_emit]
+   hufgpu_find_classes             find_cls_sub     -> find_cls_seam -> find_scan -> find_finish [-> find_emit]
+   hufgpu_find_any                 find_alt_sub     -> find_alt_seam -> find_scan -> find_finish [-> find_emit]
+   hufgpu_find_records             find_rec_sub     -> find_seam     -> RECORDS
+   hufgpu_find_records_classes     find_rec_cls_sub -> find_cls_seam -> RECORDS
+   hufgpu_find_records_any         find_rec_alt_sub -> find_alt_seam -> RECORDS
+   hufgpu_find_records_select      find_rec_alt_sub -> find_alt_seam -> RECORDS with [find_rec_invert] behind find_rec_mark
+                                   and, for the numbers, find_rec_first_bad -> find_rec_emit_no in the place of find_rec_emit
+   RECORDS = find_rec_dscan -> find_rec_mark -> find_scan -> find_finish [-> find_rec_emit]; no seam kernel for 1 byte
 
-     find_sub_kernel     workgroup = one (block, chunk of 65 536 symbols), decode_sub_kernel's geometry with eight waves;
-                         a wave takes the chunk's tiles wave, wave + 8, ...  The header is parsed and its length must
-                         be the layout's, the tables come from dsub_fast_tables (the claimed code lengths checked
-                         against the stream's tree), and EVERY tile of EVERY chunk is the item of sub_tile.hpp, with
-                         its checks: (a) the block's first tile starts at payload bit 0, (b) every group takes
-                         exactly the bits it is said to have and no walk leaves tree or payload, (c) a tile ends where
-                         the next tile of the block is said to start (the last: inside the payload).  The whole block
-                         is walked, so the induction of decode_sub.hpp closes and the caller vouches for nothing: a
-                         block is served exactly or its status says that it is not.
-                         A lane's 32 decoded bytes lie in the wave's 2 KiB of LDS (dsub_tile_slow, the step-by-step
-                         route of sub_tile.hpp: codes of any length, groups of any size) and are tested against the
-                         set - eight words in LDS - there; what leaves the workgroup is ONE 32-bit match mask per
-                         group (a bitmap row per block: block starts need not be 32-aligned raw positions) and the
-                         tile's match count.  A block of one byte value has no sub-index rows: its payload bits are
-                         seen to be 0 and its mask words are all ones or all zeros, the last one cut at the block's
-                         end.
-     find_scan_kernel    the tile counts, gated by their block's status, summed by the two-level / ticket scan of
-                         offsets.hpp (as gather_scan_kernel): a tile's rank among the matches of the served blocks; the
-                         grand total goes to d_totals[0], the blocks that are not served are counted into d_totals[2];
-     find_finish_kernel  per-block counts as differences of the tiles' ranks, and d_totals[1];
-     find_emit_kernel    one wave a tile, a lane a mask word: rank = the tile's + the wave's scan of popcounts, and
-                         b B + 32 g + bit goes to d_pos[rank] for every set bit whose rank is below pos_cap.
+   The walk: find_sub_body, the seven *_sub kernels
+     Workgroup = one (block, chunk of 65 536 symbols), decode_sub_kernel's geometry with eight waves; a wave takes the
+     chunk's tiles wave, wave + 8, ...  The header is parsed and its length must be the layout's, the tables come from
+     dsub_fast_tables (the claimed code lengths checked against the stream's tree), and EVERY tile of EVERY chunk is the
+     item of sub_tile.hpp, with its checks: (a) the block's first tile starts at payload bit 0, (b) every group takes
+     exactly the bits it is said to have and no walk leaves tree or payload, (c) a tile ends where the next tile of the
+     block is said to start (the last: inside the payload).  The whole block is walked, so the induction of
+     decode_sub.hpp closes and the caller vouches for nothing: a block is served exactly or its status says that it is
+     not.  A lane's 32 decoded bytes lie in the wave's 2 KiB of LDS (dsub_tile_slow: codes of any length, groups of any
+     size); what leaves the workgroup is ONE 32-bit match mask per group (a bitmap row per block: block starts need not
+     be 32-aligned raw positions) and the tile's match count.  A block of one byte value has no sub-index rows: its
+     payload bits are seen to be 0 and its mask words are all ones or all zeros, cut where the block or the tile ends.
+       bytes     the lane's 32 bytes against the set, eight words in LDS;
+       pattern   a set bit is a match's START.  A lane tests the starts s among its 32 with s + pattern_len <= the tile's
+                 symbols, reading on into its neighbours' bytes of the wave's slice (find_pat_lane): the matches INSIDE
+                 one tile.  The wave also stores the tile's edges: its first and its last min(symbols, pattern_len - 1)
+                 bytes, in a slot of 2 x 64 bytes a tile;
+       classes   the 2 KiB table (FindClsTable, transposed: a 64-bit set of positions a byte value) lies in LDS in the
+                 place of the 64 pattern bytes, and the lane matcher is a Shift-And automaton over the reversed pattern
+                 (find_cls_lane): one table look-up a byte, 32 + pattern_len - 1 (+ 3) a lane, whatever the data;
+       any-of    the alternatives lie one below the other in the 64 bits of the same table (FindAltArgs); a start is a
+                 byte at which the start bit of ANY alternative is set.  A lane warms up over the longest alternative's
+                 length - 1 bytes, the edges are that many, and the walk sets the starts at which the LONGEST
+                 alternative fits in the tile, whichever alternative lies there;
+       records   next to all that a DELIMITER mask word a group - the lane's 32 bytes against the delimiter set in
+                 LDS - and the tile's delimiter count.
 
-   Any failed check of any chunk raises the block's status to HUF_ERROR_READ_WRITE (atomic max; the statuses are zero
-   when the first kernel starts); nothing is decided on the host.
+   The seams: find_seam_kernel, find_cls_seam_kernel, find_alt_seam_kernel
+     One wave a tile, a lane a start among the tile's last plen - 1 (plen: the pattern's length, the LONGEST one of
+     alternatives): the matches that leave their tile.  find_seam_lane locates the lane's start, find_seam_candidate
+     answers for one pattern whether it lies there, and it holds the layout walk, the only one there is: byte k comes
+     from the tile's own tail slot while it lies in the tile, then from the HEAD of whichever later tile holds it (it
+     lies within plen - 1 of that tile's start), over the layout's tile lengths across chunks and blocks.  A start is
+     dropped when it would end behind raw_size or when any block it touches is not served.  The any-of kernel asks once
+     per alternative - a short one that ends inside the tile included - until one lies there: one bit and one count a
+     start however many do.  find_seam_end ORs the starts into the start tile's mask words and adds them to its count,
+     BEFORE the scan.
 
-   hufgpu_find_pattern: find_pat_sub -> find_seam -> find_scan -> find_finish (-> find_emit); a set bit is a match's START.
-     find_pat_sub_kernel the second instance of find_sub_kernel's body.  A lane tests the starts s among its 32 with
-                         s + pattern_len <= the tile's symbols, reading on into its neighbours' bytes of the wave's own
-                         slice: matches that lie INSIDE one tile.  The wave also stores the tile's edges: its first and
-                         its last min(symbols, pattern_len - 1) bytes, in a slot of 2 x 64 bytes a tile.
-     find_seam_kernel    one wave a tile, a lane a start among the tile's last pattern_len - 1: the matches that leave
-                         their tile.  Byte k of a candidate comes from the tile's own tail while it lies in the tile,
-                         then from the HEAD of whichever later tile holds it (it lies within pattern_len - 1 of that
-                         tile's start), walking the layout's tile lengths across chunks and blocks.  A start is dropped
-                         when it would end behind raw_size or when any block it touches is not served (the statuses
-                         are final: find_pat_sub_kernel has ended); the rest is OR-ed into the start tile's mask words
-                         and added to its count, BEFORE the scan, which with finish and emit runs unchanged.
+   Behind them
+     find_scan_kernel      the tile counts, gated by their block's status, summed by the two-level / ticket scan of
+                           offsets.hpp: a tile's rank among the matches of the served blocks; the grand total goes to
+                           d_totals[0], the blocks that are not served are counted into d_totals[2];
+     find_finish_kernel    per-block counts as differences of the tiles' ranks, and d_totals[1];
+     find_emit_kernel      one wave a tile, a lane a mask word: rank = the tile's + the wave's scan of popcounts, and
+                           b B + 32 g + bit goes to d_pos[rank] for every set bit whose rank is below pos_cap.
 
-   hufgpu_find_records: find_rec_sub -> find_seam -> find_rec_dscan -> find_rec_mark -> find_scan -> find_finish
-   (-> find_rec_emit).  ONE walk of the stream; a record is [s, e) between two delimiters (or byte 0, or
-   raw_size) and is reported once, when it holds a match and every block from the delimiter in front of it to the one that
-   ends it is served.
-     find_rec_sub_kernel   the third instance of find_sub_kernel's body: find_pat_sub_kernel's match mask, edges and counts,
-                           and next to them a DELIMITER mask word a group - the lane's 32 bytes, in registers already,
-                           against the delimiter set in LDS - and the tile's delimiter count.
-     find_seam_kernel      unchanged, on the match mask.
-     find_rec_dscan_kernel the second two-level scan: the delimiters in front of every tile.  A tile of a block that is not
-                           served counts one delimiter that is nowhere.
+   Records.  A record is [s, e) between two delimiters (or byte 0, or raw_size) and is reported once, when it holds a
+   match and every block from the delimiter in front of it to the one that ends it is served.
+     find_rec_dscan_kernel the second two-level scan: the delimiters in front of every tile.
      find_rec_mark_kernel  a wave a tile: every match sets the bit of its record's start in a third mask, by atomic OR -
                            which is what makes a record with many matches one entry.  The start is the bit behind the last
                            delimiter in front of the match: in the lane's own word, else in the tile's words (one ballot
                            and two shuffles a lane), else - for the matches in front of the tile's first delimiter only,
                            so once a TILE - in the nearest tile in front that has a delimiter, found by a binary search in
                            the scanned counts: O(log tiles) reads however far away it is, then a bit scan of that tile's
-                           64 words.  Landing on a virtual delimiter says that the record's start is unknown: the record
-                           is dropped.  The end is looked for in the same way, forward, to drop the records whose end is
-                           unknown BEFORE anything is counted.  One record of 1 GiB with a match in every tile costs two
-                           binary searches a tile, not a walk back to byte 0 a match.
-                           Whoever turns a bit from 0 to 1 counts it for the tile that holds it; find_scan_kernel and
-                           find_finish_kernel run unchanged on those counts: ranks, d_totals[0..2], and d_block_counts by
-                           the block that holds the record's START.
-     find_rec_emit_kernel  find_emit_kernel with a length: the end is the first delimiter behind the start, looked for as
-                           above; pos and min(e - s, clip) go to the record's rank, the cut ones are counted.
+                           64 words.  The end is looked for in the same way, forward, to drop the records whose end is
+                           unknown BEFORE anything is counted.  Whoever turns a bit from 0 to 1 counts it for the tile
+                           that holds it; find_scan_kernel and find_finish_kernel run on those counts: ranks,
+                           d_totals[0..2], and d_block_counts by the block that holds the record's START.
+     find_rec_invert_kernel   the non-empty records of known extent WITHOUT a match: local to its tile, plain stores over
+                           mark's words and counts.
+     find_rec_emit_kernel  find_emit_kernel with a length: the end is the first delimiter behind the start; pos and
+                           min(e - s, clip) go to the record's rank, the cut ones are counted into d_totals[3].  With
+                           find_rec_first_bad_kernel in front, find_rec_emit_no_kernel adds the record's number: the
+                           delimiters in front of it, known while no block in front of the record's is unserved.
 
-   hufgpu_find_classes / hufgpu_find_records_classes: the two routes above with every position of the pattern a SET of
-   byte values; find_scan, find_finish, find_emit, find_rec_dscan, find_rec_mark and find_rec_emit run unchanged.
-     find_cls_sub_kernel, find_rec_cls_sub_kernel
-                           two more instances of find_sub_kernel's body: the same walk, checks, edges, delimiter mask and
-                           counts; the 2 KiB class table (FindClsTable, transposed: a 64-bit set of positions a byte value)
-                           lies in LDS in the place of the 64 pattern bytes, and the lane matcher is a Shift-And automaton
-                           over the reversed pattern (find_cls_lane): one table look-up a byte, 32 + pattern_len - 1 (+ 3)
-                           a lane, whatever the data and however wide the classes.
-     find_cls_seam_kernel  the second instance of find_seam_kernel's body: byte k against class k.
-
-   hufgpu_find_any / hufgpu_find_records_any: the class routes with SEVERAL class patterns - alternatives, grep -e A -e B -
-   in the one walk; a set bit is a start at which at least one of them lies.  Everything behind the seam kernel runs unchanged.
-     find_alt_sub_kernel, find_rec_alt_sub_kernel
-                           the sixth and seventh instance of find_sub_kernel's body.  The alternatives lie one below the other
-                           in the 64 bits of the same table (FindAltArgs) and the automaton's step is the class step; a start
-                           is a byte at which the start bit of ANY alternative is set.  A lane warms up over the longest
-                           alternative's length - 1 bytes, the edges are that many, and the walk sets the starts at which
-                           the LONGEST alternative fits in the tile, whichever alternative lies there.
-     find_alt_seam_kernel  the tile's last (longest length - 1) starts, for every alternative, a short one that ends inside
-                           the tile included: one bit and one count a start however many alternatives lie there. */
+   Invariants
+     Zeroed by the host before the first kernel: the statuses d_block_errs, d_totals, and for the records rbits and rcnt.
+     Every other word that a later kernel reads is written by the walk: the mask word of every group and the count of every
+     tile of every block whose header parses (the rest is never read: every reader looks at the status first).
+     Any failed check of any chunk raises the block's status to HUF_ERROR_READ_WRITE (atomic max, find_raise); nothing is
+     decided on the host.  The statuses are FINAL when the walk kernel has ended: later kernels read them, none writes them.
+     A virtual delimiter: find_rec_dscan_kernel counts ONE delimiter that is nowhere for every tile of a block that is not
+     served.  A look-up that lands on one learns that the record's start or end is unknown, and the record is dropped; a
+     record's number is unknown behind one. */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -153,6 +153,42 @@ __device__ __forceinline__ uint64_t find_block_len(const FindArgs &a, uint64_t b
     return dmin<uint64_t>(a.s.bsize, a.s.raw_size - b * a.s.bsize);
 }
 
+/* tile (b, t) of the layout: its symbols */
+__device__ __forceinline__ uint32_t find_tile_syms(uint64_t blen, uint64_t t) { return (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE); }
+
+/* the bits 0 ... n - 1 of a word; all of them for n >= 32 */
+__device__ __forceinline__ uint32_t find_low_bits(uint32_t n) { return n < 32u ? (1u << n) - 1u : 0xffffffffu; }
+
+/* the block is not served: `who` raises its status */
+__device__ __forceinline__ void find_raise(const FindArgs &a, uint64_t b, bool who)
+{
+    if (who) atomicMax(&a.errs[b], (int32_t)HUFE_RW);
+}
+
+/* a wave = one tile, for the kernels of THREADS threads behind the walk: the wave's index i - no such tile from ntiles on -
+ * and for i < ntiles the tile (b, t) and its block's length.  The exits, and whether the block is served, are the caller's. */
+struct FindTile {
+    uint64_t b, t, blen;                    /* i = b * tpb + t; there is such a tile while t * HUF_SUB_TILE < blen */
+};
+template <uint32_t THREADS>
+__device__ __forceinline__ uint64_t find_tile_index()
+{
+    const uint32_t wave = uni32(threadIdx.x >> 6);
+    return (uint64_t)blockIdx.x * (THREADS / 64) + wave;
+}
+__device__ __forceinline__ FindTile find_tile(const FindArgs &a, uint64_t i)
+{
+    const uint64_t b = i / a.tpb;
+    return {b, i % a.tpb, find_block_len(a, b)};
+}
+
+/* how many of the lane's 32 starts - its first 0 to 32 - are starts at which plen bytes still lie inside the tile's tsym symbols */
+__device__ __forceinline__ uint32_t find_fit(uint32_t plen, uint32_t tsym, uint32_t lane)
+{
+    const uint32_t fit = tsym >= plen ? tsym - plen + 1u : 0u;      /* starts of the tile at which the pattern fits */
+    return fit > 32u * lane ? dmin<uint32_t>(32u, fit - 32u * lane) : 0u;
+}
+
 /* the starts among the lane's 32 at which the pattern lies, all of it inside the tile's tsym symbols: candidates by
  * the first byte (the lane's own words w), each verified word by word against the wave's slice; bytes behind
  * start + plen never reach a comparison, so what is stale behind a short tile does not either */
@@ -166,8 +202,7 @@ __device__ __forceinline__ uint32_t find_pat_lane(const uint32_t *tile_words, co
 #pragma unroll
         for (int i = 0; i < 4; i++) cand |= (uint32_t)(((w[j] >> (8 * i)) & 0xffu) == first) << (4 * j + i);
     }
-    const uint32_t fit = tsym >= plen ? tsym - plen + 1u : 0u;      /* starts of the tile at which the pattern fits */
-    const uint32_t mine = fit > 32u * lane ? dmin<uint32_t>(32u, fit - 32u * lane) : 0u;
+    const uint32_t mine = find_fit(plen, tsym, lane);
     cand = mine == 0u ? 0u : (mine < 32u ? cand & ((1u << mine) - 1u) : cand);
     const uint32_t nw = (plen + 3u) >> 2;
     const uint32_t last = (plen & 3u) ? (1u << (8u * (plen & 3u))) - 1u : 0xffffffffu;
@@ -270,16 +305,15 @@ __device__ __forceinline__ uint32_t find_cls_lane(const uint32_t *tile_words, co
             else m |= (hi >> 31) << (4 * j + i);
         }
     }
-    const uint32_t fit = tsym >= plen ? tsym - plen + 1u : 0u;      /* starts of the tile at which the pattern fits */
-    const uint32_t mine = fit > 32u * lane ? dmin<uint32_t>(32u, fit - 32u * lane) : 0u;
+    const uint32_t mine = find_fit(plen, tsym, lane);
     return mine == 0u ? 0u : (mine < 32u ? m & ((1u << mine) - 1u) : m);
 }
 
-/* the body of find_sub_kernel (PAT = false: p is not looked at), of find_pat_sub_kernel and of find_rec_sub_kernel (PAT
- * and REC: the pattern's work, and r's delimiter masks and counts next to it), and with CLS of find_cls_sub_kernel and
- * find_rec_cls_sub_kernel: the same walk, checks, edges, delimiter masks and counts with the class table ct in the place of
- * the pattern's bytes; with ALT of find_alt_sub_kernel and find_rec_alt_sub_kernel: ct holds several alternatives, alt
- * says where they start, and p->plen is the longest one's length; grid nblocks * cpb */
+/* the body of the seven walk kernels, grid nblocks * cpb, in one piece: the key into LDS, the header, then either the
+ * branch of a block of one byte value or the tables and the loop over the chunk's tiles.  PAT = false: the bytes' call, p
+ * is not looked at.  REC: r's delimiter masks and counts next to the pattern's work.  CLS: the class table
+ * ct in the place of the pattern's bytes.  ALT: ct holds several alternatives, alt says where they start, and p->plen is
+ * the longest one's length. */
 template <bool PAT, bool REC = false, bool CLS = false, bool ALT = false>
 __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatArgs *p, const FindRecArgs *r = nullptr, const FindClsTable *ct = nullptr,
                                               [[maybe_unused]] const FindAltArgs *alt = nullptr)
@@ -315,20 +349,15 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
     __syncthreads();
     /* ---- the header - and its length must be the layout's ---- */
     BlockHeader h;
-    if (parse_block_header(a.s.stream, a.s.stream_len, a.s.offsets[b], a.s.offsets[b + 1], a.s.max_tree, h) != HUFE_OK || h.block_len != blen) {
-        if (threadIdx.x == 0) atomicMax(&a.errs[b], (int32_t)HUFE_RW);
-        return;
-    }
+    if (parse_block_header(a.s.stream, a.s.stream_len, a.s.offsets[b], a.s.offsets[b + 1], a.s.max_tree, h) != HUFE_OK || h.block_len != blen)
+        return find_raise(a, b, threadIdx.x == 0);
     const SubBlockView v = sub_block_view(h, a.s.sub, b);
     uint32_t *row = a.bitmap + b * a.wpb;
     uint32_t *trow = a.tcnt + b * a.tpb;
     const int leaf = h.tree_len == 5 ? single_leaf_symbol(h.tree) : -1;
     if (leaf >= 0) {
         /* ---- one byte value: every symbol is a 0 bit (decode.hpp); the chunk's bits are seen to be 0 ---- */
-        if (blen > v.pay_bits) {
-            if (threadIdx.x == 0) atomicMax(&a.errs[b], (int32_t)HUFE_RW);
-            return;
-        }
+        if (blen > v.pay_bits) return find_raise(a, b, threadIdx.x == 0);
         bool match;
         uint32_t plen = 1;
         if constexpr (PAT) {
@@ -361,15 +390,15 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
             uint32_t x = load_be32(v.pay, 4ull * g, v.pay_bytes);
             if (nsym < 32u) x &= 0xffffffffu << (32u - nsym);
             set |= x != 0u;
-            if constexpr (REC) r->dbits[b * a.wpb + g] = delim ? (nsym < 32u ? (1u << nsym) - 1u : 0xffffffffu) : 0u;
+            if constexpr (REC) r->dbits[b * a.wpb + g] = delim ? find_low_bits(nsym) : 0u;
             if constexpr (PAT) {                                    /* the starts of this group at which the pattern fits in the tile */
                 const uint64_t tend = dmin<uint64_t>(blen, (g / 64u + 1u) * HUF_SUB_TILE), s0 = 32ull * g + plen;
                 nsym = s0 > tend ? 0u : (uint32_t)dmin<uint64_t>(DSUB_SPL, tend - s0 + 1u);
             }
-            row[g] = match ? (nsym < 32u ? (1u << nsym) - 1u : 0xffffffffu) : 0u;
+            row[g] = match ? find_low_bits(nsym) : 0u;
         }
         for (uint64_t t = sym0 / HUF_SUB_TILE + threadIdx.x; t * HUF_SUB_TILE < sym1; t += FIND_THREADS) {
-            const uint32_t tsym = (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE);
+            const uint32_t tsym = find_tile_syms(blen, t);
             trow[t] = match ? (tsym >= plen ? tsym - plen + 1u : 0u) : 0u;
             if constexpr (REC) r->dcnt[b * a.tpb + t] = delim ? tsym : 0u;
         }
@@ -377,20 +406,16 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
             const uint64_t t0 = sym0 / HUF_SUB_TILE, nt = (sym1 - sym0 + HUF_SUB_TILE - 1) / HUF_SUB_TILE;
             for (uint64_t i = threadIdx.x; i < nt * FIND_EDGE_SLOT; i += FIND_THREADS) {
                 const uint64_t t = t0 + i / FIND_EDGE_SLOT;
-                const uint32_t tsym = (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE);
+                const uint32_t tsym = find_tile_syms(blen, t);
                 if (((uint32_t)i & 63u) < dmin<uint32_t>(tsym, plen - 1u))
                     p->edges[(b * a.tpb + t0) * FIND_EDGE_SLOT + i] = (uint8_t)leaf;
             }
         }
-        if (set) atomicMax(&a.errs[b], (int32_t)HUFE_RW);
-        return;
+        return find_raise(a, b, set);
     }
     /* ---- the block's tables ---- */
     const DsubTreeWords tw = dsub_tree_request<FIND_THREADS>(h.tree, h.tree_len, a.s.sub.lens + b * HUF_NSYM);
-    if (!dsub_fast_tables<FIND_THREADS>(sh, h.tree_len, tw)) {      /* (workgroup-uniform) */
-        if (threadIdx.x == 0) atomicMax(&a.errs[b], (int32_t)HUFE_RW);
-        return;
-    }
+    if (!dsub_fast_tables<FIND_THREADS>(sh, h.tree_len, tw)) return find_raise(a, b, threadIdx.x == 0);     /* (workgroup-uniform) */
     uint32_t *tile_words = s_tile[wave];
     uint32_t *top = DsubLds<FIND_THREADS>::slice(sh, (int)wave) + (SH::SLICE_WORDS - 1u);
     bool good = true;
@@ -411,7 +436,7 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
         const uint32_t w[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
         uint32_t m = 0;
         if constexpr (PAT) {
-            const uint32_t tsym = (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE), plen = p->plen;
+            const uint32_t tsym = find_tile_syms(blen, t), plen = p->plen;
             if constexpr (ALT) m = find_cls_lane<true>(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane, alt->starts[0], alt->starts[1]);
             else if constexpr (CLS) m = find_cls_lane(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane);
             else m = find_pat_lane(tile_words, w, s_set, plen, tsym, lane);         /* (0 for a lane without symbols) */
@@ -437,7 +462,7 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
                 }
                 d = nsym == 0u ? 0u : (nsym < 32u ? d & ((1u << nsym) - 1u) : d);
                 if (nsym != 0u) r->dbits[b * a.wpb + t * 64u + lane] = d;
-                const uint32_t dc = wave_lane_u32(wave_incl_scan_u32((uint32_t)__popc(d)), 63);
+                const uint32_t dc = wave_total_u32((uint32_t)__popc(d));
                 if (lane == 0) r->dcnt[b * a.tpb + t] = dc;
             }
         } else {
@@ -452,10 +477,10 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
             m = nsym == 0u ? 0u : (nsym < 32u ? m & ((1u << nsym) - 1u) : m);    /* (bytes behind a short group are stale) */
         }
         if (nsym != 0u) row[t * 64u + lane] = m;
-        const uint32_t cnt = wave_lane_u32(wave_incl_scan_u32((uint32_t)__popc(m)), 63);
+        const uint32_t cnt = wave_total_u32((uint32_t)__popc(m));
         if (lane == 0) trow[t] = cnt;
     }
-    if (!good && lane == 0) atomicMax(&a.errs[b], (int32_t)HUFE_RW);
+    find_raise(a, b, !good && lane == 0);
 }
 
 __global__ __launch_bounds__(FIND_THREADS) void find_sub_kernel(FindArgs a) { find_sub_body<false>(a, nullptr); }
@@ -466,150 +491,129 @@ __global__ __launch_bounds__(FIND_THREADS) void find_rec_cls_sub_kernel(FindClsA
 __global__ __launch_bounds__(FIND_THREADS) void find_alt_sub_kernel(FindAltArgs a) { find_sub_body<true, false, true, true>(a.r.p.f, &a.r.p, nullptr, &a.t, &a); }
 __global__ __launch_bounds__(FIND_THREADS) void find_rec_alt_sub_kernel(FindAltArgs a) { find_sub_body<true, true, true, true>(a.r.p.f, &a.r.p, &a.r, &a.t, &a); }
 
-/* tile (b, t) of the layout: its symbols */
-__device__ __forceinline__ uint32_t find_tile_syms(uint64_t blen, uint64_t t) { return (uint32_t)dmin<uint64_t>(HUF_SUB_TILE, blen - t * HUF_SUB_TILE); }
+/* ---- the seams: the matches that leave their tile (launched for plen >= 2 only) ---------------------------------------- */
 
-/* a wave = one tile, a lane = one of its last plen - 1 starts (launched for plen >= 2 only); CLS: byte k is tested
- * against class k - bit 63 - k of its entry of the table c - and not against the pattern's byte k */
+/* a seam kernel's lane: the tile, and one of its last ne = min(symbols, plen - 1) starts - s in the tile, pos in the data.
+ * The lanes from ne on have no start. */
+struct FindSeam {
+    uint64_t i;
+    FindTile k;
+    uint32_t lane, ne, s;
+    uint64_t pos;
+};
+
+/* the pattern (or CLS: the class table c) into the workgroup's s_key */
+template <bool CLS>
+__device__ __forceinline__ void find_seam_key(const FindPatArgs &pa, const FindClsTable *c, uint32_t *s_key)
+{
+    if constexpr (CLS) {
+        for (uint32_t i = threadIdx.x; i < FIND_CLS_WORDS; i += FIND_SEAM_THREADS) s_key[i] = c->m[i >> 1][i & 1u];
+    } else {
+        if (threadIdx.x < FIND_PAT_MAX / 4) s_key[threadIdx.x] = pa.pat[threadIdx.x];
+    }
+    __syncthreads();
+}
+
+/* the lane's start in tile i = k (which the layout has, in a block that is served: another one counts nothing) */
+__device__ __forceinline__ FindSeam find_seam_lane(const FindPatArgs &pa, uint64_t i, const FindTile &k)
+{
+    const uint32_t lane = (uint32_t)lane_id(), tsym = find_tile_syms(k.blen, k.t);
+    const uint32_t ne = dmin<uint32_t>(tsym, pa.plen - 1u), s = tsym - ne + lane;
+    return {i, k, lane, ne, s, k.b * pa.f.s.bsize + k.t * HUF_SUB_TILE + s};
+}
+
+/* Do the len bytes from the lane's start (lane < ne) match - the pattern's bytes in s_key, or CLS: byte k against the bit
+ * hi - k of its entry of the table in s_key - without ending behind raw_size, and is every block they touch served?  Byte k
+ * comes from the tile's own tail slot, then from the heads of the tiles behind: THE walk over the layout's tile lengths. */
+template <bool CLS>
+__device__ __forceinline__ bool find_seam_candidate(const FindPatArgs &pa, const uint32_t *s_key, const FindSeam &m, uint32_t len,
+                                                    [[maybe_unused]] uint32_t hi = 63u)
+{
+    const FindArgs &a = pa.f;
+    if (m.pos + len > a.s.raw_size) return false;
+    const uint8_t *e = pa.edges + m.i * FIND_EDGE_SLOT + 64u;     /* the own tail, then the heads of the tiles behind */
+    uint64_t cb = m.k.b, ct = m.k.t, cblen = m.k.blen;
+    uint32_t off = m.lane, csym = m.ne;                             /* byte k is e[off]; csym bytes there belong to this tile */
+    [[maybe_unused]] uint32_t kbit = 1u << (hi & 31u), khalf = (hi >> 5) & 1u;      /* CLS: class k is bit kbit of half khalf of a table entry */
+    for (uint32_t k = 0; k < len; k++, off++) {
+        while (off == csym) {                                       /* on into the next tile of the layout */
+            if ((ct + 1) * HUF_SUB_TILE < cblen) {
+                ct++;
+            } else {
+                cb++;                                               /* (pos + len <= raw_size: there is such a block) */
+                ct = 0;
+                cblen = find_block_len(a, cb);
+                if (a.errs[cb] != HUFE_OK) return false;
+            }
+            e = pa.edges + (cb * a.tpb + ct) * FIND_EDGE_SLOT;
+            off = 0;
+            csym = find_tile_syms(cblen, ct);
+        }
+        if constexpr (CLS) {
+            if ((s_key[2u * e[off] + khalf] & kbit) == 0u) return false;
+            kbit >>= 1;                                             /* class k + 1: the next bit down, shifted by a constant */
+            if (kbit == 0u) {
+                kbit = 0x80000000u;
+                khalf = 0u;
+            }
+        } else {
+            if (e[off] != ((s_key[k >> 2] >> (8u * (k & 3u))) & 0xffu)) return false;
+        }
+    }
+    return true;
+}
+
+/* the starts that were found, into the tile's mask words and its count: before the scan */
+__device__ __forceinline__ void find_seam_end(const FindArgs &a, const FindSeam &m, bool hit)
+{
+    if (hit) atomicOr(&a.bitmap[m.k.b * a.wpb + m.k.t * 64u + (m.s >> 5)], 1u << (m.s & 31u));
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(hit));
+    if (m.lane == 0 && cnt != 0u) a.tcnt[m.i] += cnt;
+}
+
 template <bool CLS>
 __device__ __forceinline__ void find_seam_body(const FindPatArgs &pa, const FindClsTable *c = nullptr)
 {
-    __shared__ uint32_t s_pat[CLS ? FIND_CLS_WORDS : FIND_PAT_MAX / 4];
-    const FindArgs &a = pa.f;
-    if constexpr (CLS) {
-        for (uint32_t i = threadIdx.x; i < FIND_CLS_WORDS; i += FIND_SEAM_THREADS) s_pat[i] = c->m[i >> 1][i & 1u];
-    } else {
-        if (threadIdx.x < FIND_PAT_MAX / 4) s_pat[threadIdx.x] = pa.pat[threadIdx.x];
-    }
-    __syncthreads();
-    const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
-    const uint64_t i = (uint64_t)blockIdx.x * (FIND_SEAM_THREADS / 64) + wave;
-    if (i >= a.ntiles) return;
-    const uint64_t b = i / a.tpb, t = i % a.tpb;
-    const uint64_t blen = find_block_len(a, b);
-    if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK) return;  /* (a block that is not served counts nothing) */
-    const uint32_t plen = pa.plen, tsym = find_tile_syms(blen, t);
-    const uint32_t ne = dmin<uint32_t>(tsym, plen - 1u);
-    const uint32_t s = tsym - ne + lane;                            /* the lane's start in the tile */
-    const uint64_t pos = b * a.s.bsize + t * HUF_SUB_TILE + s;
-    bool same = lane < ne && pos + plen <= a.s.raw_size;
-    if (same) {
-        const uint8_t *e = pa.edges + i * FIND_EDGE_SLOT + 64u;     /* the own tail, then the heads of the tiles behind */
-        uint64_t cb = b, ct = t, cblen = blen;
-        uint32_t off = lane, csym = ne;                             /* byte k is e[off]; csym bytes there belong to this tile */
-        [[maybe_unused]] uint32_t kbit = 0x80000000u, khalf = 1u;   /* CLS: class k is bit kbit of half khalf of a table entry */
-        for (uint32_t k = 0; k < plen; k++, off++) {
-            while (off == csym) {                                   /* on into the next tile of the layout */
-                if ((ct + 1) * HUF_SUB_TILE < cblen) {
-                    ct++;
-                } else {
-                    cb++;                                           /* (pos + plen <= raw_size: there is such a block) */
-                    ct = 0;
-                    cblen = find_block_len(a, cb);
-                    if (a.errs[cb] != HUFE_OK) {
-                        same = false;
-                        break;
-                    }
-                }
-                e = pa.edges + (cb * a.tpb + ct) * FIND_EDGE_SLOT;
-                off = 0;
-                csym = find_tile_syms(cblen, ct);
-            }
-            bool fits;
-            if constexpr (CLS) fits = same && (s_pat[2u * e[off] + khalf] & kbit) != 0u;
-            else fits = same && e[off] == ((s_pat[k >> 2] >> (8u * (k & 3u))) & 0xffu);
-            if (!fits) {
-                same = false;
-                break;
-            }
-            if constexpr (CLS) {                                    /* class k + 1: the next bit down, shifted by a constant */
-                kbit >>= 1;
-                if (kbit == 0u) {
-                    kbit = 0x80000000u;
-                    khalf = 0u;
-                }
-            }
-        }
-    }
-    if (same) atomicOr(&a.bitmap[b * a.wpb + t * 64u + (s >> 5)], 1u << (s & 31u));
-    const uint32_t cnt = (uint32_t)__popcll(__ballot(same));
-    if (lane == 0 && cnt != 0u) a.tcnt[i] += cnt;
+    __shared__ uint32_t s_key[CLS ? FIND_CLS_WORDS : FIND_PAT_MAX / 4];
+    find_seam_key<CLS>(pa, c, s_key);
+    const uint64_t i = find_tile_index<FIND_SEAM_THREADS>();
+    if (i >= pa.f.ntiles) return;
+    const FindTile tl = find_tile(pa.f, i);
+    if (tl.t * HUF_SUB_TILE >= tl.blen || pa.f.errs[tl.b] != HUFE_OK) return;
+    const FindSeam m = find_seam_lane(pa, i, tl);
+    find_seam_end(pa.f, m, m.lane < m.ne && find_seam_candidate<CLS>(pa, s_key, m, pa.plen));
 }
 
 __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_seam_kernel(FindPatArgs pa) { find_seam_body<false>(pa); }
 __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_cls_seam_kernel(FindClsArgs a) { find_seam_body<true>(a.r.p, &a.t); }
 
-/* hufgpu_find_any: a wave = one tile, a lane = one of its last plen - 1 starts, plen the LONGEST alternative's length
- * (launched for plen >= 2 only), as find_seam_body - and these starts are this kernel's for EVERY alternative, a short one
- * that ends inside the tile included: the tile's tail slot holds all the bytes it needs.  The wave goes through the
- * alternatives together (hi_j and len_j are the wave's, in scalar registers: class k of alternative j is bit hi_j - k, a
- * mask that walks down by a constant shift); a lane takes part until one alternative fits, each with its own
- * pos + len_j <= raw_size and its own walk over served blocks, and then sets ONE bit and counts ONE match. */
+/* hufgpu_find_any: plen is the LONGEST alternative's length, and the tile's last plen - 1 starts are this kernel's for
+ * EVERY alternative, a short one that ends inside the tile included: the tile's tail slot holds all the bytes it needs.
+ * The wave goes through the alternatives together (hi_j and len_j are the wave's, in scalar registers); a lane takes part
+ * until one alternative lies at its start, and then sets ONE bit and counts ONE match. */
 __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_alt_seam_kernel(FindAltArgs aa)
 {
-    __shared__ uint32_t s_pat[FIND_CLS_WORDS];
+    __shared__ uint32_t s_key[FIND_CLS_WORDS];
     __shared__ uint32_t s_hl[FIND_PAT_MAX];
     const FindPatArgs &pa = aa.r.p;
-    const FindArgs &a = pa.f;
-    for (uint32_t i = threadIdx.x; i < FIND_CLS_WORDS; i += FIND_SEAM_THREADS) s_pat[i] = aa.t.m[i >> 1][i & 1u];
     if (threadIdx.x < FIND_PAT_MAX) s_hl[threadIdx.x] = aa.hl[threadIdx.x];
-    __syncthreads();
-    const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
-    const uint64_t i = (uint64_t)blockIdx.x * (FIND_SEAM_THREADS / 64) + wave;
-    if (i >= a.ntiles) return;
-    const uint64_t b = i / a.tpb, t = i % a.tpb;
-    const uint64_t blen = find_block_len(a, b);
-    if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK) return;  /* (a block that is not served counts nothing) */
-    const uint32_t plen = pa.plen, tsym = find_tile_syms(blen, t);
-    const uint32_t ne = dmin<uint32_t>(tsym, plen - 1u);
-    const uint32_t s = tsym - ne + lane;                            /* the lane's start in the tile */
-    const uint64_t pos = b * a.s.bsize + t * HUF_SUB_TILE + s;
+    find_seam_key<true>(pa, &aa.t, s_key);
+    const uint64_t i = find_tile_index<FIND_SEAM_THREADS>();
+    if (i >= pa.f.ntiles) return;
+    const FindTile tl = find_tile(pa.f, i);
+    if (tl.t * HUF_SUB_TILE >= tl.blen || pa.f.errs[tl.b] != HUFE_OK) return;
+    const FindSeam m = find_seam_lane(pa, i, tl);
     /* the byte AT the start, read once: an alternative whose first class does not hold it starts no walk, so a lane
      * that no alternative can start at - nearly every lane - costs this one load however many alternatives there are */
-    const uint32_t at = lane < ne ? pa.edges[i * FIND_EDGE_SLOT + 64u + lane] : 0u;
-    const uint32_t m0 = s_pat[2u * at], m1 = s_pat[2u * at + 1u];
+    const uint32_t at = m.lane < m.ne ? pa.edges[m.i * FIND_EDGE_SLOT + 64u + m.lane] : 0u;
+    const uint32_t m0 = s_key[2u * at], m1 = s_key[2u * at + 1u];
     bool hit = false;
     for (uint32_t j = 0; j < aa.n_alts; j++) {
-        const uint32_t hl = uni32(s_hl[j]), len = hl >> 8;
-        uint32_t kbit = 1u << (hl & 31u), khalf = (hl >> 5) & 1u;   /* class k is bit kbit of half khalf of a table entry */
-        bool same = lane < ne && !hit && ((khalf ? m1 : m0) & kbit) != 0u && pos + len <= a.s.raw_size;
-        if (same) {
-            const uint8_t *e = pa.edges + i * FIND_EDGE_SLOT + 64u; /* the own tail, then the heads of the tiles behind */
-            uint64_t cb = b, ct = t, cblen = blen;
-            uint32_t off = lane, csym = ne;                         /* byte k is e[off]; csym bytes there belong to this tile */
-            for (uint32_t k = 0; k < len; k++, off++) {
-                while (off == csym) {                               /* on into the next tile of the layout */
-                    if ((ct + 1) * HUF_SUB_TILE < cblen) {
-                        ct++;
-                    } else {
-                        cb++;                                       /* (pos + len <= raw_size: there is such a block) */
-                        ct = 0;
-                        cblen = find_block_len(a, cb);
-                        if (a.errs[cb] != HUFE_OK) {
-                            same = false;
-                            break;
-                        }
-                    }
-                    e = pa.edges + (cb * a.tpb + ct) * FIND_EDGE_SLOT;
-                    off = 0;
-                    csym = find_tile_syms(cblen, ct);
-                }
-                if (!same || (s_pat[2u * e[off] + khalf] & kbit) == 0u) {
-                    same = false;
-                    break;
-                }
-                kbit >>= 1;                                         /* class k + 1: the next bit down */
-                if (kbit == 0u) {
-                    kbit = 0x80000000u;
-                    khalf = 0u;
-                }
-            }
-        }
-        hit |= same;
+        const uint32_t hl = uni32(s_hl[j]), hi = hl & 63u;
+        if (m.lane < m.ne && !hit && ((((hi >> 5) ? m1 : m0) >> (hi & 31u)) & 1u) != 0u)
+            hit = find_seam_candidate<true>(pa, s_key, m, hl >> 8, hi);
     }
-    if (hit) atomicOr(&a.bitmap[b * a.wpb + t * 64u + (s >> 5)], 1u << (s & 31u));
-    const uint32_t cnt = (uint32_t)__popcll(__ballot(hit));
-    if (lane == 0 && cnt != 0u) a.tcnt[i] += cnt;
+    find_seam_end(pa.f, m, hit);
 }
 
 /* a workgroup = one SCAN_GROUP of tiles, as gather_scan_kernel sums the part counts */
@@ -640,11 +644,10 @@ __global__ __launch_bounds__(256) void find_finish_kernel(FindArgs a)
 /* a wave = one tile */
 __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_emit_kernel(FindArgs a)
 {
-    const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
-    const uint64_t i = (uint64_t)blockIdx.x * (FIND_EMIT_THREADS / 64) + wave;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t i = find_tile_index<FIND_EMIT_THREADS>();
     if (i >= a.ntiles) return;
-    const uint64_t b = i / a.tpb, t = i % a.tpb;
-    const uint64_t blen = find_block_len(a, b);
+    const auto [b, t, blen] = find_tile(a, i);
     if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK) return;
     const uint64_t rank0 = two_level_prefix(a.scan, i);
     if (rank0 >= a.pos_cap) return;
@@ -787,11 +790,10 @@ __device__ __forceinline__ FindRecLane find_rec_lane(uint32_t d, uint32_t lane)
 __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_mark_kernel(FindRecArgs ra)
 {
     const FindArgs &a = ra.p.f;
-    const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
-    const uint64_t i = (uint64_t)blockIdx.x * (FIND_EMIT_THREADS / 64) + wave;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t i = find_tile_index<FIND_EMIT_THREADS>();
     if (i >= a.ntiles) return;
-    const uint64_t b = i / a.tpb, t = i % a.tpb;
-    const uint64_t blen = find_block_len(a, b);
+    const auto [b, t, blen] = find_tile(a, i);
     if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK || a.tcnt[i] == 0u) return;
     const uint64_t g = t * 64u + lane;
     const uint32_t m = g * DSUB_SPL < blen ? a.bitmap[b * a.wpb + g] : 0u;
@@ -820,7 +822,7 @@ __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_mark_kernel(FindRe
             fresh += (atomicOr(&row[s >> 5], 1u << (s & 31u)) & (1u << (s & 31u))) == 0u;
         }
     }
-    const uint32_t cnt = wave_lane_u32(wave_incl_scan_u32(fresh), 63);
+    const uint32_t cnt = wave_total_u32(fresh);
     if (lane == 0 && cnt != 0u) atomicAdd(&ra.rcnt[i], cnt);
 }
 
@@ -858,11 +860,10 @@ __global__ __launch_bounds__(256) void find_rec_first_bad_kernel(FindSelArgs sa)
 __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_invert_kernel(FindRecArgs ra)
 {
     const FindArgs &a = ra.p.f;
-    const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
-    const uint64_t i = (uint64_t)blockIdx.x * (FIND_EMIT_THREADS / 64) + wave;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t i = find_tile_index<FIND_EMIT_THREADS>();
     if (i >= a.ntiles) return;
-    const uint64_t b = i / a.tpb, t = i % a.tpb;
-    const uint64_t blen = find_block_len(a, b);
+    const auto [b, t, blen] = find_tile(a, i);
     if (t * HUF_SUB_TILE >= blen) return;
     const uint64_t g = t * 64u + lane;
     const bool inside = g * DSUB_SPL < blen;
@@ -895,7 +896,7 @@ __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_invert_kernel(Find
     if (__ballot(tail) != 0 && find_rec_end_behind(ra, i, lane) == FIND_REC_OPEN && tail) cand &= ~k.tail;
     const uint32_t n = cand & ~r;
     if (inside) *word = n;
-    const uint32_t cnt = wave_lane_u32(wave_incl_scan_u32((uint32_t)__popc(n)), 63);
+    const uint32_t cnt = wave_total_u32((uint32_t)__popc(n));
     if (lane == 0) ra.rcnt[i] = cnt;
 }
 
@@ -910,11 +911,10 @@ template <bool NO>
 __device__ __forceinline__ void find_rec_emit_body(const FindRecArgs &ra, [[maybe_unused]] const FindSelArgs *sa = nullptr)
 {
     const FindArgs &a = ra.p.f;
-    const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
-    const uint64_t i = (uint64_t)blockIdx.x * (FIND_EMIT_THREADS / 64) + wave;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t i = find_tile_index<FIND_EMIT_THREADS>();
     if (i >= a.ntiles) return;
-    const uint64_t b = i / a.tpb, t = i % a.tpb;
-    const uint64_t blen = find_block_len(a, b);
+    const auto [b, t, blen] = find_tile(a, i);
     if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK || ra.rcnt[i] == 0u) return;
     const uint64_t rank0 = two_level_prefix(a.scan, i);
     if (rank0 >= a.pos_cap) return;
@@ -946,7 +946,7 @@ __device__ __forceinline__ void find_rec_emit_body(const FindRecArgs &ra, [[mayb
         cut += n > ra.clip;
         rank++;
     }
-    const uint32_t cuts = wave_lane_u32(wave_incl_scan_u32(cut), 63);
+    const uint32_t cuts = wave_total_u32(cut);
     if (lane == 0 && cuts != 0u) atomicAdd((unsigned long long *)&a.totals[3], (unsigned long long)cuts);
 }
 

@@ -140,6 +140,9 @@ __device__ __forceinline__ uint32_t wave_lane_u32(uint32_t v, uint32_t uniform_l
     return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)uniform_lane);
 }
 
+/* the sum of v over the wave, in every lane */
+__device__ __forceinline__ uint32_t wave_total_u32(uint32_t v) { return wave_lane_u32(wave_incl_scan_u32(v), 63); }
+
 /* Exclusive prefix sum of 32-bit values over the workgroup: DPP inside the waves, one LDS round
  * across them.  s_part needs THREADS/64 words. */
 template <int THREADS>
