@@ -580,6 +580,8 @@ int hufgpu_find_records_any(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t st
  *                   plain one or the inverted one, and a record whose extent is not known lies in neither.  EMPTY records
  *                   are never reported - grep -v prints empty lines, this call does not: an empty record has no byte of
  *                   its own, a final delimiter starts no record, and hufgpu_gather() has nothing to fetch for it.
+ *                   (hufgpu_find_records_context(): the distances COUNT empty records, as grep counts empty lines; they are
+ *                   still never reported, and as they are not in the inverted S they get no context of their own.)
  *                   d_totals[0..3], d_block_counts, rec_cap and max_len mean for the selected records what they mean for
  *                   the matching ones.
  *   d_rec_no      : optional, NULL or rec_cap entries (it may be NULL with rec_cap > 0, and is not looked at with
@@ -604,6 +606,54 @@ int hufgpu_find_records_select(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t
                                uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no, uint64_t rec_cap, uint32_t max_len,
                                uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
                                uint32_t flags, void *stream);
+
+/*
+ * FIND RECORDS, WITH CONTEXT: grep -A / -B / -C.  hufgpu_find_records_select() reports the selected records; this call
+ * reports the records AROUND them as well (grep -C 3 ERROR, grep -B 5 panic, grep -A 20 'stack trace'), from the masks
+ * that the one walk has written anyway: the delimiters, the selected records' starts, and the scanned delimiter counts
+ * that give every start its number.  Context is a dilation of the selected records' mask in record-NUMBER space: one more
+ * kernel over the masks, no second walk, no other matcher, and what comes back goes into hufgpu_gather() unchanged.  There
+ * is no CPU path.
+ *
+ * The contract is hufgpu_find_records_select()'s word for word - the pattern forms, delim_set, `select` and its check first
+ * of all, d_rec_no, rec_cap, max_len, d_totals[0..3], d_block_counts, d_block_errs, the known-extent rule, flags,
+ * nblocks = 0, enqueue-only without a host write or a wait, every argument error (worded "find_records_context: ...") -
+ * but for this:
+ *
+ *   S             : the records that hufgpu_find_records_select() reports for the same arguments: non-empty, extent known,
+ *                   holding a match - or holding none under HUFGPU_SELECT_INVERT.  A record's NUMBER no(r) is the count of
+ *                   delimiter bytes in front of its start; empty records count.
+ *   before, after : any uint32_t.  The call reports, each once and ascending, every record of S and every non-empty record
+ *                   c whose extent is known for which S holds an m with no(m) - before <= no(c) < no(m) or
+ *                   no(m) < no(c) <= no(m) + after - and that only when every block that holds a byte from the start of the
+ *                   earlier of the two records to the end of the later one is served.  A block that is not served hides its
+ *                   delimiters, so no distance is measured across it: a record is left out on doubt, never reported wrongly.
+ *                   S itself is always reported in full: the answer contains the select call's for any before, after.
+ *                   0xffffffff in both reports every non-empty record of known extent, whenever S is not empty and every
+ *                   block is served.
+ *   EMPTY records : distances count them, as grep counts empty lines, but they are never reported (hufgpu_gather() has
+ *                   nothing to fetch for them), and under HUFGPU_SELECT_INVERT they are not in S either, so they get no
+ *                   context of their own: the records around an empty line are not reported for its sake.
+ *   d_rec_sel     : optional, NULL or rec_cap bytes (not looked at with rec_cap = 0), written as d_rec_pos is: 1 when record
+ *                   i is in S, 0 when it is context only - grep's ':' and '-'.  grep's "--" between two groups follows from a
+ *                   gap in d_rec_no.
+ *   d_totals[0..3], d_block_counts, rec_cap and max_len mean for the REPORTED records what they mean for the selected ones.
+ *
+ * The identity: before = after = 0 and d_rec_sel = NULL enqueue exactly what hufgpu_find_records_select() enqueues, and the
+ * eight older calls launch what they always did.  The cost does not follow before or after: a tile of 2048 bytes costs at
+ * most three look-ups of O(log tiles) and a bit scan each - the end of its last record, the nearest selected record in
+ * front of it and the nearest one behind it - whatever the data and the distances are (kernels/find.hpp,
+ * find_rec_ctx_kernel).  A distance that is not 0 grows one workspace more: a second record mask, its tile counts and a
+ * scan.  Measured in DESIGN.md 5.20.
+ */
+int hufgpu_find_records_context(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                                const uint64_t *d_block_offsets, uint64_t nblocks,
+                                const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                                uint32_t select, uint32_t before, uint32_t after,
+                                uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no, uint8_t *d_rec_sel, uint64_t rec_cap, uint32_t max_len,
+                                uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                                uint32_t flags, void *stream);
 
 /*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from

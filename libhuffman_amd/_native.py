@@ -78,7 +78,7 @@ hufgpu_batch_geometry hufgpu_encode_batch hufgpu_decode_batch hufgpu_decode_rang
 hufgpu_sub_index_from_raw hufgpu_decode_build_sub hufgpu_build_sub_index hufgpu_update_ranges
 hufgpu_append hufgpu_truncate hufgpu_ranges_counters hufgpu_gather hufgpu_find_bytes hufgpu_find_pattern hufgpu_find_records
 hufgpu_find_classes hufgpu_find_records_classes hufgpu_find_any hufgpu_find_records_any
-hufgpu_find_records_select""".split()
+hufgpu_find_records_select hufgpu_find_records_context""".split()
 
 
 def so_path() -> str:
@@ -206,6 +206,9 @@ def load() -> C.CDLL:
     L.hufgpu_find_records_select.restype = C.c_int        # hufgpu_find_records_any's with `select` and `d_rec_no`
     L.hufgpu_find_records_select.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, u64,
                                              C.c_uint32, vp, vp, vp, C.c_uint32, vp]
+    L.hufgpu_find_records_context.restype = C.c_int       # hufgpu_find_records_select's with `before`, `after` and `d_rec_sel`
+    L.hufgpu_find_records_context.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              vp, vp, vp, vp, u64, C.c_uint32, vp, vp, vp, C.c_uint32, vp]
     _LIB = L
     return L
 

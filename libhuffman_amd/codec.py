@@ -540,6 +540,21 @@ class GpuCodec:
             return "classes", (classes.tobytes(), len(classes)), st
         return "any", (alts[0].tobytes(), alts[1].tobytes(), len(alts[1])), st
 
+    @staticmethod
+    def _find_context(before, after, context):
+        """(before, after) of hufgpu_find_records_context from the three keywords of find_records / count_records / grep:
+        `context` sets both.  Raises ValueError for `context` next to one of the two, and for a distance that is negative
+        or above 2^32 - 1."""
+        if context is not None:
+            if before or after:
+                raise ValueError("`context` sets both `before` and `after`: give it or them")
+            before = after = context
+        before, after = int(before), int(after)
+        for name, v in (("before", before), ("after", after)):
+            if not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError(f"`{name if context is None else 'context'}` is 0 to 2^32 - 1 records, not {v}")
+        return before, after
+
     def find_pattern(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, max_positions: int = 0,
                      block_counts: bool = False, relaxed: bool = False, out: torch.Tensor | None = None,
@@ -576,7 +591,8 @@ class GpuCodec:
     def find_records(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, delimiters=b"\n",
                      max_records: int = 0, max_len: int = 0, block_counts: bool = False, relaxed: bool = False, out=None,
-                     ignore_case: bool = False, invert: bool = False, line_numbers: bool = False):
+                     ignore_case: bool = False, before: int = 0, after: int = 0, context: int | None = None,
+                     invert: bool = False, line_numbers: bool = False):
         """The records of the original data - the pieces between the bytes of `delimiters` (an iterable of ints or a
         `bytes`; empty: the data is one record) - that hold `pattern` at least once, each record ONCE, on torch's current
         stream and without a synchronisation (hufgpu_find_records): one walk of the stream, no decoded byte written.
@@ -598,60 +614,86 @@ class GpuCodec:
         numbers[max_records] int64: the delimiters in front of each written record, 0-based (grep -n prints it plus 1), -1
         when a block in front of the record's is not served.  Either makes the call hufgpu_find_records_select, a `bytes` or
         `list` pattern being its one alternative; with both False the call and what it returns are what they always were.
-        `out` may then hold a third buffer, contiguous int64 [max_records], for the numbers."""
-        select = bool(invert) or bool(line_numbers)
+        `out` may then hold a third buffer, contiguous int64 [max_records], for the numbers.
+        `before`, `after` (grep -B, -A) and `context` (grep -C: both) also report the non-empty records of known extent that
+        lie at most that many records in front of or behind a record of the answer - the matching ones, or with `invert`
+        the ones without a match - when every block between the two is served; distances count empty records, which are
+        never reported.  Any of them non-zero makes the call hufgpu_find_records_context and appends one more tensor,
+        behind the numbers: selected[max_records] uint8, 1 for a record of the answer itself and 0 for context (grep's ':'
+        and '-'); a buffer for it may come last in `out`.  `context` next to `before` or `after`, a negative distance and one
+        above 2^32 - 1 are a ValueError.  With all three at their defaults nothing changes."""
+        before, after = self._find_context(before, after, context)
+        widens = bool(before or after)
+        select = bool(invert) or bool(line_numbers) or widens
         route, key, st = self._find_route(pattern, ignore_case, delimiters, select)
         max_records, max_len = int(max_records), int(max_len)
         out = tuple(out) if out is not None else (None, None)
         numbers = self._find_buffer(out[2] if len(out) > 2 else None, max_records, torch.int64) if line_numbers else None
+        at = 3 if line_numbers else 2
+        selected = self._find_buffer(out[at] if len(out) > at else None, max_records, torch.uint8) if widens else None
         pos = self._find_buffer(out[0], max_records, torch.int64)
         lens = self._find_buffer(out[1], max_records, torch.int32)
         head, tail, totals, errs, counts = self._find_args(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
                                                            block_counts, relaxed)
         ptrs = (pos.data_ptr() if max_records else None, lens.data_ptr() if max_records else None)
-        if select:
+        if widens:
+            err = self.lib.hufgpu_find_records_context(*head, st, *key, _native.SELECT_INVERT if invert else 0, before, after, *ptrs,
+                                                       numbers.data_ptr() if line_numbers and max_records else None,
+                                                       selected.data_ptr() if max_records else None, max_records, max_len, *tail)
+        elif select:
             err = self.lib.hufgpu_find_records_select(*head, st, *key, _native.SELECT_INVERT if invert else 0, *ptrs,
                                                       numbers.data_ptr() if line_numbers and max_records else None,
                                                       max_records, max_len, *tail)
         else:
             err = getattr(self.lib, self._FIND_CALLS[route][1])(*head, st, *key, *ptrs, max_records, max_len, *tail)
         self._check(err, "Failed to enqueue the search")
-        return (pos, lens, totals, errs, counts) + ((numbers,) if line_numbers else ())
+        return (pos, lens, totals, errs, counts) + ((numbers,) if line_numbers else ()) + ((selected,) if widens else ())
 
     def count_records(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                       sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, delimiters=b"\n",
-                      relaxed: bool = False, ignore_case: bool = False, invert: bool = False, line_numbers: bool = False):
+                      relaxed: bool = False, ignore_case: bool = False, before: int = 0, after: int = 0,
+                      context: int | None = None, invert: bool = False, line_numbers: bool = False):
         """How many records hold `pattern` (grep -c; with `invert` grep -v -c, but for the empty lines): find_records
         without positions, enqueue-only.  Returns CUDA tensors (totals[4], block_errs[nblocks]) as find_records does, and
-        with `line_numbers` the empty tensor of numbers behind them."""
+        with `line_numbers` the empty tensor of numbers behind them.  `before`, `after`, `context`: the records that
+        find_records reports with them are counted, and the empty tensor of flags comes last."""
         res = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
-                                delimiters, relaxed=relaxed, ignore_case=ignore_case, invert=invert, line_numbers=line_numbers)
+                                delimiters, relaxed=relaxed, ignore_case=ignore_case, before=before, after=after, context=context,
+                                invert=invert, line_numbers=line_numbers)
         return (res[2], res[3]) + tuple(res[5:])
 
     def grep(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, sub_index: torch.Tensor,
              raw_size: int, blocksize: int, pattern, max_records: int, max_len: int, delimiters=b"\n",
-             relaxed: bool = False, ignore_case: bool = False, invert: bool = False, line_numbers: bool = False):
+             relaxed: bool = False, ignore_case: bool = False, before: int = 0, after: int = 0, context: int | None = None,
+             invert: bool = False, line_numbers: bool = False):
         """The first `max_len` bytes of the first `max_records` records that hold `pattern`: find_records followed by
         gather, on torch's current stream and without a synchronisation.  Returns CUDA tensors (lines uint8 [max_records,
         max_len], raw_lens int32 [max_records] - the bytes of row i that are the record's -, errs int32 [max_records] -
         gather's per record -, totals[4] and block_errs[nblocks] as find_records gives them).  Rows from totals[1] on are
         records of 0 bytes at raw_size.  `invert`: the non-empty records that do NOT hold it (grep -v); `line_numbers`: one
-        more tensor at the end, numbers int64 [max_records] as find_records gives them, -1 from row totals[1] on."""
+        more tensor at the end, numbers int64 [max_records] as find_records gives them, -1 from row totals[1] on.
+        `before`, `after`, `context` (grep -B, -A, -C): the rows around those records as well, as find_records reports them,
+        and one more tensor behind the numbers, selected uint8 [max_records]: 1 for a row of the answer itself, 0 for a row of
+        context and from row totals[1] on."""
         max_records, max_len = int(max_records), int(max_len)
         if max_len < 1:
             raise ValueError("grep needs max_len, the bytes of a row")
         found = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
                                   pattern, delimiters, max_records=max_records, max_len=max_len,
-                                  relaxed=relaxed, ignore_case=ignore_case, invert=invert, line_numbers=line_numbers)
+                                  relaxed=relaxed, ignore_case=ignore_case, before=before, after=after, context=context,
+                                  invert=invert, line_numbers=line_numbers)
         pos, lens, totals, block_errs = found[:4]
         written = torch.arange(max_records, device=self.tdev) < totals[1]
         pos = torch.where(written, pos, raw_size)
         lens = torch.where(written, lens, 0)
         lines, errs, raw_lens = self.gather(stream, stream_len, offsets, nblocks, pos, lens, sub_index=sub_index, raw_size=raw_size,
                                             blocksize=blocksize, max_len=max_len, relaxed=relaxed)
+        more = found[5:]
         if line_numbers:
-            return lines, raw_lens, errs, totals, block_errs, torch.where(written, found[5], -1)
-        return lines, raw_lens, errs, totals, block_errs
+            more = (torch.where(written, more[0], -1),) + more[1:]
+        if len(more) > int(bool(line_numbers)):                         # the flags: 0 behind the written rows
+            more = more[:-1] + (torch.where(written, more[-1], 0),)
+        return (lines, raw_lens, errs, totals, block_errs) + more
 
     # -- overwrite: bytes [lo, hi) of the original data replaced in one indexed stream ---------------
     def update_ranges(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, ranges,

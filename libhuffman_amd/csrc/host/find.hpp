@@ -1,7 +1,8 @@
 /* find.hpp - the search family of include/huffman_gpu.h: hufgpu_find_bytes, hufgpu_find_pattern, hufgpu_find_classes and
    hufgpu_find_any give the positions of a set of byte values, of a pattern, of a pattern of sets, of any of several such
    patterns; hufgpu_find_records, hufgpu_find_records_classes, hufgpu_find_records_any and hufgpu_find_records_select give
-   the records - the pieces between delimiters - that hold one (or do not), and their numbers.  All enqueue-only.  A
+   the records - the pieces between delimiters - that hold one (or do not), and their numbers; hufgpu_find_records_context
+   gives the records around them as well.  All enqueue-only.  A
    wrapper describes its call in three structs; find_call checks them (find_check, no HIP call), fills the kernels'
    arguments and grows the workspace (find_fill) and enqueues the chain of kernels/find.hpp (find_enqueue).
    Part of hufgpu_api.hip (one translation unit). */
@@ -49,12 +50,19 @@ struct FindSelCall {
     uint64_t *d_rec_no;                     /* optional */
 };
 
+/* what hufgpu_find_records_context has beyond the select call */
+struct FindCtxCall {
+    uint32_t before, after;
+    uint8_t *d_rec_sel;                     /* optional */
+};
+
 /* What is looked for: `who` words the errors, `key` is the set (plen = 0) or the pattern of plen bytes, `key_name` its name;
  * rec is NULL but for the records' calls.  cls is NULL but for the class calls: then `key` is the caller's array of plen
  * classes, which find_call only checks for NULL and never reads - its wrapper has read it -, and cls is the table made
  * from it.  alt is NULL but for the any-of calls: then cls is alt's table (several alternatives in its 64 bits), plen is the
  * LONGEST alternative's length - what the edges workspace and the seam launch follow - and alt goes to the kernels.
- * sel is NULL but for the select call, which is the any-of records' call with up to three launches more. */
+ * sel is NULL but for the select and the context call: the any-of records' call with up to three launches more.
+ * cx is NULL but for the context call, which is the select call with a dilation of the selected records' mask. */
 struct FindKey {
     const char *who, *key_name;
     const uint8_t *key;
@@ -63,7 +71,11 @@ struct FindKey {
     const FindClsTable *cls;
     FindAltArgs *alt;
     const FindSelCall *sel;
+    const FindCtxCall *cx;
 };
+
+/* does the context call widen the answer: with both distances 0 it is the select call, maybe with flags */
+static bool find_widens(const FindKey &k) { return k.cx && (k.cx->before | k.cx->after) != 0u; }
 
 /* the layout's blocks in chunks, mask words and tiles */
 struct FindGeometry {
@@ -119,6 +131,7 @@ static int find_fill(hufgpu_ctx_t *ctx, const FindStream &in, const FindOut &out
     if (!rc && k.plen > 1) rc = grow_ws(ctx, G_FIND_EDGES, ntiles);                 /* (one byte has no seams: no edges) */
     if (!rc && k.rec) rc = grow_ws2(ctx, G_FIND_REC_WORDS, nwords, G_FIND_REC_TILES, ntiles);
     if (!rc && k.sel && k.sel->d_rec_no && out.cap > 0) rc = grow_ws(ctx, G_FIND_SEL, 1);
+    if (!rc && find_widens(k)) rc = grow_ws2(ctx, G_FIND_CTX_WORDS, nwords, G_FIND_CTX_TILES, ntiles);
     if (rc) return rc;
     memset(&ra, 0, sizeof(ra));
     FindPatArgs &pa = ra.p;
@@ -192,25 +205,53 @@ static int find_enqueue(hufgpu_ctx_t *ctx, const FindOut &out, const FindKey &k,
     const dim3 blocks(grid256(nblocks)), et(FIND_EMIT_THREADS);
     HIP_OK(ctx, hipMemsetAsync(out.d_block_errs, 0, nblocks * sizeof(int32_t), s));
     HIP_OK(ctx, hipMemsetAsync(out.d_totals, 0, 4 * sizeof(uint64_t), s));
+    const bool widens = find_widens(k);
     if (k.rec) {
         HIP_OK(ctx, hipMemsetAsync(ra.rbits, 0, nblocks * fa.wpb * sizeof(uint32_t), s));
         HIP_OK(ctx, hipMemsetAsync(ra.rcnt, 0, fa.ntiles * sizeof(uint32_t), s));
+        if (widens) HIP_OK(ctx, hipMemsetAsync(ctx->d_fctotals, 0, 4 * sizeof(uint64_t), s));
     }
     find_enqueue_walk(k, ra, walk, seams, s);
+    const uint32_t *sbits = ra.rbits;                               /* the selected records' mask, whatever the emit kernel reads */
     if (k.rec) {
         /* from the walk's two masks to the records' starts and their counts by tile; scan, finish and emit then take the
          * records of a tile as they take its matches */
-        find_rec_dscan_kernel<<<groups, dim3(SCAN_GROUP), 0, s>>>(ra);
+        FindCtxArgs ca;
+        if (widens) {                                               /* (a block that is not served lies farther away than either distance) */
+            ca = {ra, ctx->d_fcbits, ctx->d_fccnt, ctx->fctx_scan, k.cx->before, k.cx->after};
+            ca.rscan.total = ctx->d_fctotals;
+            find_ctx_dscan_kernel<<<groups, dim3(64), 0, s>>>(ca);                      /* (a wave a group) */
+        } else {
+            find_rec_dscan_kernel<<<groups, dim3(SCAN_GROUP), 0, s>>>(ra);
+        }
         find_rec_mark_kernel<<<tiles, et, 0, s>>>(ra);
         if (k.sel && (k.sel->select & HUFGPU_SELECT_INVERT)) find_rec_invert_kernel<<<tiles, et, 0, s>>>(ra);   /* over mark's words and counts */
         fa.tcnt = ra.rcnt;
+        if (widens) {
+            /* the selected records' counts into a scan of this call's own - find_scan_kernel, with four words of the
+             * workspace as its totals -, then the records to report into the second mask, which the rest of the chain takes */
+            FindArgs sfa = fa;
+            sfa.scan = ca.rscan;
+            sfa.totals = ctx->d_fctotals;
+            find_scan_kernel<<<groups, dim3(SCAN_GROUP), 0, s>>>(sfa);
+            find_rec_ctx_kernel<<<tiles, et, 0, s>>>(ca);
+            ra.rbits = ca.cbits;
+            fa.tcnt = ra.rcnt = ca.ccnt;
+        }
     }
     find_scan_kernel<<<groups, dim3(SCAN_GROUP), 0, s>>>(fa);
     find_finish_kernel<<<blocks, dim3(256), 0, s>>>(fa);
-    if (k.sel && k.sel->d_rec_no && out.cap > 0) {                  /* the numbers need the first block that is not served */
-        const FindSelArgs sa = {ra, k.sel->d_rec_no, ctx->d_fsel_first};
+    const bool numbers = k.sel && k.sel->d_rec_no && out.cap > 0, flags = k.cx && k.cx->d_rec_sel && out.cap > 0;
+    const FindSelArgs sa = {ra, numbers ? k.sel->d_rec_no : NULL, ctx->d_fsel_first};
+    if (numbers) {                                                  /* the numbers need the first block that is not served */
         HIP_OK(ctx, hipMemsetAsync(sa.first_bad, 0xff, sizeof(uint64_t), s));
         find_rec_first_bad_kernel<<<blocks, dim3(256), 0, s>>>(sa);
+    }
+    if (flags) {                                                    /* is a reported record one of the selected: its bit in sbits */
+        const FindCtxEmitArgs ea = {sa, sbits, k.cx->d_rec_sel};
+        if (numbers) find_ctx_emit_no_kernel<<<tiles, et, 0, s>>>(ea);
+        else find_ctx_emit_kernel<<<tiles, et, 0, s>>>(ea);
+    } else if (numbers) {
         find_rec_emit_no_kernel<<<tiles, et, 0, s>>>(sa);
     } else if (out.cap > 0 && k.rec) {
         find_rec_emit_kernel<<<tiles, et, 0, s>>>(ra);
@@ -250,7 +291,7 @@ extern "C" int hufgpu_find_bytes(hufgpu_ctx_t *ctx, const void *d_stream, uint64
 {
     const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
     const FindOut out = {d_pos, pos_cap, d_block_counts, d_totals, d_block_errs};
-    const FindKey k = {"find_bytes", "set", set, 0, NULL, NULL, NULL, NULL};
+    const FindKey k = {"find_bytes", "set", set, 0, NULL, NULL, NULL, NULL, NULL};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -262,7 +303,7 @@ extern "C" int hufgpu_find_pattern(hufgpu_ctx_t *ctx, const void *d_stream, uint
     if (pattern && find_pattern_len(ctx, "find_pattern", pattern_len)) return HUFE_ARGUMENT;
     const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
     const FindOut out = {d_pos, pos_cap, d_block_counts, d_totals, d_block_errs};
-    const FindKey k = {"find_pattern", "pattern", pattern, pattern_len, NULL, NULL, NULL, NULL};
+    const FindKey k = {"find_pattern", "pattern", pattern, pattern_len, NULL, NULL, NULL, NULL, NULL};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -276,7 +317,7 @@ extern "C" int hufgpu_find_records(hufgpu_ctx_t *ctx, const void *d_stream, uint
     const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
     const FindOut out = {d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs};
     const FindRecCall rec = {delim_set, d_rec_len, max_len};
-    const FindKey k = {"find_records", "pattern", pattern, pattern_len, &rec, NULL, NULL, NULL};
+    const FindKey k = {"find_records", "pattern", pattern, pattern_len, &rec, NULL, NULL, NULL, NULL};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -323,7 +364,7 @@ extern "C" int hufgpu_find_classes(hufgpu_ctx_t *ctx, const void *d_stream, uint
     if (classes && find_cls_table(ctx, "find_classes", classes, pattern_len, NULL, &t)) return HUFE_ARGUMENT;
     const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
     const FindOut out = {d_pos, pos_cap, d_block_counts, d_totals, d_block_errs};
-    const FindKey k = {"find_classes", "classes", classes, pattern_len, NULL, &t, NULL, NULL};
+    const FindKey k = {"find_classes", "classes", classes, pattern_len, NULL, &t, NULL, NULL, NULL};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -338,7 +379,7 @@ extern "C" int hufgpu_find_records_classes(hufgpu_ctx_t *ctx, const void *d_stre
     const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
     const FindOut out = {d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs};
     const FindRecCall rec = {delim_set, d_rec_len, max_len};
-    const FindKey k = {"find_records_classes", "classes", classes, pattern_len, &rec, &t, NULL, NULL};
+    const FindKey k = {"find_records_classes", "classes", classes, pattern_len, &rec, &t, NULL, NULL, NULL};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -377,16 +418,16 @@ static int find_alt_table(hufgpu_ctx_t *ctx, const char *who, const uint8_t *cla
     return HUFE_OK;
 }
 
-/* the three any-of wrappers' call: the table, when both arrays are there (find_check words a missing one), then find_call */
+/* the four any-of wrappers' call: the table, when both arrays are there (find_check words a missing one), then find_call */
 static int find_alt_call(hufgpu_ctx_t *ctx, const char *who, const FindStream &in, const FindOut &out, const uint8_t *classes,
-                         const uint32_t *alt_lens, uint32_t n_alts, const FindRecCall *rec, const FindSelCall *sel, uint32_t flags,
-                         void *stream)
+                         const uint32_t *alt_lens, uint32_t n_alts, const FindRecCall *rec, const FindSelCall *sel, const FindCtxCall *cx,
+                         uint32_t flags, void *stream)
 {
     FindAltArgs t;
     uint32_t maxlen = 0;
     const bool both = classes && alt_lens;
     if (both && find_alt_table(ctx, who, classes, alt_lens, n_alts, rec ? rec->delim_set : NULL, &t, &maxlen)) return HUFE_ARGUMENT;
-    const FindKey k = {who, "classes, alt_lens", both ? classes : NULL, maxlen, rec, &t.t, &t, sel};
+    const FindKey k = {who, "classes, alt_lens", both ? classes : NULL, maxlen, rec, &t.t, &t, sel, cx};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -397,7 +438,7 @@ extern "C" int hufgpu_find_any(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t
 {
     const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
     const FindOut out = {d_pos, pos_cap, d_block_counts, d_totals, d_block_errs};
-    return find_alt_call(ctx, "find_any", in, out, classes, alt_lens, n_alts, NULL, NULL, flags, stream);
+    return find_alt_call(ctx, "find_any", in, out, classes, alt_lens, n_alts, NULL, NULL, NULL, flags, stream);
 }
 
 extern "C" int hufgpu_find_records_any(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
@@ -409,7 +450,7 @@ extern "C" int hufgpu_find_records_any(hufgpu_ctx_t *ctx, const void *d_stream, 
     const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
     const FindOut out = {d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs};
     const FindRecCall rec = {delim_set, d_rec_len, max_len};
-    return find_alt_call(ctx, "find_records_any", in, out, classes, alt_lens, n_alts, &rec, NULL, flags, stream);
+    return find_alt_call(ctx, "find_records_any", in, out, classes, alt_lens, n_alts, &rec, NULL, NULL, flags, stream);
 }
 
 extern "C" int hufgpu_find_records_select(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
@@ -425,5 +466,23 @@ extern "C" int hufgpu_find_records_select(hufgpu_ctx_t *ctx, const void *d_strea
     const FindOut out = {d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs};
     const FindRecCall rec = {delim_set, d_rec_len, max_len};
     const FindSelCall sel = {select, d_rec_no};
-    return find_alt_call(ctx, "find_records_select", in, out, classes, alt_lens, n_alts, &rec, &sel, flags, stream);
+    return find_alt_call(ctx, "find_records_select", in, out, classes, alt_lens, n_alts, &rec, &sel, NULL, flags, stream);
+}
+
+extern "C" int hufgpu_find_records_context(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                           uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                           const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                                           uint32_t select, uint32_t before, uint32_t after, uint64_t *d_rec_pos, uint32_t *d_rec_len,
+                                           uint64_t *d_rec_no, uint8_t *d_rec_sel, uint64_t rec_cap, uint32_t max_len,
+                                           uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream)
+{
+    if (select & ~HUFGPU_SELECT_INVERT)
+        return find_bad(ctx, "find_records_context: select 0x%x has a bit other than HUFGPU_SELECT_INVERT", select);
+    const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
+    const FindOut out = {d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs};
+    const FindRecCall rec = {delim_set, d_rec_len, max_len};
+    const FindSelCall sel = {select, d_rec_no};
+    const FindCtxCall cx = {before, after, d_rec_sel};
+    const bool plain = (before | after) == 0u && !d_rec_sel;        /* the select call, by its launches */
+    return find_alt_call(ctx, "find_records_context", in, out, classes, alt_lens, n_alts, &rec, &sel, plain ? NULL : &cx, flags, stream);
 }

@@ -15,6 +15,11 @@
    hufgpu_find_records_any         find_rec_alt_sub -> find_alt_seam -> RECORDS
    hufgpu_find_records_select      find_rec_alt_sub -> find_alt_seam -> RECORDS with [find_rec_invert] behind find_rec_mark
                                    and, for the numbers, find_rec_first_bad -> find_rec_emit_no in the place of find_rec_emit
+   hufgpu_find_records_context     the select call's chain with find_ctx_dscan in the place of find_rec_dscan and, behind
+                                   find_rec_mark [-> find_rec_invert], find_scan (of the selected records' counts, into a scan
+                                   of its own) -> find_rec_ctx, whose second mask the rest of the chain takes; with d_rec_sel
+                                   find_ctx_emit / find_ctx_emit_no in the place of the emit kernel.  before = after = 0:
+                                   the select call's launches but for that emit kernel
    RECORDS = find_rec_dscan -> find_rec_mark -> find_scan -> find_finish [-> find_rec_emit]; no seam kernel for 1 byte
 
    The walk: find_sub_body, the seven *_sub kernels
@@ -82,6 +87,12 @@
                            min(e - s, clip) go to the record's rank, the cut ones are counted into d_totals[3].  With
                            find_rec_first_bad_kernel in front, find_rec_emit_no_kernel adds the record's number: the
                            delimiters in front of it, known while no block in front of the record's is unserved.
+     find_rec_ctx_kernel   hufgpu_find_records_context: the records AROUND the selected ones.  A dilation of rbits in
+                           record-number space into a second mask and count array, on which scan, finish and emit then
+                           run; a record's number comes from find_ctx_dscan_kernel's scan, in which a tile of a block that
+                           is not served weighs more than either distance, and the nearest selected record of other tiles
+                           from a scan of rcnt: three look-ups a tile at most.  find_ctx_emit_kernel and
+                           find_ctx_emit_no_kernel are the emit kernels with a flag a record: is it one of the selected.
 
    Invariants
      Zeroed by the host before the first kernel: the statuses d_block_errs, d_totals, and for the records rbits and rcnt.
@@ -681,6 +692,51 @@ __global__ __launch_bounds__(SCAN_GROUP) void find_rec_dscan_kernel(FindRecArgs 
     scan_group_publish<SCAN_GROUP>(ra.dscan, i, a.ntiles, c, s_part);
 }
 
+/* hufgpu_find_records_context: find_rec_dscan_kernel with a HEAVY virtual delimiter.  A tile of a block that is not served
+ * counts max(before, after) + 1 delimiters that are nowhere, so two records with such a block between them are farther
+ * apart, in numbers, than either distance: no context is measured across it.  The look-ups of the record kernels only need
+ * the count to be non-zero, and a record's number is known in front of the first such block only, where nothing changes.
+ * (At most 2^31 - 1 tiles of at most 2^32 each: the sums fit in the scan's 64 bits.) */
+struct FindCtxArgs {
+    FindRecArgs r;                          /* r.rbits / r.rcnt: the SELECTED records, as mark (and invert) leave them */
+    uint32_t *cbits;                        /* [nblocks][wpb] the starts of the records to report: selected or context */
+    uint32_t *ccnt;                         /* [nblocks][tpb] ... and how many of them a tile holds */
+    TwoLevel rscan;                         /* of the tiles' selected records (find_scan_kernel on rcnt); rscan.total: how many there are */
+    uint32_t before, after;
+};
+
+/* a workgroup = ONE wave = one SCAN_GROUP of tiles, a lane four of them, as two_level_arrive's last wave scans its group: no
+ * LDS.  (Tile numbers fit in 32 bits, so the lanes divide 32-bit values.) */
+__global__ __launch_bounds__(64) void find_ctx_dscan_kernel(FindCtxArgs ca)
+{
+    static_assert(SCAN_GROUP == 256, "a lane scans four tiles of its group");
+    const FindRecArgs &ra = ca.r;
+    const FindArgs &a = ra.p.f;
+    const uint32_t lane = (uint32_t)lane_id(), ntiles = (uint32_t)a.ntiles, tpb = (uint32_t)a.tpb;
+    const uint32_t i0 = blockIdx.x * SCAN_GROUP + lane * 4u;
+    const uint64_t heavy = (uint64_t)dmax(ca.before, ca.after) + 1u;
+    uint64_t v[4], own = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        const uint32_t i = i0 + j;
+        v[j] = 0;
+        if (i < ntiles) {
+            const uint32_t b = i / tpb, t = i % tpb;
+            if ((uint64_t)t * HUF_SUB_TILE < find_block_len(a, b)) v[j] = a.errs[b] == HUFE_OK ? (uint64_t)ra.dcnt[i] : heavy;
+        }
+        own += v[j];
+    }
+    const uint64_t incl = wave_incl_scan_u64(own);
+    uint64_t run = incl - own;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        if (i0 + j < ntiles) ra.dscan.local[i0 + j] = run;
+        run += v[j];
+    }
+    if (lane == 63) handover_store(ra.dscan.gsum + blockIdx.x, incl);
+    two_level_finish(ra.dscan, gridDim.x);
+}
+
 /* the delimiters, real and virtual, of the tiles in front of tile k; k = ntiles: of all tiles */
 __device__ __forceinline__ uint64_t find_rec_before(const FindRecArgs &ra, uint64_t k)
 {
@@ -906,9 +962,11 @@ __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_invert_kernel(Find
  * NO (find_rec_emit_no_kernel): the record's number goes to its rank as well - the delimiters in front of the tile, which
  * find_rec_dscan_kernel has scanned, plus those of the tile below s: a wave prefix over the words' popcounts and the bits
  * below s in the lane's own word.  The scan counts a delimiter that is nowhere for every tile of a block that is not served,
- * so the number is known only while no block in front of b is one of those: FIND_REC_NO_UNKNOWN otherwise. */
-template <bool NO>
-__device__ __forceinline__ void find_rec_emit_body(const FindRecArgs &ra, [[maybe_unused]] const FindSelArgs *sa = nullptr)
+ * so the number is known only while no block in front of b is one of those: FIND_REC_NO_UNKNOWN otherwise.
+ * SEL (find_ctx_emit_kernel, find_ctx_emit_no_kernel): the record's bit in a second mask, sbits, goes to its rank as well. */
+template <bool NO, bool SEL = false>
+__device__ __forceinline__ void find_rec_emit_body(const FindRecArgs &ra, [[maybe_unused]] const FindSelArgs *sa = nullptr,
+                                                   [[maybe_unused]] const uint32_t *sbits = nullptr, [[maybe_unused]] uint8_t *sel = nullptr)
 {
     const FindArgs &a = ra.p.f;
     const uint32_t lane = (uint32_t)lane_id();
@@ -932,6 +990,8 @@ __device__ __forceinline__ void find_rec_emit_body(const FindRecArgs &ra, [[mayb
         no0 = find_rec_before(ra, i) + (wave_incl_scan_u32((uint32_t)__popc(d)) - (uint32_t)__popc(d));
         known = *sa->first_bad >= b;
     }
+    [[maybe_unused]] uint32_t sw = 0;                               /* SEL: the lane's word of the selected records' mask */
+    if constexpr (SEL) sw = g * DSUB_SPL < blen ? sbits[b * a.wpb + g] : 0u;
     uint32_t cut = 0;
     while (r != 0u && rank < a.pos_cap) {
         const uint32_t bit = (uint32_t)__builtin_ctz(r);
@@ -943,6 +1003,7 @@ __device__ __forceinline__ void find_rec_emit_body(const FindRecArgs &ra, [[mayb
         a.pos[rank] = s;
         ra.len[rank] = n > ra.clip ? ra.clip : (uint32_t)n;
         if constexpr (NO) sa->no[rank] = known ? no0 + (uint32_t)__popc(d & ((1u << bit) - 1u)) : FIND_REC_NO_UNKNOWN;
+        if constexpr (SEL) sel[rank] = (uint8_t)((sw >> bit) & 1u);
         cut += n > ra.clip;
         rank++;
     }
@@ -952,5 +1013,228 @@ __device__ __forceinline__ void find_rec_emit_body(const FindRecArgs &ra, [[mayb
 
 __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_emit_kernel(FindRecArgs ra) { find_rec_emit_body<false>(ra); }
 __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_emit_no_kernel(FindSelArgs sa) { find_rec_emit_body<true>(sa.r, &sa); }
+
+/* ---- hufgpu_find_records_context: the records around the selected ones (grep -A / -B / -C) ----------------------------- */
+
+/* the selected records of the tiles in front of tile k (of the served blocks); k = ntiles: all of them */
+__device__ __forceinline__ uint64_t find_ctx_sel_before(const FindCtxArgs &ca, uint64_t k)
+{
+    return k < ca.r.p.f.ntiles ? two_level_prefix(ca.rscan, k) : *ca.rscan.total;
+}
+
+/* Called by a full wave, every lane with the same served tile j that holds a selected record: the NUMBER of its last
+ * (LAST) or first selected record - the delimiters in front of tile j plus those of the tile in front of the start.  One
+ * bit scan of the tile's 64 words. */
+template <bool LAST>
+__device__ __forceinline__ bool find_ctx_sel_number(const FindCtxArgs &ca, uint32_t j, uint32_t lane, uint64_t &no)
+{
+    const FindArgs &a = ca.r.p.f;
+    const uint64_t b = j / (uint32_t)a.tpb, t = j % (uint32_t)a.tpb;
+    const uint64_t g = t * 64u + lane;
+    const uint32_t r = g * DSUB_SPL < find_block_len(a, b) ? ca.r.rbits[b * a.wpb + g] : 0u;
+    const uint32_t d = find_rec_dword(ca.r, b, t, lane);
+    const uint64_t nz = __ballot(r != 0u);
+    if (nz == 0) return false;                                      /* (cannot be: the tile's count is that of its words) */
+    const uint32_t at = uni32(LAST ? 63u - (uint32_t)__builtin_clzll(nz) : (uint32_t)__builtin_ctzll(nz));
+    const uint32_t w = wave_lane_u32(r, at);
+    const uint32_t bit = LAST ? 31u - (uint32_t)__builtin_clz(w) : (uint32_t)__builtin_ctz(w);
+    const uint32_t mine = lane < at ? (uint32_t)__popc(d) : (lane == at ? (uint32_t)__popc(d & ((1u << bit) - 1u)) : 0u);
+    no = find_rec_before(ca.r, j) + wave_total_u32(mine);
+    return true;
+}
+
+/* The look-ups of find_rec_ctx_kernel gallop: what they look for is nearly always in the tile next door - the delimiter that
+ * ends a tile's last record, a selected record of a frequent pattern -, and when it is not, a tile far away seldom matters:
+ * a record that many delimiters away is out of either distance.  `pre` is a scan over the tiles - pre(k): the sum over the
+ * tiles in front of k, k = ntiles: the total -, all values are the wave's.
+ * Backward, given c = pre(i) > 0: the nearest tile j < i that counts something.  Probes at i - 1, i - 2, i - 4, ..., each
+ * followed by far(k) - "nothing in front of tile k matters", which ends the search with false -, then a binary search
+ * between the last two probes: 2 log2(tiles) probes at most, two when the neighbour holds it. */
+template <typename P, typename F>
+__device__ __forceinline__ bool find_ctx_gallop_back(P pre, F far, uint64_t i, uint64_t c, uint32_t &j)
+{
+    uint64_t lo, hi = i;                                            /* pre(hi) = c: the tiles [hi, i) count nothing */
+    for (uint64_t step = 1;; step <<= 1) {
+        lo = i > step ? i - step : 0;
+        if (pre(lo) < c) break;                                     /* (pre(0) = 0 < c at the latest) */
+        if (far(lo)) return false;
+        hi = lo;
+    }
+    lo++;                                                           /* the first k in (lo, hi] with pre(k) >= c */
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (pre(mid) >= c) hi = mid;
+        else lo = mid + 1;
+    }
+    j = uni32((uint32_t)lo - 1u);
+    return true;
+}
+/* Forward, given c = pre(i + 1) < pre(ntiles): the first tile j > i that counts something; far(k): nothing in the tiles
+ * from k on matters. */
+template <typename P, typename F>
+__device__ __forceinline__ bool find_ctx_gallop_on(P pre, F far, uint64_t i, uint64_t ntiles, uint64_t c, uint32_t &j)
+{
+    uint64_t lo = i + 1, hi;                                        /* pre(lo) = c: the tiles (i, lo) count nothing */
+    for (uint64_t step = 1;; step <<= 1) {
+        hi = dmin<uint64_t>(i + step, ntiles - 1);
+        if (pre(hi + 1) > c) break;                                 /* (pre(ntiles) > c at the latest) */
+        if (far(hi + 1)) return false;
+        lo = hi + 1;
+    }
+    while (lo < hi) {                                               /* the first j in [lo, hi] with pre(j + 1) > c */
+        const uint64_t mid = (lo + hi) >> 1;
+        if (pre(mid + 1) > c) hi = mid;
+        else lo = mid + 1;
+    }
+    j = uni32((uint32_t)lo);
+    return true;
+}
+
+/* The number of the nearest selected record in the tiles in front of tile i, in the scanned counts of the selected records
+ * as find_rec_start_before looks for a delimiter, and of the nearest one in the tiles behind.  false: there is none that
+ * matters - none at all, or tile i's candidates, whose numbers lie in [before(i), before(i + 1)], are farther than the
+ * distance from every record of the tiles that were not looked at.  (The scan counts the tiles of served blocks only.) */
+__device__ __forceinline__ bool find_ctx_prev_tile(const FindCtxArgs &ca, uint64_t i, uint32_t lane, uint64_t &no)
+{
+    const uint64_t c = find_ctx_sel_before(ca, i);
+    if (c == 0) return false;
+    const uint64_t base = find_rec_before(ca.r, i);
+    uint32_t j;
+    if (!find_ctx_gallop_back([&](uint64_t k) { return find_ctx_sel_before(ca, k); },
+                              [&](uint64_t k) { return base - find_rec_before(ca.r, k) > (uint64_t)ca.after; }, i, c, j))
+        return false;
+    return find_ctx_sel_number<true>(ca, j, lane, no);
+}
+__device__ __forceinline__ bool find_ctx_next_tile(const FindCtxArgs &ca, uint64_t i, uint32_t lane, uint64_t &no)
+{
+    const uint64_t ntiles = ca.r.p.f.ntiles;
+    const uint64_t c = find_ctx_sel_before(ca, i + 1);
+    if (c == find_ctx_sel_before(ca, ntiles)) return false;
+    const uint64_t top = find_rec_before(ca.r, i + 1);
+    uint32_t j;
+    if (!find_ctx_gallop_on([&](uint64_t k) { return find_ctx_sel_before(ca, k); },
+                            [&](uint64_t k) { return find_rec_before(ca.r, k) - top > (uint64_t)ca.before; }, i, ntiles, c, j))
+        return false;
+    return find_ctx_sel_number<false>(ca, j, lane, no);
+}
+
+/* find_rec_end_behind, galloping: where the record ends that is open at the end of tile i - nearly always in tile i + 1 */
+__device__ __forceinline__ uint64_t find_ctx_end_behind(const FindRecArgs &ra, uint64_t i, uint32_t lane)
+{
+    const FindArgs &a = ra.p.f;
+    const uint64_t c = find_rec_before(ra, i + 1);
+    if (c == find_rec_before(ra, a.ntiles)) return a.s.raw_size;
+    uint32_t j;
+    find_ctx_gallop_on([&](uint64_t k) { return find_rec_before(ra, k); }, [](uint64_t) { return false; }, i, a.ntiles, c, j);
+    const uint64_t b = j / (uint32_t)a.tpb, t = j % (uint32_t)a.tpb;
+    if (a.errs[b] != HUFE_OK) return FIND_REC_OPEN;
+    const uint32_t d = find_rec_dword(ra, b, t, lane);
+    const uint64_t nz = __ballot(d != 0u);
+    if (nz == 0) return FIND_REC_OPEN;
+    const uint32_t first = uni32((uint32_t)__builtin_ctzll(nz));
+    return b * a.s.bsize + t * HUF_SUB_TILE + 32u * first + (uint32_t)__builtin_ctz(wave_lane_u32(d, first));
+}
+
+/* Behind find_rec_mark_kernel (and find_rec_invert_kernel), with the selected records' counts scanned: a wave = one tile, a
+ * lane = one word.  Context is a dilation of rbits in record-NUMBER space.  The candidates are find_rec_invert_kernel's: the
+ * starts of the non-empty records whose extent is known.  A candidate's number is the delimiters in front of its tile
+ * (find_ctx_dscan_kernel) + the wave's prefix over the words' popcounts + the bits below it in its own word.  The nearest
+ * selected record in front of it lies in the lane's own word, else in the lanes below (a wave max-scan of "my highest
+ * selected start's number"), else in the tiles in front: ONE look-up a tile, and only for the candidates in front of the
+ * tile's first selected record.  The nearest one behind it: the same, mirrored.  A candidate is reported when it is selected
+ * itself, when it lies at most `after` behind the one or at most `before` in front of the other.  So a tile costs three
+ * look-ups at most - the end of its last candidate, a neighbour in front, one behind -, each 2 log2(tiles) probes of a scan
+ * at most and one bit scan, whatever the data and the distances are (and two probes when the neighbouring tile answers),
+ * and none when it has no candidate that is not selected.  The answer goes to a SECOND mask and
+ * count array (other tiles' waves read rbits); scan, finish and emit then run on those.  A tile of a block that is not
+ * served writes nothing: the scan does not look at it. */
+__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_ctx_kernel(FindCtxArgs ca)
+{
+    const FindRecArgs &ra = ca.r;
+    const FindArgs &a = ra.p.f;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t i = find_tile_index<FIND_EMIT_THREADS>();
+    if (i >= a.ntiles) return;
+    const auto [b, t, blen] = find_tile(a, i);
+    if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK) return;
+    const uint64_t g = t * 64u + lane;
+    const bool inside = g * DSUB_SPL < blen;
+    const uint32_t d = find_rec_dword(ra, b, t, lane);
+    const uint32_t r = inside ? ra.rbits[b * a.wpb + g] : 0u;
+    uint32_t c0;                                                    /* is the byte in front of the tile a delimiter (the wave's) */
+    if (i == 0) {
+        c0 = 1u;
+    } else if (t != 0) {
+        c0 = ra.dbits[b * a.wpb + t * 64u - 1u] >> 31;              /* (the tile in front is a full one) */
+    } else if (a.errs[b - 1] != HUFE_OK) {
+        c0 = 0u;
+    } else {
+        const uint64_t last = a.s.bsize - 1u;                       /* (a block with a block behind it is a full one) */
+        c0 = (ra.dbits[(b - 1) * a.wpb + (last >> 5)] >> ((uint32_t)last & 31u)) & 1u;
+    }
+    const uint32_t below = wave_up1_u32(d);                         /* (by every lane) */
+    const uint32_t carry = lane == 0 ? c0 : below >> 31;
+    const uint64_t left = inside ? blen - g * DSUB_SPL : 0u;
+    const uint32_t valid = left >= 32u ? 0xffffffffu : (1u << (uint32_t)left) - 1u;
+    uint32_t cand = ((d << 1) | carry) & ~d & valid & ~r;           /* the candidates that are not selected themselves */
+    uint32_t out = 0;
+    if (__ballot(cand != 0u) != 0) {
+        const FindRecLane k = find_rec_lane(d, lane);
+        const bool tail = k.next < 0 && (cand & k.tail) != 0u;
+        if (__ballot(tail) != 0 && find_ctx_end_behind(ra, i, lane) == FIND_REC_OPEN && tail) cand &= ~k.tail;
+        /* numbers inside the tile: the delimiters of the tile in front of a start */
+        const uint32_t pd = (uint32_t)__popc(d), rel0 = wave_incl_scan_u32(pd) - pd;
+        const uint32_t rtop = r != 0u ? 31u - (uint32_t)__builtin_clz(r) : 0u, rlow = r != 0u ? (uint32_t)__builtin_ctz(r) : 0u;
+        const uint32_t hs = r != 0u ? rel0 + (uint32_t)__popc(d & ((1u << rtop) - 1u)) + 1u : 0u;    /* (+ 1: 0 is "none") */
+        const uint32_t ls = rel0 + (uint32_t)__popc(d & ((1u << rlow) - 1u));
+        const uint32_t pmax = wave_excl_max_u32(hs);                /* the nearest selected record of the lanes below: its number + 1 */
+        /* the nearest lane above with a selected record, in halves of 32 lanes (find_rec_lane) */
+        const uint64_t nz = __ballot(r != 0u);
+        const uint32_t nlo = (uint32_t)nz, nhi = (uint32_t)(nz >> 32), l = lane & 31u;
+        const uint32_t gt = l == 31u ? 0u : 0xffffffffu << (l + 1u);
+        const uint32_t above_lo = lane < 32u ? nlo & gt : 0u, above_hi = lane < 32u ? nhi : nhi & gt;
+        const int nl = above_lo != 0u ? __builtin_ctz(above_lo) : (above_hi != 0u ? 32 + __builtin_ctz(above_hi) : -1);
+        const uint32_t nmin = (uint32_t)__shfl((int)ls, nl < 0 ? 0 : nl);
+        /* the tiles in front and behind, for the candidates that have no selected record on that side in the tile */
+        const bool want_prev = pmax == 0u && (cand & (r != 0u ? (1u << rlow) - 1u : 0xffffffffu)) != 0u;
+        const bool want_next = nl < 0 && (cand & (r != 0u ? (rtop == 31u ? 0u : 0xffffffffu << (rtop + 1u)) : 0xffffffffu)) != 0u;
+        uint64_t pno = 0, nno = 0;
+        bool has_prev = false, has_next = false;
+        if (ca.after != 0u && __ballot(want_prev) != 0) has_prev = find_ctx_prev_tile(ca, i, lane, pno);
+        if (ca.before != 0u && __ballot(want_next) != 0) has_next = find_ctx_next_tile(ca, i, lane, nno);
+        const uint64_t base = find_rec_before(ra, i);
+        uint32_t cc = cand;
+        while (cc != 0u) {
+            const uint32_t bit = (uint32_t)__builtin_ctz(cc);
+            cc &= cc - 1u;
+            const uint32_t lowm = (1u << bit) - 1u;
+            const uint32_t n = rel0 + (uint32_t)__popc(d & lowm);
+            const uint32_t rl = r & lowm, ru = r & ~lowm;            /* (the bit itself is not selected) */
+            bool near = false;
+            if (rl != 0u) near = n - (rel0 + (uint32_t)__popc(d & ((1u << (31u - (uint32_t)__builtin_clz(rl))) - 1u))) <= ca.after;
+            else if (pmax != 0u) near = n + 1u - pmax <= ca.after;
+            else if (has_prev) near = base + n - pno <= (uint64_t)ca.after;
+            if (ru != 0u) near |= rel0 + (uint32_t)__popc(d & ((1u << (uint32_t)__builtin_ctz(ru)) - 1u)) - n <= ca.before;
+            else if (nl >= 0) near |= nmin - n <= ca.before;
+            else if (has_next) near |= nno - (base + n) <= (uint64_t)ca.before;
+            out |= (uint32_t)near << bit;
+        }
+    }
+    out |= r;
+    if (inside) ca.cbits[b * a.wpb + g] = out;
+    const uint32_t cnt = wave_total_u32((uint32_t)__popc(out));
+    if (lane == 0) ca.ccnt[i] = cnt;
+}
+
+/* find_rec_emit_kernel and find_rec_emit_no_kernel with d_rec_sel: s.r.rbits / s.r.rcnt are the mask and the counts of the
+ * records to report, sbits is the mask of the selected ones - the flag of a reported record is its bit there - and sel goes
+ * to the record's rank as its start and its length do.  s.no and s.first_bad are not looked at without the numbers. */
+struct FindCtxEmitArgs {
+    FindSelArgs s;
+    const uint32_t *sbits;
+    uint8_t *sel;
+};
+__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_ctx_emit_kernel(FindCtxEmitArgs ea) { find_rec_emit_body<false, true>(ea.s.r, &ea.s, ea.sbits, ea.sel); }
+__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_ctx_emit_no_kernel(FindCtxEmitArgs ea) { find_rec_emit_body<true, true>(ea.s.r, &ea.s, ea.sbits, ea.sel); }
 
 }  // namespace hufgpu
