@@ -656,6 +656,81 @@ int hufgpu_find_records_context(hufgpu_ctx_t *ctx, const void *d_stream, uint64_
                                 uint32_t flags, void *stream);
 
 /*
+ * FIND, ANCHORED: grep -w, grep -x, '^' and '$'.  The forms of a search that look at the byte NEXT TO a match:
+ * grep -w error (not "errors", not "stderror"), grep -x OK, grep '^2026-10-19', grep 'refused$'.  hufgpu_find_any_anchored()
+ * is hufgpu_find_any() and hufgpu_find_records_anchored() is hufgpu_find_records_context() - the contracts hold word for
+ * word: the pattern forms, d_sub_index (the caller vouches for NOTHING), every output, cap and total, `select`, d_rec_no,
+ * before / after, d_rec_sel, the known-extent rule, flags, nblocks = 0, enqueue-only without a host write or a wait, every
+ * argument error (worded "find_any_anchored: ..." and "find_records_anchored: ...") in the older calls' order - but for
+ * which occurrences count.  One walk of the stream (two for the records call with HUFGPU_ANCHOR_WORD): the byte behind a
+ * match is one more position an alternative in the matcher's table, the byte in front of it one AND of two masks that the
+ * walk writes.  There is no CPU path.
+ *
+ *   delim_set     : D, the bytes that end a record; the positions call takes it behind n_alts and looks at it only with
+ *                   HUFGPU_ANCHOR_BOL or HUFGPU_ANCHOR_EOL (NULL otherwise is fine).  The records call has its own, in the
+ *                   place where hufgpu_find_records_context() has it, and there the caller's classes still may not hold a
+ *                   delimiter.
+ *   word_set      : W, the word bytes, 32 bytes in hufgpu_find_bytes()' encoding ([A-Za-z0-9_] for grep's); looked at only
+ *                   with HUFGPU_ANCHOR_WORD.
+ *   anchors       : 0 or an OR of the three bits below; grep -x is HUFGPU_ANCHOR_BOL | HUFGPU_ANCHOR_EOL.
+ *   an occurrence : a pair (p, j) as hufgpu_find_any() defines a match of alternative j at p.  Its left neighbour is
+ *                   L = data[p - 1], ABSENT when p = 0; its right neighbour is R = data[p + len_j], absent when
+ *                   p + len_j = raw_size.  It QUALIFIES when every anchor that is asked for holds:
+ *                     HUFGPU_ANCHOR_BOL   L is absent or L is in D
+ *                     HUFGPU_ANCHOR_EOL   R is absent or R is in D
+ *                     HUFGPU_ANCHOR_WORD  (L is absent or L is not in W) and (R is absent or R is not in W)
+ *   what is reported: a start p once, ascending, when at least one alternative that lies there qualifies AND every block
+ *                   that holds a byte of that alternative's tested span is served: [p, p + len_j), widened by one byte on
+ *                   each side where a neighbour exists and an anchor tests it.  A start is left out on doubt, never reported
+ *                   wrongly; each alternative has its own span (hufgpu_find_any()'s own seam rule).  The records call selects
+ *                   on "holds a qualifying occurrence"; HUFGPU_SELECT_INVERT, d_rec_no, before / after, d_rec_sel, max_len,
+ *                   the caps, d_totals[0..3], d_block_counts and the known-extent rule then apply unchanged.  EVERY
+ *                   overlapping occurrence is tested, so a record qualifies when any occurrence in it does - what GNU grep
+ *                   gives for patterns of fixed length: grep -w foo selects "foofoo foo".
+ *   one-symbol blocks: served; an alternative lies inside one only if the one value is in each of its classes AND may stand
+ *                   behind it.
+ *
+ * Found on the host, before anything is enqueued and before the context is looked at, behind the `select` check and
+ * otherwise in the older calls' order, and HUF_ERROR_INVALID_ARGUMENT are besides the older calls' errors:
+ *
+ *   - an `anchors` bit beyond the three (the message names the value);
+ *   - HUFGPU_ANCHOR_BOL or HUFGPU_ANCHOR_EOL without delim_set, for the positions call (the records call always needs one);
+ *   - HUFGPU_ANCHOR_WORD without word_set;
+ *   - with HUFGPU_ANCHOR_EOL or HUFGPU_ANCHOR_WORD: sum(alt_lens) + n_alts > HUFGPU_FIND_PATTERN_MAX - each alternative
+ *     takes one more bit of the matcher's state (the message names the total).  HUFGPU_ANCHOR_BOL alone costs nothing.
+ *
+ * The identity: anchors = 0 enqueues exactly what hufgpu_find_any() / hufgpu_find_records_context() enqueue, and the sets
+ * are not looked at; the nine older calls launch what they always did.  With EOL or WORD the cost is that of a longest
+ * alternative one position longer; with BOL or WORD one kernel over the masks is added.  The records call with WORD needs a
+ * third mask next to the matches' and the delimiters': hufgpu_find_bytes()' kernel walks the stream a SECOND time for it,
+ * which grows two workspaces more; every other form stays at one walk.  Measured in DESIGN.md 5.21.
+ *
+ * OUT OF SCOPE: anchors per alternative ('^foo|bar$': make two calls, or one without anchors and look), patterns of
+ * variable length, and \b INSIDE a pattern.
+ */
+#define HUFGPU_ANCHOR_BOL   1u   /* '^' : the match starts where a record starts */
+#define HUFGPU_ANCHOR_EOL   2u   /* '$' : the match ends where a record ends     */
+#define HUFGPU_ANCHOR_WORD  4u   /* -w  : no word byte on either side            */
+/* -x is BOL | EOL */
+int hufgpu_find_any_anchored(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                             const uint64_t *d_block_offsets, uint64_t nblocks,
+                             const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                             const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                             const uint8_t delim_set[32], const uint8_t word_set[32], uint32_t anchors,
+                             uint64_t *d_pos, uint64_t pos_cap,
+                             uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                             uint32_t flags, void *stream);
+int hufgpu_find_records_anchored(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                                 const uint64_t *d_block_offsets, uint64_t nblocks,
+                                 const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                 const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                                 const uint8_t word_set[32], uint32_t anchors,
+                                 uint32_t select, uint32_t before, uint32_t after,
+                                 uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no, uint8_t *d_rec_sel, uint64_t rec_cap, uint32_t max_len,
+                                 uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                                 uint32_t flags, void *stream);
+
+/*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from
  * another rank, or encoded here by a caller that did not keep the 7 % of side data.  hufgpu_encode_sub() writes the
  * sub-index as a by-product of packing; these three rebuild exactly that - the same entries, entry for entry

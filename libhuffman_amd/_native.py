@@ -39,6 +39,7 @@ RELAXED_TREE = 1
 SEQUENTIAL = 2                  # hufgpu_decode_stream only
 RANGES_TILES = 4                # hufgpu_decode_ranges only: cut blocks by the sub-index tile (include/huffman_gpu.h, TILES)
 SELECT_INVERT = 1               # HUFGPU_SELECT_INVERT: hufgpu_find_records_select reports the records WITHOUT a match
+ANCHOR_BOL, ANCHOR_EOL, ANCHOR_WORD = 1, 2, 4   # HUFGPU_ANCHOR_*: the anchored calls' '^', '$' and -w
 FIND_PATTERN_MAX = 64           # HUFGPU_FIND_PATTERN_MAX: the bytes of a hufgpu_find_pattern pattern
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -78,7 +79,7 @@ hufgpu_batch_geometry hufgpu_encode_batch hufgpu_decode_batch hufgpu_decode_rang
 hufgpu_sub_index_from_raw hufgpu_decode_build_sub hufgpu_build_sub_index hufgpu_update_ranges
 hufgpu_append hufgpu_truncate hufgpu_ranges_counters hufgpu_gather hufgpu_find_bytes hufgpu_find_pattern hufgpu_find_records
 hufgpu_find_classes hufgpu_find_records_classes hufgpu_find_any hufgpu_find_records_any
-hufgpu_find_records_select hufgpu_find_records_context""".split()
+hufgpu_find_records_select hufgpu_find_records_context hufgpu_find_any_anchored hufgpu_find_records_anchored""".split()
 
 
 def so_path() -> str:
@@ -209,6 +210,11 @@ def load() -> C.CDLL:
     L.hufgpu_find_records_context.restype = C.c_int       # hufgpu_find_records_select's with `before`, `after` and `d_rec_sel`
     L.hufgpu_find_records_context.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                               vp, vp, vp, vp, u64, C.c_uint32, vp, vp, vp, C.c_uint32, vp]
+    L.hufgpu_find_any_anchored.restype = C.c_int          # hufgpu_find_any's with (delim_set, word_set, anchors) behind n_alts
+    L.hufgpu_find_any_anchored.argtypes = (L.hufgpu_find_any.argtypes[:11] + [vp, vp, C.c_uint32] + L.hufgpu_find_any.argtypes[11:])
+    L.hufgpu_find_records_anchored.restype = C.c_int      # hufgpu_find_records_context's with (word_set, anchors) behind n_alts
+    L.hufgpu_find_records_anchored.argtypes = (L.hufgpu_find_records_context.argtypes[:12] + [vp, C.c_uint32] +
+                                               L.hufgpu_find_records_context.argtypes[12:])
     _LIB = L
     return L
 

@@ -501,12 +501,34 @@ class GpuCodec:
                    "classes": ("hufgpu_find_classes", "hufgpu_find_records_classes"),
                    "any": ("hufgpu_find_any", "hufgpu_find_records_any")}
 
+    WORD_BYTES = b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789_"     # grep -w's: [A-Za-z0-9_]
+
     @staticmethod
-    def _find_route(pattern, ignore_case, delimiters=_NO_RECORDS, select=False):
+    def _find_route(pattern, ignore_case, delimiters=_NO_RECORDS, select=False, anchors=None):
         """(route, key, st): which of _FIND_CALLS serves `pattern` - "any" for an AnyOf (and, with `select`, for every
         pattern: it is the one alternative), "classes" for a list / tuple or with `ignore_case`, else "literal" -, the
         pattern's part of the C argument list, and the delimiters' byte_set (None when no `delimiters` are given: no records).
-        Raises what find_pattern and find_records raise for a pattern."""
+        Raises what find_pattern and find_records raise for a pattern.
+        `anchors`: the keywords (bol, eol, whole_line, word, word_bytes) of the calls that have them.  A fourth item then
+        comes back, (bits, word_set): the `anchors` of hufgpu_find_any_anchored / hufgpu_find_records_anchored - 0: the call
+        is the one it always was - and the word bytes' byte_set (None without `word`); any bit makes the route "any".  Raises
+        ValueError for `word_bytes` without `word` and for alternatives that leave no bit of the matcher's state for the
+        byte behind each of them (`eol`, `whole_line`, `word`)."""
+        if anchors is not None:
+            bol, eol, whole_line, word, word_bytes = anchors
+            if word_bytes is not None and not word:
+                raise ValueError("`word_bytes` says what `word` looks at: give `word=True` with it")
+            bits = ((_native.ANCHOR_BOL if bol or whole_line else 0) | (_native.ANCHOR_EOL if eol or whole_line else 0) |
+                    (_native.ANCHOR_WORD if word else 0))
+            ws = GpuCodec.byte_set(GpuCodec.WORD_BYTES if word_bytes is None else word_bytes) if word else None
+            route, key, st = GpuCodec._find_route(pattern, ignore_case, delimiters, select or bits != 0)
+            if bits & (_native.ANCHOR_EOL | _native.ANCHOR_WORD):
+                total = int(np.frombuffer(key[1], np.uint32).sum()) + key[2]
+                if total > _native.FIND_PATTERN_MAX:
+                    raise ValueError(f"the alternatives' lengths and one position behind each of the {key[2]} sum to {total}, "
+                                     f"above {_native.FIND_PATTERN_MAX}: `eol`, `whole_line` and `word` take a bit of the matcher's "
+                                     "state an alternative")
+            return route, key, st, (bits, ws)
         if select and not isinstance(pattern, GpuCodec.AnyOf):
             if isinstance(pattern, str):
                 raise TypeError("a pattern is a bytes-like object or a list / tuple of classes, not a str")
@@ -558,7 +580,8 @@ class GpuCodec:
     def find_pattern(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, max_positions: int = 0,
                      block_counts: bool = False, relaxed: bool = False, out: torch.Tensor | None = None,
-                     ignore_case: bool = False):
+                     ignore_case: bool = False, bol: bool = False, eol: bool = False, whole_line: bool = False,
+                     word: bool = False, word_bytes=None, delimiters=b"\n"):
         """The positions in the original data at which `pattern` (1 to FIND_PATTERN_MAX bytes) starts, overlapping
         occurrences included, on torch's current stream and without a synchronisation (hufgpu_find_pattern).  Returns
         what find_bytes returns, (positions, totals, block_errs, block_counts): a match counts for the block that holds
@@ -568,30 +591,41 @@ class GpuCodec:
         `ignore_case` makes classes of a literal's letters (hufgpu_find_classes): a match is a start p with data[p + k] in
         class k for every k.  A bytes-like pattern without `ignore_case` makes the literal call.
         A GpuCodec.AnyOf pattern looks for SEVERAL alternatives in the one walk (hufgpu_find_any): a start at which at least
-        one of them lies is reported once; which one is not reported.  `ignore_case` applies to every alternative."""
-        route, key, _ = self._find_route(pattern, ignore_case)
+        one of them lies is reported once; which one is not reported.  `ignore_case` applies to every alternative.
+        `bol`, `eol` ('^', '$'), `whole_line` (grep -x: both) and `word` (grep -w) keep the occurrences whose neighbours allow
+        it (hufgpu_find_any_anchored): the byte in front is absent or one of `delimiters`, the byte behind is, neither is one
+        of `word_bytes` ([A-Za-z0-9_] when not given).  The reported position is still the pattern's own start.  `delimiters`
+        matters with `bol`, `eol` or `whole_line` only; with none of the five set the call is the one it always was.  Raises
+        ValueError for `word_bytes` without `word`, and with `eol`, `whole_line` or `word` for alternatives whose lengths plus
+        one each exceed FIND_PATTERN_MAX."""
+        route, key, st, (anchors, ws) = self._find_route(pattern, ignore_case, anchors=(bol, eol, whole_line, word, word_bytes))
         max_positions = int(max_positions)
         pos = self._find_buffer(out, max_positions, torch.int64)
         head, tail, totals, errs, counts = self._find_args(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
                                                            block_counts, relaxed)
-        call = getattr(self.lib, self._FIND_CALLS[route][0])
+        if anchors:
+            key = key + (self.byte_set(delimiters), ws, anchors)
+        call = self.lib.hufgpu_find_any_anchored if anchors else getattr(self.lib, self._FIND_CALLS[route][0])
         err = call(*head, *key, pos.data_ptr() if max_positions else None, max_positions, *tail)
         self._check(err, "Failed to enqueue the search")
         return pos, totals, errs, counts
 
     def count_pattern(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                       sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, relaxed: bool = False,
-                      ignore_case: bool = False):
+                      ignore_case: bool = False, bol: bool = False, eol: bool = False, whole_line: bool = False,
+                      word: bool = False, word_bytes=None, delimiters=b"\n"):
         """How often `pattern` occurs in the original data: find_pattern without positions, enqueue-only.  Returns CUDA
-        tensors (totals[4], block_errs[nblocks]) as find_pattern does."""
+        tensors (totals[4], block_errs[nblocks]) as find_pattern does.  `bol` to `delimiters`: as for find_pattern."""
         _, totals, errs, _ = self.find_pattern(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
-                                               relaxed=relaxed, ignore_case=ignore_case)
+                                               relaxed=relaxed, ignore_case=ignore_case, bol=bol, eol=eol, whole_line=whole_line,
+                                               word=word, word_bytes=word_bytes, delimiters=delimiters)
         return totals, errs
 
     def find_records(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, delimiters=b"\n",
                      max_records: int = 0, max_len: int = 0, block_counts: bool = False, relaxed: bool = False, out=None,
                      ignore_case: bool = False, before: int = 0, after: int = 0, context: int | None = None,
+                     bol: bool = False, eol: bool = False, whole_line: bool = False, word: bool = False, word_bytes=None,
                      invert: bool = False, line_numbers: bool = False):
         """The records of the original data - the pieces between the bytes of `delimiters` (an iterable of ints or a
         `bytes`; empty: the data is one record) - that hold `pattern` at least once, each record ONCE, on torch's current
@@ -621,11 +655,18 @@ class GpuCodec:
         never reported.  Any of them non-zero makes the call hufgpu_find_records_context and appends one more tensor,
         behind the numbers: selected[max_records] uint8, 1 for a record of the answer itself and 0 for context (grep's ':'
         and '-'); a buffer for it may come last in `out`.  `context` next to `before` or `after`, a negative distance and one
-        above 2^32 - 1 are a ValueError.  With all three at their defaults nothing changes."""
+        above 2^32 - 1 are a ValueError.  With all three at their defaults nothing changes.
+        `bol`, `eol` (grep '^...', '...$'), `whole_line` (grep -x: both) and `word` (grep -w) select on the occurrences whose
+        neighbours allow it: the byte in front is absent or a delimiter, the byte behind is, neither is one of `word_bytes`
+        ([A-Za-z0-9_] when not given).  Every overlapping occurrence is tested, so `word` selects b"foofoo foo" for b"foo" as
+        GNU grep does.  Any of them makes the call hufgpu_find_records_anchored; everything else - `invert`, `line_numbers`,
+        the distances, what is returned - applies to that selection unchanged.  `word_bytes` without `word` is a ValueError,
+        and so are, with `eol`, `whole_line` or `word`, alternatives whose lengths plus one each exceed FIND_PATTERN_MAX."""
         before, after = self._find_context(before, after, context)
         widens = bool(before or after)
         select = bool(invert) or bool(line_numbers) or widens
-        route, key, st = self._find_route(pattern, ignore_case, delimiters, select)
+        route, key, st, (anchors, ws) = self._find_route(pattern, ignore_case, delimiters, select,
+                                                         (bol, eol, whole_line, word, word_bytes))
         max_records, max_len = int(max_records), int(max_len)
         out = tuple(out) if out is not None else (None, None)
         numbers = self._find_buffer(out[2] if len(out) > 2 else None, max_records, torch.int64) if line_numbers else None
@@ -636,7 +677,12 @@ class GpuCodec:
         head, tail, totals, errs, counts = self._find_args(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
                                                            block_counts, relaxed)
         ptrs = (pos.data_ptr() if max_records else None, lens.data_ptr() if max_records else None)
-        if widens:
+        if anchors:
+            err = self.lib.hufgpu_find_records_anchored(*head, st, *key, ws, anchors, _native.SELECT_INVERT if invert else 0, before,
+                                                        after, *ptrs, numbers.data_ptr() if line_numbers and max_records else None,
+                                                        selected.data_ptr() if widens and max_records else None, max_records, max_len,
+                                                        *tail)
+        elif widens:
             err = self.lib.hufgpu_find_records_context(*head, st, *key, _native.SELECT_INVERT if invert else 0, before, after, *ptrs,
                                                        numbers.data_ptr() if line_numbers and max_records else None,
                                                        selected.data_ptr() if max_records else None, max_records, max_len, *tail)
@@ -652,19 +698,23 @@ class GpuCodec:
     def count_records(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                       sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, delimiters=b"\n",
                       relaxed: bool = False, ignore_case: bool = False, before: int = 0, after: int = 0,
-                      context: int | None = None, invert: bool = False, line_numbers: bool = False):
+                      context: int | None = None, bol: bool = False, eol: bool = False, whole_line: bool = False,
+                      word: bool = False, word_bytes=None, invert: bool = False, line_numbers: bool = False):
         """How many records hold `pattern` (grep -c; with `invert` grep -v -c, but for the empty lines): find_records
         without positions, enqueue-only.  Returns CUDA tensors (totals[4], block_errs[nblocks]) as find_records does, and
         with `line_numbers` the empty tensor of numbers behind them.  `before`, `after`, `context`: the records that
-        find_records reports with them are counted, and the empty tensor of flags comes last."""
+        find_records reports with them are counted, and the empty tensor of flags comes last.  `bol`, `eol`, `whole_line`,
+        `word`, `word_bytes`: as for find_records (grep -c -w, grep -c -x)."""
         res = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
                                 delimiters, relaxed=relaxed, ignore_case=ignore_case, before=before, after=after, context=context,
+                                bol=bol, eol=eol, whole_line=whole_line, word=word, word_bytes=word_bytes,
                                 invert=invert, line_numbers=line_numbers)
         return (res[2], res[3]) + tuple(res[5:])
 
     def grep(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, sub_index: torch.Tensor,
              raw_size: int, blocksize: int, pattern, max_records: int, max_len: int, delimiters=b"\n",
              relaxed: bool = False, ignore_case: bool = False, before: int = 0, after: int = 0, context: int | None = None,
+             bol: bool = False, eol: bool = False, whole_line: bool = False, word: bool = False, word_bytes=None,
              invert: bool = False, line_numbers: bool = False):
         """The first `max_len` bytes of the first `max_records` records that hold `pattern`: find_records followed by
         gather, on torch's current stream and without a synchronisation.  Returns CUDA tensors (lines uint8 [max_records,
@@ -674,13 +724,15 @@ class GpuCodec:
         more tensor at the end, numbers int64 [max_records] as find_records gives them, -1 from row totals[1] on.
         `before`, `after`, `context` (grep -B, -A, -C): the rows around those records as well, as find_records reports them,
         and one more tensor behind the numbers, selected uint8 [max_records]: 1 for a row of the answer itself, 0 for a row of
-        context and from row totals[1] on."""
+        context and from row totals[1] on.
+        `bol`, `eol`, `whole_line`, `word`, `word_bytes` (grep '^...', '...$', -x, -w): as for find_records."""
         max_records, max_len = int(max_records), int(max_len)
         if max_len < 1:
             raise ValueError("grep needs max_len, the bytes of a row")
         found = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
                                   pattern, delimiters, max_records=max_records, max_len=max_len,
                                   relaxed=relaxed, ignore_case=ignore_case, before=before, after=after, context=context,
+                                  bol=bol, eol=eol, whole_line=whole_line, word=word, word_bytes=word_bytes,
                                   invert=invert, line_numbers=line_numbers)
         pos, lens, totals, block_errs = found[:4]
         written = torch.arange(max_records, device=self.tdev) < totals[1]

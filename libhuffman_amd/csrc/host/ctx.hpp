@@ -132,6 +132,10 @@ struct hufgpu_ctx {
     uint32_t *d_fcbits, *d_fccnt;
     TwoLevel fctx_scan;
     uint64_t *d_fctotals;
+    /* hufgpu_find_records_anchored with HUFGPU_ANCHOR_WORD: a third mask, the bytes that may stand in front of a match, and
+     * the tile counts that find_sub_kernel writes next to it (nobody reads them); no other call allocates them */
+    uint64_t faws_words, faws_tiles;
+    uint32_t *d_fabits, *d_fatcnt;
 
     /* the sub-index builders (kernels/sub_build.hpp): what their kernels hand to one another, per block and per chunk */
     uint64_t sbws_blocks, sbws_chunks;
@@ -270,6 +274,8 @@ static const ws_buf WS_FIND_REC_TILES[] = {DEV(d_frdcnt, n * sizeof(uint32_t)), 
 static const ws_buf WS_FIND_SEL[] = {DEV(d_fsel_first, n * sizeof(uint64_t))};
 static const ws_buf WS_FIND_CTX_WORDS[] = {DEV(d_fcbits, n * sizeof(uint32_t))};
 static const ws_buf WS_FIND_CTX_TILES[] = {DEV(d_fccnt, n * sizeof(uint32_t)), DEV(d_fctotals, 4 * sizeof(uint64_t))};
+static const ws_buf WS_FIND_ANC_WORDS[] = {DEV(d_fabits, n * sizeof(uint32_t))};
+static const ws_buf WS_FIND_ANC_TILES[] = {DEV(d_fatcnt, n * sizeof(uint32_t))};
 static const ws_buf WS_SB_BLOCKS[] = {DEV(d_sb_state, n * sizeof(uint32_t)), DEV(d_sb_pay, n * sizeof(uint64_t))};
 static const ws_buf WS_SB_CHUNKS[] = {DEV(d_sb_chunk_tot, n * sizeof(uint64_t)), DEV(d_sb_chunk_bits, n * sizeof(uint64_t))};
 static const ws_buf WS_UPD_BLOCKS[] = {
@@ -283,7 +289,7 @@ static const ws_buf WS_UPD_PIECES[] = {DEV(d_upiece, n * sizeof(uint32_t))};
  * block of many MiB and the range scratch take what they are asked for (grow_range_scratch adds its own eighth).
  * Soft groups report nothing: the caller has another way, or words the error itself. */
 enum { G_FIXED, G_ENCODE, G_CHUNK, G_DECODE, G_DISC_WGS, G_DISC_CANDS, G_BIG_LANES, G_BIG_SUB, G_BSTAGE, G_BATCH, G_RANGE,
-       G_RSCRATCH, G_GATHER_BLOCKS, G_GATHER_PARTS, G_FIND_WORDS, G_FIND_TILES, G_FIND_EDGES, G_FIND_REC_WORDS, G_FIND_REC_TILES, G_FIND_SEL, G_FIND_CTX_WORDS, G_FIND_CTX_TILES, G_SB_BLOCKS, G_SB_CHUNKS, G_UPD_BLOCKS,
+       G_RSCRATCH, G_GATHER_BLOCKS, G_GATHER_PARTS, G_FIND_WORDS, G_FIND_TILES, G_FIND_EDGES, G_FIND_REC_WORDS, G_FIND_REC_TILES, G_FIND_SEL, G_FIND_CTX_WORDS, G_FIND_CTX_TILES, G_FIND_ANC_WORDS, G_FIND_ANC_TILES, G_SB_BLOCKS, G_SB_CHUNKS, G_UPD_BLOCKS,
        G_UPD_PIECES, G_COUNT };
 #define ROWS(a) a, (int)(sizeof(a) / sizeof(a[0]))
 #define CAP(member) {offsetof(hufgpu_ctx, member), WS_NO_CAP}
@@ -313,6 +319,8 @@ static const ws_group WS[G_COUNT] = {
     {"find select", ROWS(WS_FIND_SEL), CAP(fsel_ws), WS_EXACT, false, NO_SCAN},
     {"find context words", ROWS(WS_FIND_CTX_WORDS), CAP(fcws_words), WS_DOUBLE, false, NO_SCAN},
     {"find context tiles", ROWS(WS_FIND_CTX_TILES), CAP(fcws_tiles), WS_DOUBLE, false, SCAN_AT(fctx_scan)},
+    {"find anchor words", ROWS(WS_FIND_ANC_WORDS), CAP(faws_words), WS_DOUBLE, false, NO_SCAN},
+    {"find anchor tiles", ROWS(WS_FIND_ANC_TILES), CAP(faws_tiles), WS_DOUBLE, false, NO_SCAN},
     {"sub-build blocks", ROWS(WS_SB_BLOCKS), CAP(sbws_blocks), WS_EIGHTH, false, NO_SCAN},
     {"sub-build chunks", ROWS(WS_SB_CHUNKS), CAP(sbws_chunks), WS_EIGHTH, false, NO_SCAN},
     {"update blocks", ROWS(WS_UPD_BLOCKS), CAP(uws_blocks), WS_EIGHTH, false, NO_SCAN},

@@ -2,7 +2,8 @@
    hufgpu_find_any give the positions of a set of byte values, of a pattern, of a pattern of sets, of any of several such
    patterns; hufgpu_find_records, hufgpu_find_records_classes, hufgpu_find_records_any and hufgpu_find_records_select give
    the records - the pieces between delimiters - that hold one (or do not), and their numbers; hufgpu_find_records_context
-   gives the records around them as well.  All enqueue-only.  A
+   gives the records around them as well; hufgpu_find_any_anchored and hufgpu_find_records_anchored are hufgpu_find_any and
+   the context call for the matches that begin or end at a record's or a word's edge.  All enqueue-only.  A
    wrapper describes its call in three structs; find_call checks them (find_check, no HIP call), fills the kernels'
    arguments and grows the workspace (find_fill) and enqueues the chain of kernels/find.hpp (find_enqueue).
    Part of hufgpu_api.hip (one translation unit). */
@@ -56,13 +57,23 @@ struct FindCtxCall {
     uint8_t *d_rec_sel;                     /* optional */
 };
 
+/* what hufgpu_find_any_anchored and hufgpu_find_records_anchored have beyond their older calls, with anchors != 0: the two
+ * boundary sets that the anchors, delim_set and word_set come to (find_anc_sets) */
+struct FindAncCall {
+    uint32_t anchors;
+    uint8_t front[32];                      /* BOL / WORD: the bytes that may stand in front of a match */
+    uint8_t behind[32];                     /* EOL / WORD: ... and behind one */
+};
+
 /* What is looked for: `who` words the errors, `key` is the set (plen = 0) or the pattern of plen bytes, `key_name` its name;
  * rec is NULL but for the records' calls.  cls is NULL but for the class calls: then `key` is the caller's array of plen
  * classes, which find_call only checks for NULL and never reads - its wrapper has read it -, and cls is the table made
  * from it.  alt is NULL but for the any-of calls: then cls is alt's table (several alternatives in its 64 bits), plen is the
  * LONGEST alternative's length - what the edges workspace and the seam launch follow - and alt goes to the kernels.
  * sel is NULL but for the select and the context call: the any-of records' call with up to three launches more.
- * cx is NULL but for the context call, which is the select call with a dilation of the selected records' mask. */
+ * cx is NULL but for the context call, which is the select call with a dilation of the selected records' mask.
+ * anc is NULL but for the anchored calls with an anchor: then alt's table holds one position more an alternative when
+ * the byte behind a match is tested, and find_anchor_kernel runs when the byte in front is. */
 struct FindKey {
     const char *who, *key_name;
     const uint8_t *key;
@@ -72,10 +83,18 @@ struct FindKey {
     FindAltArgs *alt;
     const FindSelCall *sel;
     const FindCtxCall *cx;
+    const FindAncCall *anc;
 };
 
 /* does the context call widen the answer: with both distances 0 it is the select call, maybe with flags */
 static bool find_widens(const FindKey &k) { return k.cx && (k.cx->before | k.cx->after) != 0u; }
+
+/* is the byte in front of a match tested (find_anchor_kernel), the byte behind it (a table position and find_anc_seam_kernel),
+ * and does the call need a third mask: the records' own delimiter mask cannot be the boundary mask of a word, and a records
+ * walk has room for one set next to the table, so find_sub_kernel walks the stream once more with the boundary set */
+static bool find_anc_front(const FindKey &k) { return k.anc && (k.anc->anchors & (HUFGPU_ANCHOR_BOL | HUFGPU_ANCHOR_WORD)) != 0u; }
+static bool find_anc_behind(const FindKey &k) { return k.anc && (k.anc->anchors & (HUFGPU_ANCHOR_EOL | HUFGPU_ANCHOR_WORD)) != 0u; }
+static bool find_anc_third(const FindKey &k) { return k.rec && k.anc && (k.anc->anchors & HUFGPU_ANCHOR_WORD) != 0u; }
 
 /* the layout's blocks in chunks, mask words and tiles */
 struct FindGeometry {
@@ -129,7 +148,9 @@ static int find_fill(hufgpu_ctx_t *ctx, const FindStream &in, const FindOut &out
     const uint64_t nwords = in.nblocks * g.wpb, ntiles = in.nblocks * g.tpb;
     int rc = ensure_find_ws(ctx, nwords, ntiles);
     if (!rc && k.plen > 1) rc = grow_ws(ctx, G_FIND_EDGES, ntiles);                 /* (one byte has no seams: no edges) */
-    if (!rc && k.rec) rc = grow_ws2(ctx, G_FIND_REC_WORDS, nwords, G_FIND_REC_TILES, ntiles);
+    const bool front = find_anc_front(k);                           /* (the positions call then walks as a records call does) */
+    if (!rc && (k.rec || front)) rc = grow_ws2(ctx, G_FIND_REC_WORDS, nwords, G_FIND_REC_TILES, ntiles);
+    if (!rc && find_anc_third(k)) rc = grow_ws2(ctx, G_FIND_ANC_WORDS, nwords, G_FIND_ANC_TILES, ntiles);
     if (!rc && k.sel && k.sel->d_rec_no && out.cap > 0) rc = grow_ws(ctx, G_FIND_SEL, 1);
     if (!rc && find_widens(k)) rc = grow_ws2(ctx, G_FIND_CTX_WORDS, nwords, G_FIND_CTX_TILES, ntiles);
     if (rc) return rc;
@@ -138,7 +159,7 @@ static int find_fill(hufgpu_ctx_t *ctx, const FindStream &in, const FindOut &out
     FindArgs &fa = pa.f;
     fa.s = sub_stream_args(in.d_stream, in.stream_len, in.d_block_offsets, in.nblocks, in.d_sub_index, in.raw_size, g.blocksize, flags);
     fa.cpb = (uint32_t)g.cpb;
-    const uint8_t *set = k.rec ? k.rec->delim_set : k.plen == 0 ? k.key : NULL;    /* the delimiters, or the values looked for */
+    const uint8_t *set = k.rec ? k.rec->delim_set : front ? k.anc->front : k.plen == 0 ? k.key : NULL;  /* the delimiters, the boundary bytes, or the values looked for */
     for (int i = 0; set && i < 32; i++) fa.set[i >> 2] |= (uint32_t)set[i] << (8 * (i & 3));
     for (uint32_t i = 0; !k.cls && i < k.plen; i++) pa.pat[i >> 2] |= (uint32_t)k.key[i] << (8 * (i & 3));
     if (k.plen) {
@@ -166,21 +187,40 @@ static int find_fill(hufgpu_ctx_t *ctx, const FindStream &in, const FindOut &out
         ra.dscan.total = ctx->d_frdtotal;
         ra.len = k.rec->d_len;
         ra.clip = k.rec->max_len ? k.rec->max_len : 0xffffffffu;
+    } else if (front) {
+        ra.dbits = ctx->d_frdbits;
+        ra.dcnt = ctx->d_frdcnt;
     }
     return HUFE_OK;
 }
 
 /* the walk of the stream and, for a pattern of two bytes or more, the seams of its tiles: the one place where a route
  * chooses its kernels.  The any-of table goes with the launches' own arguments. */
-static void find_enqueue_walk(const FindKey &k, const FindRecArgs &ra, dim3 walk, dim3 seams, hipStream_t s)
+static void find_enqueue_walk(hufgpu_ctx_t *ctx, const FindKey &k, const FindRecArgs &ra, dim3 walk, dim3 seams, dim3 tiles, hipStream_t s)
 {
     const dim3 wt(FIND_THREADS), st(FIND_SEAM_THREADS);
     const bool rec = k.rec != NULL, seam = k.plen > 1;
     if (k.alt) {
         k.alt->r = ra;
-        if (rec) find_rec_alt_sub_kernel<<<walk, wt, 0, s>>>(*k.alt);
+        const bool front = find_anc_front(k), third = find_anc_third(k);
+        if (rec || front) find_rec_alt_sub_kernel<<<walk, wt, 0, s>>>(*k.alt);
         else find_alt_sub_kernel<<<walk, wt, 0, s>>>(*k.alt);
-        if (seam) find_alt_seam_kernel<<<seams, st, 0, s>>>(*k.alt);
+        if (third) {
+            /* the bytes' walk with the boundary set, into a mask and tile counts of its own: the same checks, so the same
+             * statuses a second time, and no word of the first walk is touched */
+            FindArgs ba = ra.p.f;
+            memset(ba.set, 0, sizeof(ba.set));
+            for (int i = 0; i < 32; i++) ba.set[i >> 2] |= (uint32_t)k.anc->front[i] << (8 * (i & 3));
+            ba.bitmap = ctx->d_fabits;
+            ba.tcnt = ctx->d_fatcnt;
+            find_sub_kernel<<<walk, wt, 0, s>>>(ba);
+        }
+        if (seam && find_anc_behind(k)) find_anc_seam_kernel<<<seams, st, 0, s>>>(*k.alt);
+        else if (seam) find_alt_seam_kernel<<<seams, st, 0, s>>>(*k.alt);
+        if (front) {
+            const FindAnchorArgs fa = {ra.p.f, third ? ctx->d_fabits : ra.dbits};
+            find_anchor_kernel<<<tiles, dim3(FIND_EMIT_THREADS), 0, s>>>(fa);
+        }
     } else if (k.cls) {
         const FindClsArgs ca = {ra, *k.cls};
         if (rec) find_rec_cls_sub_kernel<<<walk, wt, 0, s>>>(ca);
@@ -211,7 +251,7 @@ static int find_enqueue(hufgpu_ctx_t *ctx, const FindOut &out, const FindKey &k,
         HIP_OK(ctx, hipMemsetAsync(ra.rcnt, 0, fa.ntiles * sizeof(uint32_t), s));
         if (widens) HIP_OK(ctx, hipMemsetAsync(ctx->d_fctotals, 0, 4 * sizeof(uint64_t), s));
     }
-    find_enqueue_walk(k, ra, walk, seams, s);
+    find_enqueue_walk(ctx, k, ra, walk, seams, tiles, s);
     const uint32_t *sbits = ra.rbits;                               /* the selected records' mask, whatever the emit kernel reads */
     if (k.rec) {
         /* from the walk's two masks to the records' starts and their counts by tile; scan, finish and emit then take the
@@ -291,7 +331,7 @@ extern "C" int hufgpu_find_bytes(hufgpu_ctx_t *ctx, const void *d_stream, uint64
 {
     const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
     const FindOut out = {d_pos, pos_cap, d_block_counts, d_totals, d_block_errs};
-    const FindKey k = {"find_bytes", "set", set, 0, NULL, NULL, NULL, NULL, NULL};
+    const FindKey k = {"find_bytes", "set", set, 0, NULL, NULL, NULL, NULL, NULL, NULL};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -303,7 +343,7 @@ extern "C" int hufgpu_find_pattern(hufgpu_ctx_t *ctx, const void *d_stream, uint
     if (pattern && find_pattern_len(ctx, "find_pattern", pattern_len)) return HUFE_ARGUMENT;
     const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
     const FindOut out = {d_pos, pos_cap, d_block_counts, d_totals, d_block_errs};
-    const FindKey k = {"find_pattern", "pattern", pattern, pattern_len, NULL, NULL, NULL, NULL, NULL};
+    const FindKey k = {"find_pattern", "pattern", pattern, pattern_len, NULL, NULL, NULL, NULL, NULL, NULL};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -317,15 +357,17 @@ extern "C" int hufgpu_find_records(hufgpu_ctx_t *ctx, const void *d_stream, uint
     const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
     const FindOut out = {d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs};
     const FindRecCall rec = {delim_set, d_rec_len, max_len};
-    const FindKey k = {"find_records", "pattern", pattern, pattern_len, &rec, NULL, NULL, NULL, NULL};
+    const FindKey k = {"find_records", "pattern", pattern, pattern_len, &rec, NULL, NULL, NULL, NULL, NULL};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
 /* One alternative's `len` classes into the transposed table (kernels/find.hpp): position k at bit hi - k of m[v], for
  * every value v of the class; `full` gets every position's bit, `first` that of the LAST position.  No class may be empty
- * or hold a delimiter; `of` names the alternative in those errors ("the pattern": the class calls' only one). */
+ * or hold a delimiter; `of` names the alternative in those errors ("the pattern": the class calls' only one).
+ * `behind` (the anchored calls): one position more, at bit hi - len, with that class - an internal one, which may be empty
+ * or hold a delimiter - and the automaton starts there. */
 static int find_table_add(hufgpu_ctx_t *ctx, const char *who, const char *of, const uint8_t *cl, uint32_t len, uint32_t hi,
-                          const uint8_t *delim_set, FindClsTable *t)
+                          const uint8_t *delim_set, FindClsTable *t, const uint8_t *behind = NULL)
 {
     for (uint32_t k = 0; k < len; k++, cl += 32) {
         const uint32_t bit = hi - k;
@@ -340,7 +382,14 @@ static int find_table_add(hufgpu_ctx_t *ctx, const char *who, const char *of, co
         if (!any) return find_bad(ctx, "%s: class %u of %s is empty: it matches nothing", who, k, of);
         t->full[bit >> 5] |= 1u << (bit & 31u);
     }
-    const uint32_t last = hi - (len - 1u);
+    uint32_t last = hi - (len - 1u);
+    if (behind) {
+        last--;
+        for (uint32_t v = 0; v < 256; v++) {
+            if ((behind[v >> 3] >> (v & 7)) & 1) t->m[v][last >> 5] |= 1u << (last & 31u);
+        }
+        t->full[last >> 5] |= 1u << (last & 31u);
+    }
     t->first[last >> 5] |= 1u << (last & 31u);
     return HUFE_OK;
 }
@@ -364,7 +413,7 @@ extern "C" int hufgpu_find_classes(hufgpu_ctx_t *ctx, const void *d_stream, uint
     if (classes && find_cls_table(ctx, "find_classes", classes, pattern_len, NULL, &t)) return HUFE_ARGUMENT;
     const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
     const FindOut out = {d_pos, pos_cap, d_block_counts, d_totals, d_block_errs};
-    const FindKey k = {"find_classes", "classes", classes, pattern_len, NULL, &t, NULL, NULL, NULL};
+    const FindKey k = {"find_classes", "classes", classes, pattern_len, NULL, &t, NULL, NULL, NULL, NULL};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -379,16 +428,17 @@ extern "C" int hufgpu_find_records_classes(hufgpu_ctx_t *ctx, const void *d_stre
     const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
     const FindOut out = {d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs};
     const FindRecCall rec = {delim_set, d_rec_len, max_len};
-    const FindKey k = {"find_records_classes", "classes", classes, pattern_len, &rec, &t, NULL, NULL, NULL};
+    const FindKey k = {"find_records_classes", "classes", classes, pattern_len, &rec, &t, NULL, NULL, NULL, NULL};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
 /* The any-of calls' own checks - 1 to 64 alternatives, none of length 0, lengths that sum to at most 64, and
  * find_table_add's - and their table (kernels/find.hpp, FindAltArgs: alternative 0 at the bits 63 ... 64 - len_0,
  * alternative 1 below it).  `classes` and `alt_lens` are not NULL; the total is looked at before `classes` is read.
- * *maxlen: the longest alternative's length. */
+ * *maxlen: the longest alternative's length.  `behind` (the anchored calls): every alternative gets one position more, that
+ * class, which takes a bit of the state and counts into *maxlen. */
 static int find_alt_table(hufgpu_ctx_t *ctx, const char *who, const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
-                          const uint8_t *delim_set, FindAltArgs *t, uint32_t *maxlen)
+                          const uint8_t *delim_set, FindAltArgs *t, uint32_t *maxlen, const uint8_t *behind = NULL)
 {
     if (n_alts == 0 || n_alts > HUFGPU_FIND_PATTERN_MAX)
         return find_bad(ctx, "%s: n_alts %u is not 1 to %d", who, n_alts, HUFGPU_FIND_PATTERN_MAX);
@@ -400,34 +450,38 @@ static int find_alt_table(hufgpu_ctx_t *ctx, const char *who, const uint8_t *cla
     if (total > HUFGPU_FIND_PATTERN_MAX)
         return find_bad(ctx, "%s: the lengths of the %u alternatives sum to %llu, above %d", who, n_alts, (unsigned long long)total,
                         HUFGPU_FIND_PATTERN_MAX);
+    if (behind && total + n_alts > HUFGPU_FIND_PATTERN_MAX)
+        return find_bad(ctx, "%s: the lengths of the %u alternatives and one boundary position each sum to %llu, above %d", who, n_alts,
+                        (unsigned long long)(total + n_alts), HUFGPU_FIND_PATTERN_MAX);
     memset(t, 0, sizeof(*t));
     t->n_alts = n_alts;
     *maxlen = 0;
     uint32_t hi = 63;
     for (uint32_t j = 0; j < n_alts; j++) {
-        const uint32_t len = alt_lens[j];
+        const uint32_t len = alt_lens[j], bits = len + (behind ? 1u : 0u);
         char of[32];
         snprintf(of, sizeof(of), "alternative %u", j);
-        if (find_table_add(ctx, who, of, classes, len, hi, delim_set, &t->t)) return HUFE_ARGUMENT;
+        if (find_table_add(ctx, who, of, classes, len, hi, delim_set, &t->t, behind)) return HUFE_ARGUMENT;
         t->starts[hi >> 5] |= 1u << (hi & 31u);
-        t->hl[j] = (uint16_t)(hi | (len << 8));
-        if (len > *maxlen) *maxlen = len;
+        t->hl[j] = (uint16_t)(hi | (bits << 8));
+        if (bits > *maxlen) *maxlen = bits;
         classes += 32u * len;
-        hi -= len;                                                  /* (wraps behind the last alternative of a total of 64: not used again) */
+        hi -= bits;                                                 /* (wraps behind the last alternative of a total of 64: not used again) */
     }
     return HUFE_OK;
 }
 
-/* the four any-of wrappers' call: the table, when both arrays are there (find_check words a missing one), then find_call */
+/* the six any-of wrappers' call: the table, when both arrays are there (find_check words a missing one), then find_call */
 static int find_alt_call(hufgpu_ctx_t *ctx, const char *who, const FindStream &in, const FindOut &out, const uint8_t *classes,
                          const uint32_t *alt_lens, uint32_t n_alts, const FindRecCall *rec, const FindSelCall *sel, const FindCtxCall *cx,
-                         uint32_t flags, void *stream)
+                         uint32_t flags, void *stream, const FindAncCall *anc = NULL)
 {
     FindAltArgs t;
     uint32_t maxlen = 0;
     const bool both = classes && alt_lens;
-    if (both && find_alt_table(ctx, who, classes, alt_lens, n_alts, rec ? rec->delim_set : NULL, &t, &maxlen)) return HUFE_ARGUMENT;
-    const FindKey k = {who, "classes, alt_lens", both ? classes : NULL, maxlen, rec, &t.t, &t, sel, cx};
+    const uint8_t *behind = anc && (anc->anchors & (HUFGPU_ANCHOR_EOL | HUFGPU_ANCHOR_WORD)) ? anc->behind : NULL;
+    if (both && find_alt_table(ctx, who, classes, alt_lens, n_alts, rec ? rec->delim_set : NULL, &t, &maxlen, behind)) return HUFE_ARGUMENT;
+    const FindKey k = {who, "classes, alt_lens", both ? classes : NULL, maxlen, rec, &t.t, &t, sel, cx, anc};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -485,4 +539,62 @@ extern "C" int hufgpu_find_records_context(hufgpu_ctx_t *ctx, const void *d_stre
     const FindCtxCall cx = {before, after, d_rec_sel};
     const bool plain = (before | after) == 0u && !d_rec_sel;        /* the select call, by its launches */
     return find_alt_call(ctx, "find_records_context", in, out, classes, alt_lens, n_alts, &rec, &sel, plain ? NULL : &cx, flags, stream);
+}
+
+/* The anchored calls' own checks, behind the `select` check and in front of the older calls': a bit that is no anchor, BOL or
+ * EOL without delimiters (the positions call; a records call without them is find_check's to word), WORD without word bytes.
+ * Then the two boundary sets: in front of a match BOL asks for a delimiter and WORD for a byte that is no word byte, both
+ * for a byte of both kinds; behind it EOL and WORD ask for the same.  A set that no anchor asks for is not used. */
+static int find_anc_sets(hufgpu_ctx_t *ctx, const char *who, uint32_t anchors, const uint8_t *delim_set, const uint8_t *word_set, bool rec,
+                         FindAncCall *anc)
+{
+    const uint32_t all = HUFGPU_ANCHOR_BOL | HUFGPU_ANCHOR_EOL | HUFGPU_ANCHOR_WORD;
+    if (anchors & ~all)
+        return find_bad(ctx, "%s: anchors 0x%x has a bit other than HUFGPU_ANCHOR_BOL, HUFGPU_ANCHOR_EOL and HUFGPU_ANCHOR_WORD", who, anchors);
+    if (!rec && (anchors & (HUFGPU_ANCHOR_BOL | HUFGPU_ANCHOR_EOL)) && !delim_set)
+        return find_bad(ctx, "%s: HUFGPU_ANCHOR_BOL and HUFGPU_ANCHOR_EOL need the delim_set (anchors 0x%x)", who, anchors);
+    if ((anchors & HUFGPU_ANCHOR_WORD) && !word_set)
+        return find_bad(ctx, "%s: HUFGPU_ANCHOR_WORD needs the word_set (anchors 0x%x)", who, anchors);
+    anc->anchors = anchors;
+    for (int i = 0; i < 32; i++) {
+        const uint8_t d = delim_set ? delim_set[i] : 0, nw = (anchors & HUFGPU_ANCHOR_WORD) ? (uint8_t)~word_set[i] : 0xff;
+        anc->front[i] = (uint8_t)(((anchors & HUFGPU_ANCHOR_BOL) ? d : 0xff) & nw);
+        anc->behind[i] = (uint8_t)(((anchors & HUFGPU_ANCHOR_EOL) ? d : 0xff) & nw);
+    }
+    return HUFE_OK;
+}
+
+extern "C" int hufgpu_find_any_anchored(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                        uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                        const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts, const uint8_t delim_set[32],
+                                        const uint8_t word_set[32], uint32_t anchors, uint64_t *d_pos, uint64_t pos_cap,
+                                        uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream)
+{
+    FindAncCall anc;
+    if (anchors && find_anc_sets(ctx, "find_any_anchored", anchors, delim_set, word_set, false, &anc)) return HUFE_ARGUMENT;
+    const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
+    const FindOut out = {d_pos, pos_cap, d_block_counts, d_totals, d_block_errs};
+    return find_alt_call(ctx, "find_any_anchored", in, out, classes, alt_lens, n_alts, NULL, NULL, NULL, flags, stream, anchors ? &anc : NULL);
+}
+
+extern "C" int hufgpu_find_records_anchored(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                            uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                            const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                                            const uint8_t word_set[32], uint32_t anchors, uint32_t select, uint32_t before, uint32_t after,
+                                            uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no, uint8_t *d_rec_sel, uint64_t rec_cap,
+                                            uint32_t max_len, uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                                            uint32_t flags, void *stream)
+{
+    if (select & ~HUFGPU_SELECT_INVERT)
+        return find_bad(ctx, "find_records_anchored: select 0x%x has a bit other than HUFGPU_SELECT_INVERT", select);
+    FindAncCall anc;
+    if (anchors && find_anc_sets(ctx, "find_records_anchored", anchors, delim_set, word_set, true, &anc)) return HUFE_ARGUMENT;
+    const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
+    const FindOut out = {d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs};
+    const FindRecCall rec = {delim_set, d_rec_len, max_len};
+    const FindSelCall sel = {select, d_rec_no};
+    const FindCtxCall cx = {before, after, d_rec_sel};
+    const bool plain = (before | after) == 0u && !d_rec_sel;        /* the select call, by its launches */
+    return find_alt_call(ctx, "find_records_anchored", in, out, classes, alt_lens, n_alts, &rec, &sel, plain ? NULL : &cx, flags, stream,
+                         anchors ? &anc : NULL);
 }

@@ -20,6 +20,14 @@
                                    of its own) -> find_rec_ctx, whose second mask the rest of the chain takes; with d_rec_sel
                                    find_ctx_emit / find_ctx_emit_no in the place of the emit kernel.  before = after = 0:
                                    the select call's launches but for that emit kernel
+   hufgpu_find_any_anchored        anchors = 0: hufgpu_find_any's chain.  EOL / WORD: find_anc_seam in the place of
+                                   find_alt_seam (the table has one position more an alternative).  BOL / WORD: the walk is
+                                   find_rec_alt_sub with the boundary set in the delimiters' place, and find_anchor runs
+                                   behind the seam kernel; then find_scan -> find_finish [-> find_emit] as ever
+   hufgpu_find_records_anchored    anchors = 0: the context call's chain.  EOL / WORD: find_anc_seam.  BOL alone:
+                                   find_anchor on the delimiters' mask, behind the seam kernel and in front of dscan / mark.
+                                   WORD: find_sub walks the stream a second time, behind find_rec_alt_sub, for a third mask -
+                                   the bytes that may stand in front of a match -, which find_anchor takes
    RECORDS = find_rec_dscan -> find_rec_mark -> find_scan -> find_finish [-> find_rec_emit]; no seam kernel for 1 byte
 
    The walk: find_sub_body, the seven *_sub kernels
@@ -47,9 +55,12 @@
                  length - 1 bytes, the edges are that many, and the walk sets the starts at which the LONGEST
                  alternative fits in the tile, whichever alternative lies there;
        records   next to all that a DELIMITER mask word a group - the lane's 32 bytes against the delimiter set in
-                 LDS - and the tile's delimiter count.
+                 LDS - and the tile's delimiter count;
+       anchored  no walk kernel of its own.  The byte BEHIND a match needs no kernel: it is one position more an
+                 alternative in the table - its class the delimiters, the bytes that are no word byte, or both -, plen is
+                 the longest alternative + 1, and edges, warm-up and the walk / seam split follow it as they always did.
 
-   The seams: find_seam_kernel, find_cls_seam_kernel, find_alt_seam_kernel
+   The seams: find_seam_kernel, find_cls_seam_kernel, find_alt_seam_kernel, find_anc_seam_kernel
      One wave a tile, a lane a start among the tile's last plen - 1 (plen: the pattern's length, the LONGEST one of
      alternatives): the matches that leave their tile.  find_seam_lane locates the lane's start, find_seam_candidate
      answers for one pattern whether it lies there, and it holds the layout walk, the only one there is: byte k comes
@@ -58,7 +69,13 @@
      dropped when it would end behind raw_size or when any block it touches is not served.  The any-of kernel asks once
      per alternative - a short one that ends inside the tile included - until one lies there: one bit and one count a
      start however many do.  find_seam_end ORs the starts into the start tile's mask words and adds them to its count,
-     BEFORE the scan.
+     BEFORE the scan.  find_anc_seam_kernel is the any-of kernel for tables with a boundary position: the one case that a
+     table cannot express is the match that ends where the data ends - no byte to look up -, and that start lies among its
+     tile's last plen - 1, so the kernel asks for such an alternative without its last position.
+     find_anchor_kernel    the byte in FRONT of a match, behind the seam kernel: a wave a tile, a lane a word,
+                           m &= (b << 1) | carry with b the walk's mask of the bytes that may stand there; the carry comes
+                           from the lane below, the tile in front, the block in front (0 when that one is not served, 1
+                           at byte 0); then the tile's count anew.
 
    Behind them
      find_scan_kernel      the tile counts, gated by their block's status, summed by the two-level / ticket scan of
@@ -602,7 +619,15 @@ __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_cls_seam_kernel(FindCl
  * EVERY alternative, a short one that ends inside the tile included: the tile's tail slot holds all the bytes it needs.
  * The wave goes through the alternatives together (hi_j and len_j are the wave's, in scalar registers); a lane takes part
  * until one alternative lies at its start, and then sets ONE bit and counts ONE match. */
-__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_alt_seam_kernel(FindAltArgs aa)
+/* find_anc_seam_kernel: the positions to ask for of an alternative of `len`, its boundary position included - without that
+ * one when the data ends where the boundary byte would lie */
+__device__ __forceinline__ uint32_t find_anc_len(const FindArgs &a, const FindSeam &m, uint32_t len)
+{
+    return m.pos + len == a.s.raw_size + 1u ? len - 1u : len;
+}
+
+template <bool ANC>
+__device__ __forceinline__ void find_alt_seam_body(const FindAltArgs &aa)
 {
     __shared__ uint32_t s_key[FIND_CLS_WORDS];
     __shared__ uint32_t s_hl[FIND_PAT_MAX];
@@ -622,9 +647,63 @@ __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_alt_seam_kernel(FindAl
     for (uint32_t j = 0; j < aa.n_alts; j++) {
         const uint32_t hl = uni32(s_hl[j]), hi = hl & 63u;
         if (m.lane < m.ne && !hit && ((((hi >> 5) ? m1 : m0) >> (hi & 31u)) & 1u) != 0u)
-            hit = find_seam_candidate<true>(pa, s_key, m, hl >> 8, hi);
+            hit = find_seam_candidate<true>(pa, s_key, m, ANC ? find_anc_len(pa.f, m, hl >> 8) : hl >> 8, hi);
     }
     find_seam_end(pa.f, m, hit);
+}
+__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_alt_seam_kernel(FindAltArgs aa) { find_alt_seam_body<false>(aa); }
+
+/* The anchored calls with HUFGPU_ANCHOR_EOL or HUFGPU_ANCHOR_WORD: every alternative ends with one position more, the class
+ * of the bytes that may stand BEHIND a match, so the walk and the kernel above need not know of anchors - but for the match
+ * that ends where the data ends: there is no byte to look up, and nothing behind the data stands in the way.  That start
+ * lies among the last plen - 1 of its tile (plen - 1 is the longest alternative's own length now), so it is this kernel's:
+ * an alternative whose boundary position would be the byte AT raw_size is asked for without it (len_j >= 1 positions are
+ * left).  Every other start is find_alt_seam_kernel's word for word. */
+__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_anc_seam_kernel(FindAltArgs aa) { find_alt_seam_body<true>(aa); }
+
+/* The anchored calls with HUFGPU_ANCHOR_BOL or HUFGPU_ANCHOR_WORD, behind the seam kernel and in front of everything that
+ * reads the match mask: a wave = one tile, a lane = one word.  `bound` is a mask of the walk's, a bit a byte: may this byte
+ * stand in FRONT of a match - the delimiters' mask for BOL in a records call, for WORD there the mask that find_sub_kernel
+ * writes in a second walk with that set (a records walk has room for ONE set next to the table, and the record kernels need
+ * the delimiters' there), and for the positions call the records' walk's "delimiter" mask, written with the boundary set in the place
+ * of the delimiters.  A start stays when the byte in front of it is one of those: m &= (bound << 1) | carry, the carry being
+ * the bit of the symbol in front of the lane's word - the lane below's, and for lane 0 the last symbol of the tile in front
+ * (a full one), for a block's first tile that of block b - 1 (a full block; its row ends where it ends), 1 at byte 0, where
+ * nothing stands in front, and 0 when block b - 1 is not served: left out on doubt.  Then the tile's count anew: nobody else
+ * writes tcnt behind the seam kernel.  A tile without a start, or of a block that is not served, is left as it is. */
+struct FindAnchorArgs {
+    FindArgs f;
+    const uint32_t *bound;                  /* [nblocks][wpb] */
+};
+__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_anchor_kernel(FindAnchorArgs aa)
+{
+    const FindArgs &a = aa.f;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t i = find_tile_index<FIND_EMIT_THREADS>();
+    if (i >= a.ntiles) return;
+    const auto [b, t, blen] = find_tile(a, i);
+    if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK || a.tcnt[i] == 0u) return;
+    const uint64_t g = t * 64u + lane;
+    const bool inside = g * DSUB_SPL < blen;
+    const uint32_t w = inside ? aa.bound[b * a.wpb + g] : 0u;
+    uint32_t c0;                                                    /* may the byte in front of the tile stand there (the wave's) */
+    if (i == 0) {
+        c0 = 1u;
+    } else if (t != 0) {
+        c0 = aa.bound[b * a.wpb + t * 64u - 1u] >> 31;              /* (the tile in front is a full one) */
+    } else if (a.errs[b - 1] != HUFE_OK) {
+        c0 = 0u;
+    } else {
+        const uint64_t last = a.s.bsize - 1u;                       /* (a block with a block behind it is a full one) */
+        c0 = (aa.bound[(b - 1) * a.wpb + (last >> 5)] >> ((uint32_t)last & 31u)) & 1u;
+    }
+    const uint32_t below = wave_up1_u32(w);                         /* (by every lane: a lane that sits out of a DPP move is not read) */
+    const uint32_t carry = lane == 0 ? c0 : below >> 31;
+    uint32_t *word = a.bitmap + b * a.wpb + g;
+    const uint32_t m = inside ? *word & ((w << 1) | carry) : 0u;
+    if (inside) *word = m;
+    const uint32_t cnt = wave_total_u32((uint32_t)__popc(m));
+    if (lane == 0) a.tcnt[i] = cnt;
 }
 
 /* a workgroup = one SCAN_GROUP of tiles, as gather_scan_kernel sums the part counts */
