@@ -1,13 +1,8 @@
-"""hufgpu_find_any_anchored and hufgpu_find_records_anchored: the symbols, their declarations, their argument checks, the NumPy
-models of their results (tests/find_anchor_model.py) and the `bol` / `eol` / `whole_line` / `word` / `word_bytes` keywords of
-GpuCodec (no GPU needed).
-
-As for the older find calls argument errors are found before anything is enqueued and before the context is looked at, so
-they can be provoked with a NULL context and made-up device pointers (never dereferenced); hufgpu_last_error(NULL) says which
-check spoke.  The argument cases of hufgpu_find_any (tests/test_find_any_args.py) and of hufgpu_find_records_context
-(tests/test_find_context_args.py) are repeated here with the `find_any_anchored:` / `find_records_anchored:` wording, with and
-without anchors.  The models are checked against Python's `re`: look-behind and look-ahead assertions around an alternative
-for the positions, `bytes.split` and the same expression a piece for the records.
+"""hufgpu_find_any_anchored and hufgpu_find_records_anchored: their declarations, the checks of the arguments of their own, the
+NumPy models of their results (tests/find_anchor_model.py) and the `bol` / `eol` / `whole_line` / `word` / `word_bytes`
+keywords of GpuCodec (no GPU needed).  The checks they share with the other calls of the search family, with and without
+anchors, are the functions of tests/find_args_cases.py.  The models are checked against Python's `re`: look-behind and look-ahead
+assertions around an alternative for the positions, `bytes.split` and the same expression a piece for the records.
 """
 import inspect
 import os
@@ -16,55 +11,30 @@ import re
 import numpy as np
 import pytest
 
+import find_args_cases as cases
 from find_anchor_model import BOL, EOL, WORD, anchored_hits, find_any_anchored_model, find_records_anchored_model
 from find_any_model import alt_tables, find_any_model
+from find_args_support import HUFE_ARGUMENT, LAYOUTS, NEWLINE, ROOT, WORDS, alts_of, bracket, call, lib, regex, valid
 from find_context_model import find_context_model
 from find_model import byte_set
 from libhuffman_amd import _native
 from libhuffman_amd.codec import GpuCodec
-from test_find_any_args import ALTS, DEFAULT, EMPTY, FULL, LAYOUTS, NEWLINE, alts_of, bracket, regex
 
-HUFE_OK, HUFE_ARGUMENT = 0, 2
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STREAM, INDEX, SUB, POS, LEN, NO, SEL, COUNTS, TOTALS, ERRS = (0x10000, 0x20000, 0x30008, 0x40000, 0x48000, 0x4c000, 0x4e000, 0x50000,
-                                                               0x60000, 0x70000)
-WORDS = byte_set(GpuCodec.WORD_BYTES)
 AnyOf = GpuCodec.AnyOf
 ANCHORS = [0, BOL, EOL, WORD, BOL | EOL, BOL | WORD, EOL | WORD, 7]
 EVERY = pytest.mark.parametrize("anchors", ANCHORS)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    return _native.load()
+def call_pos(lib, older=False, **kw):
+    return call(lib, "find_any" if older else "find_any_anchored", **kw)
 
 
-def call_pos(lib, stream=STREAM, stream_len=1000, index=INDEX, nblocks=4, sub=SUB, raw_size=4 * 4096, blocksize=4096, alts=ALTS,
-             cls=DEFAULT, lens=DEFAULT, n=DEFAULT, delims=NEWLINE, words=WORDS, anchors=WORD, pos=POS, cap=16, counts=COUNTS, totals=TOTALS,
-             errs=ERRS, flags=0, older=False):
-    cls, lens, n = (alts[0] if cls is DEFAULT else cls, alts[1] if lens is DEFAULT else lens, alts[2] if n is DEFAULT else n)
-    head, tail = (None, stream, stream_len, index, nblocks, sub, raw_size, blocksize, cls, lens, n), (pos, cap, counts, totals, errs, flags, None)
-    rc = lib.hufgpu_find_any(*head, *tail) if older else lib.hufgpu_find_any_anchored(*head, delims, words, anchors, *tail)
-    return rc, lib.hufgpu_last_error(None).decode()
-
-
-def call_rec(lib, stream=STREAM, stream_len=1000, index=INDEX, nblocks=4, sub=SUB, raw_size=4 * 4096, blocksize=4096, delims=NEWLINE,
-             alts=ALTS, cls=DEFAULT, lens=DEFAULT, n=DEFAULT, words=WORDS, anchors=WORD, select=0, ba=(2, 3), pos=POS, rlens=LEN, no=NO,
-             sel=SEL, cap=16, max_len=128, counts=COUNTS, totals=TOTALS, errs=ERRS, flags=0, older=False):
-    cls, lens, n = (alts[0] if cls is DEFAULT else cls, alts[1] if lens is DEFAULT else lens, alts[2] if n is DEFAULT else n)
-    head = (None, stream, stream_len, index, nblocks, sub, raw_size, blocksize, delims, cls, lens, n)
-    tail = (select, ba[0], ba[1], pos, rlens, no, sel, cap, max_len, counts, totals, errs, flags, None)
-    rc = lib.hufgpu_find_records_context(*head, *tail) if older else lib.hufgpu_find_records_anchored(*head, words, anchors, *tail)
-    return rc, lib.hufgpu_last_error(None).decode()
+def call_rec(lib, older=False, **kw):
+    return call(lib, "find_records_context" if older else "find_records_anchored", **kw)
 
 
 CALLS = [(call_pos, "find_any_anchored:", "find_any:"), (call_rec, "find_records_anchored:", "find_records_context:")]
 BOTH = pytest.mark.parametrize("call,who,was", CALLS, ids=["positions", "records"])
-
-
-def valid(rc, msg, who):
-    """every check but the last has passed"""
-    return rc == HUFE_ARGUMENT and "needs a context" in msg and msg.startswith(who)
 
 
 # ---- the symbols ---------------------------------------------------------------------------------------------------------
@@ -96,42 +66,26 @@ def test_the_symbols_are_exported_and_declared(lib):
     assert "OUT OF SCOPE" in doc and "per alternative" in doc and "variable length" in doc and "INSIDE a pattern" in doc
 
 
-# ---- the older calls' argument cases, in their order ---------------------------------------------------------------------
+# ---- the older calls' arguments, in their order ----------------------------------------------------------------------------
 @BOTH
 @EVERY
 def test_null_arrays_counts_lengths_and_classes(lib, call, who, was, anchors):
-    cls = b"".join([byte_set(b"ab")] * 64)
-    for nblocks, raw_size in LAYOUTS:
-        kw = dict(nblocks=nblocks, raw_size=raw_size, anchors=anchors)
-        for bad in (dict(cls=None), dict(lens=None), dict(cls=None, lens=None), dict(n=0), dict(n=65), dict(n=0xFFFFFFFF),
-                    dict(alts=alts_of(*[[b"x"]] * 65))):
-            rc, msg = call(lib, **kw, **bad)
-            assert rc == HUFE_ARGUMENT and msg.startswith(who) and "needs a context" not in msg, (bad, msg)
-        for bad in (dict(cls=None), dict(lens=None), dict(totals=None)):
-            assert "classes, alt_lens and d_totals are required" in call(lib, **kw, **bad)[1]
-        assert "n_alts 0 is not 1 to 64" in call(lib, n=0, **kw)[1]
-        assert "n_alts 65 is not 1 to 64" in call(lib, alts=alts_of(*[[b"x"]] * 65), **kw)[1]
-        rc, msg = call(lib, cls=cls, lens=np.array([3, 0, 2], np.uint32).tobytes(), n=3, **kw)
-        assert rc == HUFE_ARGUMENT and msg.startswith(who) and "alternative 1 has length 0" in msg
-        rc, msg = call(lib, cls=cls, lens=np.array([32, 33], np.uint32).tobytes(), n=2, **kw)
-        assert rc == HUFE_ARGUMENT and msg.startswith(who) and "sum to 65" in msg and "above 64" in msg
-        rc, msg = call(lib, alts=alts_of([b"ab"] * 2, [b"ab", b"ab", b""]), **kw)
-        assert rc == HUFE_ARGUMENT and msg.startswith(who) and "class 2 of alternative 1 is empty" in msg
-        assert valid(*call(lib, alts=alts_of([b"xy"] * 20, [b"x"] * 31), **kw), who)
+    name, kw = who[:-1], dict(anchors=anchors)
+    cases.null_arrays_and_counts_of_0_and_65(lib, name, kw)
+    cases.an_alternative_of_length_0(lib, name, kw, [3, 0, 2], 1)
+    cases.a_total_above_64(lib, name, kw, [32, 33])
+    cases.an_empty_class(lib, name, kw, *cases.EMPTY_CLASSES[-1])
 
 
 @EVERY
 def test_the_records_call_s_delimiters(lib, anchors):
+    """... and an unknown select bit is refused in front of everything else, the anchors included; the numbers and the flags
+    are optional"""
     who = "find_records_anchored:"
-    for nblocks, raw_size in LAYOUTS:
-        kw = dict(nblocks=nblocks, raw_size=raw_size, anchors=anchors)
-        for select in (0, 1):
-            rc, msg = call_rec(lib, alts=alts_of([b"ab"] * 2, [b"ab", b"a\nz"]), select=select, **kw)
-            assert rc == HUFE_ARGUMENT and msg.startswith(who) and "class 1 of alternative 1 holds a delimiter (value 10)" in msg
-        rc, msg = call_rec(lib, delims=None, **kw)
-        assert rc == HUFE_ARGUMENT and msg.startswith(who) and "delim_set is required" in msg and "needs a context" not in msg
-    assert valid(*call_rec(lib, delims=EMPTY, anchors=anchors), who)
-    assert valid(*call_rec(lib, alts=(FULL + byte_set(b"a"), np.array([1, 1], np.uint32).tobytes(), 2), delims=EMPTY, anchors=anchors), who)
+    for select in (0, 1):
+        cases.a_class_that_meets_the_delimiter_set(lib, who[:-1], dict(anchors=anchors, select=select), *cases.DELIMITER_CLASSES[-1])
+    cases.a_null_delimiter_set(lib, who[:-1], dict(anchors=anchors))
+    cases.the_full_class_and_the_delimiter_set(lib, who[:-1], dict(anchors=anchors))
     for select in (2, 3, 0x80000000, 0xFFFFFFFE):           # the first check of all
         for more in (dict(), dict(cls=None, totals=None), dict(anchors=8), dict(words=None, anchors=WORD)):
             rc, msg = call_rec(lib, **{**dict(anchors=anchors, select=select), **more})
@@ -144,28 +98,14 @@ def test_the_records_call_s_delimiters(lib, anchors):
 @BOTH
 @EVERY
 def test_caps_layouts_and_device_arrays(lib, call, who, was, anchors):
-    kw = dict(anchors=anchors)
-    if call is call_rec:
-        for bad in (dict(pos=None), dict(rlens=None), dict(pos=None, rlens=None)):
-            rc, msg = call(lib, cap=3, **kw, **bad)
-            assert rc == HUFE_ARGUMENT and msg.startswith(who) and "rec_cap 3 needs d_rec_pos and d_rec_len" in msg
-            assert valid(*call(lib, cap=0, **kw, **bad), who)
-    else:
-        rc, msg = call(lib, cap=3, pos=None, **kw)
-        assert rc == HUFE_ARGUMENT and msg.startswith(who) and "pos_cap 3 needs d_pos" in msg
-        assert valid(*call(lib, cap=0, pos=None, **kw), who)
-    for missing in ("stream", "index", "errs"):
-        rc, msg = call(lib, **kw, **{missing: None})
-        assert rc == HUFE_ARGUMENT and "are required" in msg and "needs a context" not in msg and msg.startswith(who)
-    for sub in (None, 0x30004, 0x30001):
-        rc, msg = call(lib, sub=sub, **kw)
-        assert rc == HUFE_ARGUMENT and "8-byte aligned" in msg and msg.startswith(who)
-    for bad in (dict(raw_size=5 * 4096), dict(raw_size=3 * 4096), dict(raw_size=0), dict(blocksize=0), dict(nblocks=0),
-                dict(blocksize=(1 << 38) + 1, raw_size=4 * ((1 << 38) + 1))):
-        rc, msg = call(lib, **kw, **bad)
-        assert rc == HUFE_ARGUMENT and "must be those of the encode" in msg and msg.startswith(who)
-    assert valid(*call(lib, blocksize=0, nblocks=1, **kw), who)
-    assert valid(*call(lib, stream=None, index=None, sub=None, errs=None, nblocks=0, raw_size=0, counts=None, **kw), who)
+    name, kw = who[:-1], dict(anchors=anchors)
+    cases.a_cap_without_its_outputs(lib, name, kw)
+    for missing in cases.NULL_ARRAYS:
+        cases.null_device_arrays(lib, name, kw, missing)
+    cases.missing_or_misaligned_sub_index(lib, name, kw)
+    for layout in cases.BAD_LAYOUTS:
+        cases.a_layout_that_does_not_give_nblocks(lib, name, kw, layout)
+    cases.valid_arguments_still_need_a_context(lib, name, kw)
 
 
 @BOTH
@@ -185,8 +125,8 @@ def test_the_order_of_the_checks_is_the_older_call_s(lib, call, who, was, anchor
 
 
 def test_the_older_calls_keep_their_wording(lib):
-    assert call_pos(lib, older=True, cls=None)[1] == "find_any: the classes, alt_lens and d_totals are required"
-    assert call_rec(lib, older=True, cls=None)[1] == "find_records_context: the classes, alt_lens and d_totals are required"
+    for older in ("find_any", "find_records_context"):
+        cases.the_call_keeps_its_wording(lib, older)
 
 
 # ---- the four new errors -------------------------------------------------------------------------------------------------

@@ -1,11 +1,8 @@
-"""hufgpu_find_any and hufgpu_find_records_any: the symbols, their declarations, their argument checks, the NumPy models of
-their results, and GpuCodec.AnyOf / alt_classes (no GPU needed).
-
-As for the class calls (tests/test_find_classes_args.py, whose cases are repeated here with the `find_any:` /
-`find_records_any:` wording) argument errors are found before anything is enqueued and before the context is looked at, so
-they can be provoked with a NULL context and made-up device pointers (never dereferenced); hufgpu_last_error(NULL) says which
-check spoke.  The models are checked against Python's `re` on `bytes`: an alternation of bracket expressions under a
-look-ahead for the positions - with the served rule applied per alternative -, bytes.split and re.search for the records.
+"""hufgpu_find_any and hufgpu_find_records_any: their declarations, the NumPy models of their results, and GpuCodec.AnyOf /
+alt_classes (no GPU needed).  Their argument checks - those of every call and those of the any-of table, which the four later
+calls take as well - are the functions of tests/find_args_cases.py.  The models are checked against Python's `re` on `bytes`: an
+alternation of bracket expressions under a look-ahead for the positions - with the served rule applied per alternative -,
+bytes.split and re.search for the records.
 """
 import os
 import re
@@ -13,56 +10,16 @@ import re
 import numpy as np
 import pytest
 
+import find_args_cases as cases
 from find_any_model import find_any_model, find_any_records_model
+from find_args_support import ROOT, lib, members, re_positions, re_records
 from find_classes_model import find_class_records_model, find_classes_model
-from find_model import byte_set
 from libhuffman_amd import _native
 from libhuffman_amd.codec import GpuCodec
 
-HUFE_OK, HUFE_ARGUMENT = 0, 2
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-STREAM, INDEX, SUB, POS, LEN, COUNTS, TOTALS, ERRS = 0x10000, 0x20000, 0x30008, 0x40000, 0x48000, 0x50000, 0x60000, 0x70000
-NEWLINE = byte_set(b"\n")
-FULL, EMPTY = bytes([255] * 32), bytes(32)
-DEFAULT = object()
 AnyOf = GpuCodec.AnyOf
-
-
-def alts_of(*alternatives):
-    """the two C arrays: 32 bytes a class, the alternatives one behind the other, and their lengths"""
-    return (b"".join(byte_set(s) for a in alternatives for s in a), np.array([len(a) for a in alternatives], np.uint32).tobytes(),
-            len(alternatives))
-
-
-ALTS = alts_of([b"eE", b"rR", b"rR"], [b"f", b"a", b"t", b"a", b"l"], [b"pP"])
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _native.load()
-
-
-def call_pos(lib, stream=STREAM, stream_len=1000, index=INDEX, nblocks=4, sub=SUB, raw_size=4 * 4096, blocksize=4096, alts=ALTS,
-             cls=DEFAULT, lens=DEFAULT, n=DEFAULT, pos=POS, cap=16, counts=COUNTS, totals=TOTALS, errs=ERRS, flags=0):
-    cls, lens, n = (alts[0] if cls is DEFAULT else cls, alts[1] if lens is DEFAULT else lens, alts[2] if n is DEFAULT else n)
-    rc = lib.hufgpu_find_any(None, stream, stream_len, index, nblocks, sub, raw_size, blocksize, cls, lens, n, pos, cap, counts,
-                             totals, errs, flags, None)
-    return rc, lib.hufgpu_last_error(None).decode()
-
-
-def call_rec(lib, stream=STREAM, stream_len=1000, index=INDEX, nblocks=4, sub=SUB, raw_size=4 * 4096, blocksize=4096, delims=NEWLINE,
-             alts=ALTS, cls=DEFAULT, lens=DEFAULT, n=DEFAULT, pos=POS, rlens=LEN, cap=16, max_len=128, counts=COUNTS, totals=TOTALS,
-             errs=ERRS, flags=0):
-    cls, lens, n = (alts[0] if cls is DEFAULT else cls, alts[1] if lens is DEFAULT else lens, alts[2] if n is DEFAULT else n)
-    rc = lib.hufgpu_find_records_any(None, stream, stream_len, index, nblocks, sub, raw_size, blocksize, delims, cls, lens, n, pos,
-                                     rlens, cap, max_len, counts, totals, errs, flags, None)
-    return rc, lib.hufgpu_last_error(None).decode()
-
-
-CALLS = [(call_pos, "find_any:"), (call_rec, "find_records_any:")]
-BOTH = pytest.mark.parametrize("call,who", CALLS, ids=["positions", "records"])
-LAYOUTS = ((4, 4 * 4096), (0, 0))
+NAMES = ("find_any", "find_records_any")
+EACH = pytest.mark.parametrize("name", NAMES, ids=["positions", "records"])
 
 
 # ---- the symbols ---------------------------------------------------------------------------------------------------------
@@ -81,179 +38,83 @@ def test_symbols_are_exported_and_declared(lib):
         assert header.index(name + "(hufgpu_ctx_t") > header.index("hufgpu_find_records_classes(hufgpu_ctx_t")
 
 
-# ---- the new cases -------------------------------------------------------------------------------------------------------
-@BOTH
-def test_null_arrays_and_counts_of_0_and_65(lib, call, who):
-    for kw in (dict(cls=None), dict(lens=None), dict(cls=None, lens=None), dict(n=0), dict(n=65), dict(n=0xFFFFFFFF),
-               dict(alts=alts_of(*[[b"x"]] * 65))):
-        for nblocks, raw_size in LAYOUTS:
-            rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, **kw)
-            assert rc == HUFE_ARGUMENT and msg.startswith(who) and "needs a context" not in msg, (kw, msg)
-    for kw in (dict(cls=None), dict(lens=None)):
-        rc, msg = call(lib, **kw)
-        assert "classes, alt_lens and d_totals are required" in msg
-    rc, msg = call(lib, n=0)
-    assert "n_alts 0 is not 1 to 64" in msg
-    rc, msg = call(lib, alts=alts_of(*[[b"x"]] * 65))
-    assert "n_alts 65 is not 1 to 64" in msg
-    for alts in (alts_of([b"xy"]), alts_of([b"xy"] * 64), alts_of(*[[b"xy"]] * 64), alts_of([b"x"] * 31, [b"y"] * 33),
-                 alts_of([b"x"], [b"y"] * 63)):     # the ends of what is allowed reach the last check
-        rc, msg = call(lib, alts=alts)
-        assert rc == HUFE_ARGUMENT and "needs a context" in msg and msg.startswith(who), msg
+# ---- the checks that every call shares (tests/find_args_cases.py), under the names they have always had here -----------------
+@EACH
+def test_null_arrays_and_counts_of_0_and_65(lib, name):
+    cases.null_arrays_and_counts_of_0_and_65(lib, name, {})
 
 
-@BOTH
-@pytest.mark.parametrize("lens,at", [([0], 0), ([3, 0, 2], 1), ([1, 1, 0], 2), ([1] * 63 + [0], 63), ([0, 70], 0)])
-def test_an_alternative_of_length_0(lib, call, who, lens, at):
-    cls = b"".join([byte_set(b"ab")] * 64)
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, cls=cls, lens=np.array(lens, np.uint32).tobytes(), n=len(lens))
-        assert rc == HUFE_ARGUMENT and msg.startswith(who) and "needs a context" not in msg, msg
-        assert f"alternative {at} has length 0" in msg
+@EACH
+@pytest.mark.parametrize("lens,at", cases.LENGTHS_OF_0)
+def test_an_alternative_of_length_0(lib, name, lens, at):
+    cases.an_alternative_of_length_0(lib, name, {}, lens, at)
 
 
-@BOTH
-@pytest.mark.parametrize("lens", [[65], [64, 1], [32, 33], [1] * 63 + [2], [2, 5, 33, 25], [0xFFFFFFFF, 2], [0x80000000, 0x80000000]])
-def test_a_total_above_64(lib, call, who, lens):
-    cls = b"".join([byte_set(b"ab")] * 64)                 # (never read past: the total is looked at first)
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, cls=cls, lens=np.array(lens, np.uint32).tobytes(), n=len(lens))
-        assert rc == HUFE_ARGUMENT and msg.startswith(who) and "needs a context" not in msg, msg
-        assert f"sum to {sum(lens)}" in msg and "above 64" in msg
+@EACH
+@pytest.mark.parametrize("lens", cases.TOTALS_ABOVE_64)
+def test_a_total_above_64(lib, name, lens):
+    cases.a_total_above_64(lib, name, {}, lens)
 
 
-@BOTH
-@pytest.mark.parametrize("lens,j,k", [([5], 0, 0), ([5], 0, 4), ([2, 5, 33], 1, 2), ([2, 5, 33], 2, 32), ([31, 33], 1, 0), ([1] * 64, 63, 0),
-                                      ([1, 63], 1, 62), ([32, 32], 0, 31)])
-def test_an_empty_class(lib, call, who, lens, j, k):
-    alts = [[b"ab"] * m for m in lens]
-    alts[j][k] = b""
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, alts=alts_of(*alts))
-        assert rc == HUFE_ARGUMENT and msg.startswith(who) and "is empty" in msg and "needs a context" not in msg, msg
-        assert f"class {k} of alternative {j} " in msg
+@EACH
+@pytest.mark.parametrize("lens,j,k", cases.EMPTY_CLASSES[:8])
+def test_an_empty_class(lib, name, lens, j, k):
+    cases.an_empty_class(lib, name, {}, lens, j, k)
 
 
-@pytest.mark.parametrize("lens,j,k", [([5], 0, 0), ([2, 5, 33], 1, 4), ([2, 5, 33], 2, 0), ([31, 33], 1, 32), ([1] * 64, 40, 0), ([1, 63], 0, 0)])
+@pytest.mark.parametrize("lens,j,k", cases.DELIMITER_CLASSES[:6])
 def test_a_class_that_meets_the_delimiter_set(lib, lens, j, k):
-    alts = [[b"ab"] * m for m in lens]
-    alts[j][k] = b"a\nz"
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call_rec(lib, nblocks=nblocks, raw_size=raw_size, alts=alts_of(*alts))
-        assert rc == HUFE_ARGUMENT and msg.startswith("find_records_any:") and "holds a delimiter" in msg, msg
-        assert "needs a context" not in msg and f"class {k} of alternative {j} " in msg and "(value 10)" in msg
-        rc, msg = call_rec(lib, nblocks=nblocks, raw_size=raw_size, alts=alts_of(*alts), delims=byte_set(b"\r\x00"))   # (no delimiter now)
-        assert rc == HUFE_ARGUMENT and "needs a context" in msg
-        rc, msg = call_pos(lib, nblocks=nblocks, raw_size=raw_size, alts=alts_of(*alts))         # the positions' call has no delimiters
-        assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    rc, msg = call_rec(lib, alts=alts_of([b"a"], [b"b", [3, 255]]), delims=byte_set([255]))
-    assert rc == HUFE_ARGUMENT and "class 1 of alternative 1 holds a delimiter (value 255)" in msg
+    for name in NAMES:                                      # (the positions' call has no delimiters)
+        cases.a_class_that_meets_the_delimiter_set(lib, name, {}, lens, j, k)
 
 
 def test_the_full_class_and_the_delimiter_set(lib):
-    for cls, j, k in (((FULL + byte_set(b"a"), np.array([1, 1], np.uint32).tobytes(), 2), 0, 0),
-                      ((byte_set(b"a") + byte_set(b"b") + FULL, np.array([1, 2], np.uint32).tobytes(), 2), 1, 1)):
-        for nblocks, raw_size in LAYOUTS:
-            rc, msg = call_rec(lib, nblocks=nblocks, raw_size=raw_size, alts=cls)
-            assert rc == HUFE_ARGUMENT and "holds a delimiter" in msg and f"class {k} of alternative {j} " in msg and "(value 10)" in msg
-            assert "needs a context" not in msg
-        rc, msg = call_rec(lib, alts=cls, delims=EMPTY)    # the empty delimiter set: valid
-        assert rc == HUFE_ARGUMENT and "needs a context" in msg
-        rc, msg = call_pos(lib, alts=cls)
-        assert rc == HUFE_ARGUMENT and "needs a context" in msg
+    for name in NAMES:
+        cases.the_full_class_and_the_delimiter_set(lib, name, {})
+
+
+@EACH
+def test_valid_arguments_still_need_a_context(lib, name):
+    cases.valid_arguments_still_need_a_context(lib, name, {})
+
+
+@EACH
+@pytest.mark.parametrize("missing", cases.NULL_ARRAYS)
+def test_null_device_arrays(lib, name, missing):
+    cases.null_device_arrays(lib, name, {}, missing)
+
+
+@EACH
+def test_null_totals(lib, name):
+    cases.null_totals(lib, name, {})
+
+
+@EACH
+def test_missing_or_misaligned_sub_index(lib, name):
+    cases.missing_or_misaligned_sub_index(lib, name, {})
+
+
+@EACH
+@pytest.mark.parametrize("kw", cases.BAD_LAYOUTS)
+def test_a_layout_that_does_not_give_nblocks(lib, name, kw):
+    cases.a_layout_that_does_not_give_nblocks(lib, name, {}, kw)
 
 
 def test_a_null_delimiter_set(lib):
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call_rec(lib, nblocks=nblocks, raw_size=raw_size, delims=None)
-        assert rc == HUFE_ARGUMENT and msg.startswith("find_records_any:") and "delim_set is required" in msg, msg
-        assert "needs a context" not in msg
-    rc, msg = call_rec(lib, delims=EMPTY)
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    rc, msg = call_rec(lib, delims=byte_set(range(256)), cls=None)
-    assert "classes, alt_lens and d_totals are required" in msg
+    cases.a_null_delimiter_set(lib, NAMES[1], {})
 
 
 def test_a_cap_without_both_outputs(lib):
-    for kw in (dict(pos=None), dict(rlens=None), dict(pos=None, rlens=None)):
-        for cap in (1, 16):
-            rc, msg = call_rec(lib, cap=cap, **kw)
-            assert rc == HUFE_ARGUMENT and msg.startswith("find_records_any:") and "needs d_rec_pos and d_rec_len" in msg, (kw, msg)
-            assert f"rec_cap {cap}" in msg and "needs a context" not in msg
-        rc, msg = call_rec(lib, cap=0, **kw)             # with rec_cap = 0 both may be NULL
-        assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    rc, msg = call_pos(lib, pos=None, cap=1)
-    assert rc == HUFE_ARGUMENT and "needs d_pos" in msg and msg.startswith("find_any:")
-
-
-# ---- the cases of the older calls ----------------------------------------------------------------------------------------
-@BOTH
-def test_valid_arguments_still_need_a_context(lib, call, who):
-    rc, msg = call(lib)
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg and msg.startswith(who)
-    rc, msg = call(lib, pos=None, cap=0, counts=None, **(dict(rlens=None) if call is call_rec else {}))
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    if call is call_rec:
-        rc, msg = call(lib, max_len=0)
-        assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    rc, msg = call(lib, blocksize=0, nblocks=1)
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    # nblocks = 0 is success only with a context to enqueue the zeroing of d_totals on
-    rc, msg = call(lib, stream=None, index=None, sub=None, errs=None, nblocks=0, raw_size=0)
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg
-
-
-@BOTH
-@pytest.mark.parametrize("missing", ["stream", "index", "errs"])
-def test_null_device_arrays(lib, call, who, missing):
-    rc, msg = call(lib, **{missing: None})
-    assert rc == HUFE_ARGUMENT and "are required" in msg and "needs a context" not in msg and msg.startswith(who)
-
-
-@BOTH
-def test_null_totals(lib, call, who):
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, totals=None)
-        assert rc == HUFE_ARGUMENT and "classes, alt_lens and d_totals are required" in msg and msg.startswith(who)
-
-
-@BOTH
-def test_missing_or_misaligned_sub_index(lib, call, who):
-    for sub in (None, 0x30004, 0x30001):
-        rc, msg = call(lib, sub=sub)
-        assert rc == HUFE_ARGUMENT and "8-byte aligned" in msg and msg.startswith(who)
-
-
-@BOTH
-@pytest.mark.parametrize("kw", [
-    dict(raw_size=5 * 4096),                            # five blocks
-    dict(raw_size=3 * 4096),                            # three
-    dict(raw_size=0),
-    dict(blocksize=0),                                  # one block
-    dict(nblocks=0),                                    # no blocks, but bytes
-    dict(blocksize=(1 << 38) + 1, raw_size=4 * ((1 << 38) + 1)),
-])
-def test_a_layout_that_does_not_give_nblocks(lib, call, who, kw):
-    rc, msg = call(lib, **kw)
-    assert rc == HUFE_ARGUMENT and "must be those of the encode" in msg and msg.startswith(who)
+    for name in NAMES:
+        cases.a_cap_without_its_outputs(lib, name, {})
 
 
 def test_the_other_calls_keep_their_wording(lib):
-    rc = lib.hufgpu_find_bytes(None, STREAM, 1000, INDEX, 4, SUB, 4 * 4096, 4096, None, POS, 16, COUNTS, TOTALS, ERRS, 0, None)
-    assert rc == HUFE_ARGUMENT and lib.hufgpu_last_error(None).decode() == "find_bytes: the set and d_totals are required"
-    rc = lib.hufgpu_find_classes(None, STREAM, 1000, INDEX, 4, SUB, 4 * 4096, 4096, None, 3, POS, 1, COUNTS, TOTALS, ERRS, 0, None)
-    assert rc == HUFE_ARGUMENT and lib.hufgpu_last_error(None).decode() == "find_classes: the classes and d_totals are required"
-    rc = lib.hufgpu_find_records_classes(None, STREAM, 1000, INDEX, 4, SUB, 4 * 4096, 4096, NEWLINE, byte_set(b"a") + byte_set(b"\n"), 2,
-                                         POS, LEN, 1, 0, COUNTS, TOTALS, ERRS, 0, None)
-    assert rc == HUFE_ARGUMENT
-    assert lib.hufgpu_last_error(None).decode().startswith("find_records_classes: class 1 of the pattern holds a delimiter (value 10)")
+    for older in ("find_bytes", "find_classes", "find_records_classes"):
+        cases.the_call_keeps_its_wording(lib, older)
 
 
 # ---- AnyOf and alt_classes -----------------------------------------------------------------------------------------------
-def members(row):
-    return [v for v in range(256) if row[v >> 3] >> (v & 7) & 1]
-
-
 def test_alt_classes():
     a = AnyOf(b"ERROR", [b"fF", ord("x"), {1, 2}], b"p")
     assert len(a) == 3 and list(a) == [b"ERROR", [b"fF", ord("x"), {1, 2}], b"p"] and "AnyOf(" in repr(a)
@@ -291,58 +152,6 @@ def test_alt_classes_errors():
 
 
 # ---- the models against re -----------------------------------------------------------------------------------------------
-def bracket(values):
-    return b"[" + b"".join(b"\\x%02x" % v for v in sorted(values)) + b"]"
-
-
-def regex(sets):
-    return b"".join(bracket(s) for s in sets)
-
-
-def re_positions(data, alts, blocksize, cap=0, served=None):
-    """the same answer from re.finditer: per alternative a look-ahead sees overlapping matches, and the served rule is the
-    alternative's own; a start counts once"""
-    raw, n = bytes(data), len(data)
-    bs = blocksize or n
-    nb = (n + bs - 1) // bs if n else 0
-    served = [True] * nb if served is None else list(served)
-    found = set()
-    for sets in alts:
-        for hit in re.finditer(b"(?=(" + regex(sets) + b"))", raw, re.DOTALL):
-            p = hit.start()
-            if all(served[b] for b in range(p // bs, (p + len(sets) - 1) // bs + 1)):
-                found.add(p)
-    pos, counts = sorted(found), [0] * nb
-    for p in pos:
-        counts[p // bs] += 1
-    written = min(len(pos), cap)
-    return pos[:written], counts, [len(pos), written, nb - sum(served), 0]
-
-
-def re_records(data, alts, delims, blocksize, cap=0, max_len=0, served=None):
-    """... and from bytes.split (one delimiter value) or re.split, with re.search of the ALTERNATION a piece"""
-    raw, n = bytes(data), len(data)
-    delims = sorted(set(bytes(delims)))
-    bs = blocksize or n
-    nb = (n + bs - 1) // bs if n else 0
-    served = [True] * nb if served is None else list(served)
-    clip = max_len or 2**32 - 1
-    pieces = [raw] if not delims else raw.split(bytes(delims)) if len(delims) == 1 else re.split(bracket(delims), raw, flags=re.DOTALL)
-    want = re.compile(b"|".join(b"(?:" + regex(sets) + b")" for sets in alts), re.DOTALL)
-    pos, lens, counts, cut = [], [], [0] * nb, []
-    s = 0
-    for piece in pieces if n else []:
-        e = s + len(piece)
-        if want.search(piece) and all(served[b] for b in range(max(s - 1, 0) // bs, min(e, n - 1) // bs + 1)):
-            pos.append(s)
-            lens.append(min(e - s, clip))
-            cut.append(e - s > clip)
-            counts[s // bs] += 1
-        s = e + 1
-    written = min(len(pos), cap)
-    return pos[:written], lens[:written], counts, [len(pos), written, nb - sum(served), sum(cut[:written])]
-
-
 def same_positions(data, alts, blocksize, cap=0, served=None):
     got = find_any_model(data, alts, blocksize, cap, served)
     want = re_positions(data, alts, blocksize, cap, served)

@@ -1,18 +1,18 @@
-"""hufgpu_find_classes and hufgpu_find_records_classes: the symbols, their declarations, their argument checks, the NumPy
-models of their results and GpuCodec.byte_classes (no GPU needed).
-
-As for the literal calls (tests/test_find_pattern_args.py and tests/test_find_records_args.py, whose cases are repeated
-here with the `find_classes:` / `find_records_classes:` wording) argument errors are found before anything is enqueued and
-before the context is looked at, so they can be provoked with a NULL context and made-up device pointers (never
-dereferenced); hufgpu_last_error(NULL) says which check spoke.  The models are checked against Python's `re` on `bytes`:
-bracket expressions under a look-ahead for the positions, bytes.split and re.search for the records.
+"""hufgpu_find_classes and hufgpu_find_records_classes: their declarations, the argument checks of their own, the NumPy models
+of their results and GpuCodec.byte_classes (no GPU needed).  The checks they share with the other calls of the search family
+are the functions of tests/find_args_cases.py.  The models are checked against Python's `re` on `bytes`: bracket expressions under a
+look-ahead for the positions, bytes.split and re.search for the records.
 """
+import functools
 import os
 import re
 
 import numpy as np
 import pytest
 
+import find_args_cases as cases
+import find_args_support
+from find_args_support import EMPTY, FULL, HUFE_ARGUMENT, LAYOUTS, ROOT, classes_of, lib, members, re_positions, re_records
 from find_classes_model import class_table, find_class_records_model, find_classes_model
 from find_model import byte_set, find_model
 from find_pattern_model import find_pattern_model
@@ -20,49 +20,12 @@ from find_records_model import find_records_model
 from libhuffman_amd import _native
 from libhuffman_amd.codec import GpuCodec
 
-HUFE_OK, HUFE_ARGUMENT = 0, 2
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-STREAM, INDEX, SUB, POS, LEN, COUNTS, TOTALS, ERRS = 0x10000, 0x20000, 0x30008, 0x40000, 0x48000, 0x50000, 0x60000, 0x70000
-NEWLINE = byte_set(b"\n")
-FULL, EMPTY = bytes([255] * 32), bytes(32)
-DEFAULT = object()
-
-
-def classes_of(*sets):
-    """the C array: 32 bytes a class"""
-    return b"".join(byte_set(s) for s in sets)
-
-
-CLS = classes_of(b"eE", b"rR", b"rR", b"oO", b"rR")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _native.load()
-
-
-def call_pos(lib, stream=STREAM, stream_len=1000, index=INDEX, nblocks=4, sub=SUB, raw_size=4 * 4096, blocksize=4096, cls=CLS,
-             plen=DEFAULT, pos=POS, cap=16, counts=COUNTS, totals=TOTALS, errs=ERRS, flags=0):
-    if plen is DEFAULT:
-        plen = len(cls) // 32 if cls is not None else 5
-    rc = lib.hufgpu_find_classes(None, stream, stream_len, index, nblocks, sub, raw_size, blocksize, cls, plen, pos, cap, counts,
-                                 totals, errs, flags, None)
-    return rc, lib.hufgpu_last_error(None).decode()
-
-
-def call_rec(lib, stream=STREAM, stream_len=1000, index=INDEX, nblocks=4, sub=SUB, raw_size=4 * 4096, blocksize=4096, delims=NEWLINE,
-             cls=CLS, plen=DEFAULT, pos=POS, lens=LEN, cap=16, max_len=128, counts=COUNTS, totals=TOTALS, errs=ERRS, flags=0):
-    if plen is DEFAULT:
-        plen = len(cls) // 32 if cls is not None else 5
-    rc = lib.hufgpu_find_records_classes(None, stream, stream_len, index, nblocks, sub, raw_size, blocksize, delims, cls, plen, pos,
-                                         lens, cap, max_len, counts, totals, errs, flags, None)
-    return rc, lib.hufgpu_last_error(None).decode()
-
-
+call_pos = functools.partial(find_args_support.call, name="find_classes")
+call_rec = functools.partial(find_args_support.call, name="find_records_classes")
 CALLS = [(call_pos, "find_classes:"), (call_rec, "find_records_classes:")]
 BOTH = pytest.mark.parametrize("call,who", CALLS, ids=["positions", "records"])
-LAYOUTS = ((4, 4 * 4096), (0, 0))
+NAMES = ("find_classes", "find_records_classes")
+EACH = pytest.mark.parametrize("name", NAMES, ids=["positions", "records"])
 
 
 # ---- the symbols ---------------------------------------------------------------------------------------------------------
@@ -79,7 +42,7 @@ def test_symbols_are_exported_and_declared(lib):
         assert header.index(name + "(hufgpu_ctx_t") > header.index("hufgpu_find_records(hufgpu_ctx_t")
 
 
-# ---- the new cases -------------------------------------------------------------------------------------------------------
+# ---- the classes -----------------------------------------------------------------------------------------------------------
 @BOTH
 def test_null_classes_and_lengths_of_0_and_65(lib, call, who):
     for kw in (dict(cls=None), dict(plen=0), dict(cls=classes_of(*[b"x"] * 65)), dict(plen=65), dict(plen=0xFFFFFFFF)):
@@ -136,96 +99,50 @@ def test_the_full_class_and_the_delimiter_set(lib):
         assert rc == HUFE_ARGUMENT and "needs a context" in msg
 
 
+# ---- the checks that every call shares (tests/find_args_cases.py), under the names they have always had here -----------------
+
+@EACH
+def test_valid_arguments_still_need_a_context(lib, name):
+    cases.valid_arguments_still_need_a_context(lib, name, {})
+
+
+@EACH
+@pytest.mark.parametrize("missing", cases.NULL_ARRAYS)
+def test_null_device_arrays(lib, name, missing):
+    cases.null_device_arrays(lib, name, {}, missing)
+
+
+@EACH
+def test_null_totals(lib, name):
+    cases.null_totals(lib, name, {})
+
+
+@EACH
+def test_missing_or_misaligned_sub_index(lib, name):
+    cases.missing_or_misaligned_sub_index(lib, name, {})
+
+
+@EACH
+@pytest.mark.parametrize("kw", cases.BAD_LAYOUTS)
+def test_a_layout_that_does_not_give_nblocks(lib, name, kw):
+    cases.a_layout_that_does_not_give_nblocks(lib, name, {}, kw)
+
+
 def test_a_null_delimiter_set(lib):
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call_rec(lib, nblocks=nblocks, raw_size=raw_size, delims=None)
-        assert rc == HUFE_ARGUMENT and msg.startswith("find_records_classes:") and "delim_set is required" in msg, msg
-        assert "needs a context" not in msg
-    rc, msg = call_rec(lib, delims=EMPTY)
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    rc, msg = call_rec(lib, delims=byte_set(range(256)), cls=None)
-    assert "classes and d_totals are required" in msg
+    cases.a_null_delimiter_set(lib, NAMES[1], {})
 
 
 def test_a_cap_without_both_outputs(lib):
-    for kw in (dict(pos=None), dict(lens=None), dict(pos=None, lens=None)):
-        for cap in (1, 16):
-            rc, msg = call_rec(lib, cap=cap, **kw)
-            assert rc == HUFE_ARGUMENT and msg.startswith("find_records_classes:") and "needs d_rec_pos and d_rec_len" in msg, (kw, msg)
-            assert f"rec_cap {cap}" in msg and "needs a context" not in msg
-        rc, msg = call_rec(lib, cap=0, **kw)             # with rec_cap = 0 both may be NULL
-        assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    rc, msg = call_pos(lib, pos=None, cap=1)
-    assert rc == HUFE_ARGUMENT and "needs d_pos" in msg and msg.startswith("find_classes:")
-
-
-# ---- the cases of the literal calls --------------------------------------------------------------------------------------
-@BOTH
-def test_valid_arguments_still_need_a_context(lib, call, who):
-    rc, msg = call(lib)
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg and msg.startswith(who)
-    rc, msg = call(lib, pos=None, cap=0, counts=None, **(dict(lens=None) if call is call_rec else {}))
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    if call is call_rec:
-        rc, msg = call(lib, max_len=0)
-        assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    rc, msg = call(lib, blocksize=0, nblocks=1)
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    # nblocks = 0 is success only with a context to enqueue the zeroing of d_totals on
-    rc, msg = call(lib, stream=None, index=None, sub=None, errs=None, nblocks=0, raw_size=0)
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg
-
-
-@BOTH
-@pytest.mark.parametrize("missing", ["stream", "index", "errs"])
-def test_null_device_arrays(lib, call, who, missing):
-    rc, msg = call(lib, **{missing: None})
-    assert rc == HUFE_ARGUMENT and "are required" in msg and "needs a context" not in msg and msg.startswith(who)
-
-
-@BOTH
-def test_null_totals(lib, call, who):
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, totals=None)
-        assert rc == HUFE_ARGUMENT and "classes and d_totals are required" in msg and msg.startswith(who)
-
-
-@BOTH
-def test_missing_or_misaligned_sub_index(lib, call, who):
-    for sub in (None, 0x30004, 0x30001):
-        rc, msg = call(lib, sub=sub)
-        assert rc == HUFE_ARGUMENT and "8-byte aligned" in msg and msg.startswith(who)
-
-
-@BOTH
-@pytest.mark.parametrize("kw", [
-    dict(raw_size=5 * 4096),                            # five blocks
-    dict(raw_size=3 * 4096),                            # three
-    dict(raw_size=0),
-    dict(blocksize=0),                                  # one block
-    dict(nblocks=0),                                    # no blocks, but bytes
-    dict(blocksize=(1 << 38) + 1, raw_size=4 * ((1 << 38) + 1)),
-])
-def test_a_layout_that_does_not_give_nblocks(lib, call, who, kw):
-    rc, msg = call(lib, **kw)
-    assert rc == HUFE_ARGUMENT and "must be those of the encode" in msg and msg.startswith(who)
+    for name in NAMES:
+        cases.a_cap_without_its_outputs(lib, name, {})
 
 
 def test_the_other_calls_keep_their_wording(lib):
-    rc = lib.hufgpu_find_bytes(None, STREAM, 1000, INDEX, 4, SUB, 4 * 4096, 4096, None, POS, 16, COUNTS, TOTALS, ERRS, 0, None)
-    assert rc == HUFE_ARGUMENT and lib.hufgpu_last_error(None).decode() == "find_bytes: the set and d_totals are required"
-    rc = lib.hufgpu_find_pattern(None, STREAM, 1000, INDEX, 4, SUB, 4 * 4096, 4096, b"a\nb", 3, None, 1, COUNTS, TOTALS, ERRS, 0, None)
-    assert rc == HUFE_ARGUMENT and lib.hufgpu_last_error(None).decode() == "find_pattern: pos_cap 1 needs d_pos"
-    rc = lib.hufgpu_find_records(None, STREAM, 1000, INDEX, 4, SUB, 4 * 4096, 4096, NEWLINE, b"a\nb", 3, POS, LEN, 1, 0, COUNTS, TOTALS,
-                                 ERRS, 0, None)
-    assert rc == HUFE_ARGUMENT and lib.hufgpu_last_error(None).decode().startswith("find_records: byte 1 of the pattern (value 10)")
+    for older in ("find_bytes", "find_pattern", "find_records"):
+        cases.the_call_keeps_its_wording(lib, older)
 
 
 # ---- byte_classes --------------------------------------------------------------------------------------------------------
-def members(row):
-    return [v for v in range(256) if row[v >> 3] >> (v & 7) & 1]
-
-
 def test_byte_classes_of_a_literal():
     c = GpuCodec.byte_classes(b"a\x00\xff")
     assert c.dtype == np.uint8 and c.shape == (3, 32)
@@ -271,52 +188,6 @@ def test_byte_classes_errors():
 
 
 # ---- the models against re -----------------------------------------------------------------------------------------------
-def bracket(values):
-    return b"[" + b"".join(b"\\x%02x" % v for v in sorted(values)) + b"]"
-
-
-def regex(sets):
-    return b"".join(bracket(s) for s in sets)
-
-
-def re_positions(data, sets, blocksize, cap=0, served=None):
-    """the same answer from re.finditer: a look-ahead sees overlapping matches"""
-    raw, n, m = bytes(data), len(data), len(sets)
-    bs = blocksize or n
-    nb = (n + bs - 1) // bs if n else 0
-    served = [True] * nb if served is None else list(served)
-    pos, counts = [], [0] * nb
-    for hit in re.finditer(b"(?=(" + regex(sets) + b"))", raw, re.DOTALL):
-        p = hit.start()
-        if all(served[b] for b in range(p // bs, (p + m - 1) // bs + 1)):
-            pos.append(p)
-            counts[p // bs] += 1
-    written = min(len(pos), cap)
-    return pos[:written], counts, [len(pos), written, nb - sum(served), 0]
-
-
-def re_records(data, sets, delims, blocksize, cap=0, max_len=0, served=None):
-    """... and from bytes.split (one delimiter value) or re.split, with re.search a piece"""
-    raw, n = bytes(data), len(data)
-    delims = sorted(set(bytes(delims)))
-    bs = blocksize or n
-    nb = (n + bs - 1) // bs if n else 0
-    served = [True] * nb if served is None else list(served)
-    clip = max_len or 2**32 - 1
-    pieces = [raw] if not delims else raw.split(bytes(delims)) if len(delims) == 1 else re.split(bracket(delims), raw, flags=re.DOTALL)
-    want = re.compile(regex(sets), re.DOTALL)
-    pos, lens, counts, cut = [], [], [0] * nb, []
-    s = 0
-    for piece in pieces if n else []:
-        e = s + len(piece)
-        if want.search(piece) and all(served[b] for b in range(max(s - 1, 0) // bs, min(e, n - 1) // bs + 1)):
-            pos.append(s)
-            lens.append(min(e - s, clip))
-            cut.append(e - s > clip)
-            counts[s // bs] += 1
-        s = e + 1
-    written = min(len(pos), cap)
-    return pos[:written], lens[:written], counts, [len(pos), written, nb - sum(served), sum(cut[:written])]
 
 
 def random_sets(rng, m, alphabet, width):
@@ -326,14 +197,14 @@ def random_sets(rng, m, alphabet, width):
 
 def same_positions(data, sets, blocksize, cap=0, served=None):
     got = find_classes_model(data, sets, blocksize, cap, served)
-    want = re_positions(data, sets, blocksize, cap, served)
+    want = re_positions(data, [sets], blocksize, cap, served)
     assert tuple(g.tolist() for g in got) == want
     return want
 
 
 def same_records(data, sets, delims, blocksize, cap=0, max_len=0, served=None):
     got = find_class_records_model(data, sets, delims, blocksize, cap, max_len, served)
-    want = re_records(data, sets, delims, blocksize, cap, max_len, served)
+    want = re_records(data, [sets], delims, blocksize, cap, max_len, served)
     assert tuple(g.tolist() for g in got) == want
     return want
 

@@ -1,12 +1,10 @@
-"""hufgpu_find_records_context: the symbol, its declaration, its argument checks, the NumPy model of its results
-(tests/find_context_model.py) and the `before` / `after` / `context` keywords of GpuCodec (no GPU needed).
-
-As for the older find calls argument errors are found before anything is enqueued and before the context is looked at, so
-they can be provoked with a NULL context and made-up device pointers (never dereferenced); hufgpu_last_error(NULL) says which
-check spoke.  Every argument case of hufgpu_find_records_select (tests/test_find_select_args.py) is repeated here with the
-`find_records_context:` wording, for distances of 0 and others.  The model is checked against plain Python over
-`bytes.split`: the indices of the selected pieces, a window around each, the union, the empty pieces dropped.
+"""hufgpu_find_records_context: its declaration, the checks of the arguments of its own, the NumPy model of its results
+(tests/find_context_model.py) and the `before` / `after` / `context` keywords of GpuCodec (no GPU needed).  The checks it
+shares with the other calls of the search family, for distances of 0 and others, are the functions of tests/find_args_cases.py.  The
+model is checked against plain Python over `bytes.split`: the indices of the selected pieces, a window around each, the
+union, the empty pieces dropped.
 """
+import functools
 import inspect
 import os
 import re
@@ -14,50 +12,20 @@ import re
 import numpy as np
 import pytest
 
+import find_args_cases as cases
+import find_args_support
+from find_args_support import FAR, HUFE_ARGUMENT, LAYOUTS, ROOT, alts_of, lib, random_case, regex, valid
 from find_context_model import find_context_model
-from find_model import byte_set
 from find_select_model import NO_UNKNOWN, find_select_model
 from libhuffman_amd import _native
 from libhuffman_amd.codec import GpuCodec
-from test_find_any_args import ALTS, DEFAULT, EMPTY, FULL, LAYOUTS, NEWLINE, alts_of, regex
-from test_find_select_args import random_case
 
-HUFE_OK, HUFE_ARGUMENT = 0, 2
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STREAM, INDEX, SUB, POS, LEN, NO, SEL, COUNTS, TOTALS, ERRS = (0x10000, 0x20000, 0x30008, 0x40000, 0x48000, 0x4c000, 0x4e000, 0x50000,
-                                                               0x60000, 0x70000)
 WHO = "find_records_context:"
 AnyOf = GpuCodec.AnyOf
-FAR = 2**32 - 1
+NAME = "find_records_context"
+call = functools.partial(find_args_support.call, name=NAME)
 DISTANCES = [(0, 1), (1, 0), (2, 2), (0, 5), (7, 0), (3, 40), (FAR, FAR)]
 WINDOWS = pytest.mark.parametrize("ba", [(0, 0), (2, 3), (FAR, FAR)], ids=["select", "2-3", "all"])
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _native.load()
-
-
-def call(lib, stream=STREAM, stream_len=1000, index=INDEX, nblocks=4, sub=SUB, raw_size=4 * 4096, blocksize=4096, delims=NEWLINE,
-         alts=ALTS, cls=DEFAULT, lens=DEFAULT, n=DEFAULT, select=0, ba=(2, 3), pos=POS, rlens=LEN, no=NO, sel=SEL, cap=16, max_len=128,
-         counts=COUNTS, totals=TOTALS, errs=ERRS, flags=0):
-    cls, lens, n = (alts[0] if cls is DEFAULT else cls, alts[1] if lens is DEFAULT else lens, alts[2] if n is DEFAULT else n)
-    rc = lib.hufgpu_find_records_context(None, stream, stream_len, index, nblocks, sub, raw_size, blocksize, delims, cls, lens, n, select,
-                                         ba[0], ba[1], pos, rlens, no, sel, cap, max_len, counts, totals, errs, flags, None)
-    return rc, lib.hufgpu_last_error(None).decode()
-
-
-def select_call(lib, stream=STREAM, index=INDEX, sub=SUB, raw_size=4 * 4096, delims=NEWLINE, alts=ALTS, cls=DEFAULT, n=DEFAULT, select=0,
-                pos=POS):
-    """hufgpu_find_records_select with what `call` passes for the same keywords"""
-    cls, n = (alts[0] if cls is DEFAULT else cls, alts[2] if n is DEFAULT else n)
-    return lib.hufgpu_find_records_select(None, stream, 1000, index, 4, sub, raw_size, 4096, delims, cls, alts[1], n, select, pos, LEN, NO, 16,
-                                          128, COUNTS, TOTALS, ERRS, 0, None)
-
-
-def valid(rc, msg):
-    """every check but the last has passed"""
-    return rc == HUFE_ARGUMENT and "needs a context" in msg and msg.startswith(WHO)
 
 
 # ---- the symbol ----------------------------------------------------------------------------------------------------------
@@ -100,7 +68,7 @@ def test_an_unknown_select_bit(lib, select):
 def test_the_numbers_and_the_flags_are_optional(lib, select, ba):
     for out in (dict(), dict(no=None), dict(sel=None), dict(no=None, sel=None)):
         for kw in (dict(), dict(cap=0), dict(cap=0, pos=None, rlens=None)):
-            assert valid(*call(lib, select=select, ba=ba, **out, **kw)), (out, kw)
+            assert valid(*call(lib, select=select, ba=ba, **out, **kw), WHO), (out, kw)
         rc, msg = call(lib, select=select, ba=ba, pos=None, **out)      # neither stands in for one of the two other outputs
         assert rc == HUFE_ARGUMENT and "needs d_rec_pos and d_rec_len" in msg and msg.startswith(WHO)
 
@@ -108,72 +76,10 @@ def test_the_numbers_and_the_flags_are_optional(lib, select, ba):
 @pytest.mark.parametrize("ba", [(0, 0), (0, 1), (1, 0), (0x80000000, 5), (FAR, 0), (0, FAR), (FAR, FAR)])
 def test_any_distance_is_valid(lib, ba):
     for select in (0, 1):
-        assert valid(*call(lib, select=select, ba=ba))
+        assert valid(*call(lib, select=select, ba=ba), WHO)
 
 
-# ---- every argument case of hufgpu_find_records_select, with no context at all, in the same order ----------------------------
-@WINDOWS
-def test_null_arrays_and_counts_of_0_and_65(lib, ba):
-    for kw in (dict(cls=None), dict(lens=None), dict(cls=None, lens=None), dict(n=0), dict(n=65), dict(n=0xFFFFFFFF),
-               dict(alts=alts_of(*[[b"x"]] * 65))):
-        for nblocks, raw_size in LAYOUTS:
-            rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, ba=ba, **kw)
-            assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "needs a context" not in msg, (kw, msg)
-    for kw in (dict(cls=None), dict(lens=None)):
-        assert "classes, alt_lens and d_totals are required" in call(lib, ba=ba, **kw)[1]
-    assert "n_alts 0 is not 1 to 64" in call(lib, ba=ba, n=0)[1]
-    assert "n_alts 65 is not 1 to 64" in call(lib, ba=ba, alts=alts_of(*[[b"x"]] * 65))[1]
-    for alts in (alts_of([b"xy"]), alts_of([b"xy"] * 64), alts_of(*[[b"xy"]] * 64), alts_of([b"x"] * 31, [b"y"] * 33)):
-        assert valid(*call(lib, ba=ba, alts=alts))
-
-
-@WINDOWS
-def test_lengths_classes_and_delimiters(lib, ba):
-    cls = b"".join([byte_set(b"ab")] * 64)
-    for nblocks, raw_size in LAYOUTS:
-        kw = dict(nblocks=nblocks, raw_size=raw_size, ba=ba)
-        rc, msg = call(lib, cls=cls, lens=np.array([3, 0, 2], np.uint32).tobytes(), n=3, **kw)
-        assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "alternative 1 has length 0" in msg
-        rc, msg = call(lib, cls=cls, lens=np.array([32, 33], np.uint32).tobytes(), n=2, **kw)
-        assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "sum to 65" in msg and "above 64" in msg
-        rc, msg = call(lib, alts=alts_of([b"ab"] * 2, [b"ab", b"ab", b""]), **kw)
-        assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "class 2 of alternative 1 is empty" in msg
-        for select in (0, 1):
-            rc, msg = call(lib, alts=alts_of([b"ab"] * 2, [b"ab", b"a\nz"]), select=select, **kw)
-            assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "class 1 of alternative 1 holds a delimiter (value 10)" in msg
-        rc, msg = call(lib, alts=(FULL + byte_set(b"a"), np.array([1, 1], np.uint32).tobytes(), 2), select=1, **kw)
-        assert rc == HUFE_ARGUMENT and "class 0 of alternative 0 holds a delimiter" in msg and "needs a context" not in msg
-        rc, msg = call(lib, delims=None, **kw)
-        assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "delim_set is required" in msg and "needs a context" not in msg
-        rc, msg = call(lib, totals=None, **kw)
-        assert rc == HUFE_ARGUMENT and "classes, alt_lens and d_totals are required" in msg and msg.startswith(WHO)
-    assert valid(*call(lib, alts=(FULL + byte_set(b"a"), np.array([1, 1], np.uint32).tobytes(), 2), delims=EMPTY, ba=ba))
-    assert valid(*call(lib, delims=EMPTY, ba=ba))
-
-
-@WINDOWS
-def test_caps_layouts_and_device_arrays(lib, ba):
-    for kw in (dict(pos=None), dict(rlens=None), dict(pos=None, rlens=None)):
-        for cap in (1, 16):
-            rc, msg = call(lib, cap=cap, ba=ba, **kw)
-            assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "needs d_rec_pos and d_rec_len" in msg, (kw, msg)
-            assert f"rec_cap {cap}" in msg and "needs a context" not in msg
-        assert valid(*call(lib, cap=0, ba=ba, **kw))
-    for missing in ("stream", "index", "errs"):
-        rc, msg = call(lib, ba=ba, **{missing: None})
-        assert rc == HUFE_ARGUMENT and "are required" in msg and "needs a context" not in msg and msg.startswith(WHO)
-    for sub in (None, 0x30004, 0x30001):
-        rc, msg = call(lib, sub=sub, ba=ba)
-        assert rc == HUFE_ARGUMENT and "8-byte aligned" in msg and msg.startswith(WHO)
-    for kw in (dict(raw_size=5 * 4096), dict(raw_size=3 * 4096), dict(raw_size=0), dict(blocksize=0), dict(nblocks=0),
-               dict(blocksize=(1 << 38) + 1, raw_size=4 * ((1 << 38) + 1))):
-        rc, msg = call(lib, ba=ba, **kw)
-        assert rc == HUFE_ARGUMENT and "must be those of the encode" in msg and msg.startswith(WHO)
-    for select in (0, 1):
-        assert valid(*call(lib, select=select, ba=ba, pos=None, rlens=None, no=None, sel=None, cap=0, counts=None))
-        assert valid(*call(lib, select=select, ba=ba, max_len=0))
-        assert valid(*call(lib, select=select, ba=ba, blocksize=0, nblocks=1))
-        assert valid(*call(lib, select=select, ba=ba, stream=None, index=None, sub=None, errs=None, nblocks=0, raw_size=0))
+# ---- the older checks, in the older order ------------------------------------------------------------------------------------
 
 
 def test_the_order_of_the_checks_is_the_select_call_s(lib):
@@ -184,16 +90,47 @@ def test_the_order_of_the_checks_is_the_select_call_s(lib):
         for b in mistakes[i:]:
             kw = {**a, **b}
             rc, msg = call(lib, **kw)
-            select_call(lib, **kw)
-            other = lib.hufgpu_last_error(None).decode()
+            other = find_args_support.call(lib, "find_records_select", **kw)[1]
             assert rc == HUFE_ARGUMENT and msg == other.replace("find_records_select:", WHO), (kw, msg, other)
 
 
+# ---- the checks that every call shares (tests/find_args_cases.py), under the names they have always had here -----------------
+BOTH_SELECTS = (0, 1)
+
+
+@WINDOWS
+def test_null_arrays_and_counts_of_0_and_65(lib, ba):
+    cases.null_arrays_and_counts_of_0_and_65(lib, NAME, dict(ba=ba))
+
+
+@WINDOWS
+def test_lengths_classes_and_delimiters(lib, ba):
+    kw = dict(ba=ba)
+    cases.an_alternative_of_length_0(lib, NAME, kw, [3, 0, 2], 1)
+    cases.a_total_above_64(lib, NAME, kw, [32, 33])
+    cases.an_empty_class(lib, NAME, kw, *cases.EMPTY_CLASSES[-1])
+    for select in BOTH_SELECTS:
+        cases.a_class_that_meets_the_delimiter_set(lib, NAME, dict(ba=ba, select=select), *cases.DELIMITER_CLASSES[-1])
+    cases.the_full_class_and_the_delimiter_set(lib, NAME, dict(ba=ba, select=1))
+    cases.a_null_delimiter_set(lib, NAME, kw)
+    cases.null_totals(lib, NAME, kw)
+
+
+@WINDOWS
+def test_caps_layouts_and_device_arrays(lib, ba):
+    kw = dict(ba=ba)
+    cases.a_cap_without_its_outputs(lib, NAME, kw)
+    for missing in cases.NULL_ARRAYS:
+        cases.null_device_arrays(lib, NAME, kw, missing)
+    cases.missing_or_misaligned_sub_index(lib, NAME, kw)
+    for layout in cases.BAD_LAYOUTS:
+        cases.a_layout_that_does_not_give_nblocks(lib, NAME, kw, layout)
+    for select in BOTH_SELECTS:
+        cases.valid_arguments_still_need_a_context(lib, NAME, dict(ba=ba, select=select))
+
+
 def test_the_select_call_keeps_its_wording(lib):
-    rc = lib.hufgpu_find_records_select(None, STREAM, 1000, INDEX, 4, SUB, 4 * 4096, 4096, NEWLINE, None, None, 1, 0, POS, LEN, NO, 1, 0,
-                                        COUNTS, TOTALS, ERRS, 0, None)
-    assert rc == HUFE_ARGUMENT
-    assert lib.hufgpu_last_error(None).decode() == "find_records_select: the classes, alt_lens and d_totals are required"
+    cases.the_call_keeps_its_wording(lib, "find_records_select")
 
 
 # ---- the Python keywords -------------------------------------------------------------------------------------------------

@@ -1,40 +1,23 @@
-"""hufgpu_find_pattern: the symbol, its declaration, its argument checks and the NumPy model of its result (no GPU needed).
-
-As for hufgpu_find_bytes (tests/test_find_args.py, whose cases are repeated here) argument errors are found before
-anything is enqueued and before the context is looked at, so they can be provoked with a NULL context and made-up device
-pointers (never dereferenced); hufgpu_last_error(NULL) says which check spoke.  The model is checked against a plain
-bytes.find loop.
+"""hufgpu_find_pattern: its declaration, the argument check of its own and the NumPy model of its result (no GPU needed).  The
+checks it shares with the other calls of the search family are the functions of tests/find_args_cases.py.  The model is checked
+against a plain bytes.find loop.
 """
+import functools
 import os
 import re
 
 import numpy as np
 import pytest
 
+import find_args_cases as cases
+import find_args_support
+from find_args_support import HUFE_ARGUMENT, LAYOUTS, ROOT, lib
 from find_model import find_model
 from find_pattern_model import find_pattern_model
 from libhuffman_amd import _native
 
-HUFE_OK, HUFE_ARGUMENT = 0, 2
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-STREAM, INDEX, SUB, POS, COUNTS, TOTALS, ERRS = 0x10000, 0x20000, 0x30008, 0x40000, 0x50000, 0x60000, 0x70000
-PAT = b"ERROR"
-DEFAULT = object()
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _native.load()
-
-
-def call(lib, stream=STREAM, stream_len=1000, index=INDEX, nblocks=4, sub=SUB, raw_size=4 * 4096, blocksize=4096, pat=PAT,
-         plen=DEFAULT, pos=POS, cap=16, counts=COUNTS, totals=TOTALS, errs=ERRS, flags=0):
-    if plen is DEFAULT:
-        plen = len(pat) if pat is not None else 5
-    rc = lib.hufgpu_find_pattern(None, stream, stream_len, index, nblocks, sub, raw_size, blocksize, pat, plen, pos, cap, counts,
-                                 totals, errs, flags, None)
-    return rc, lib.hufgpu_last_error(None).decode()
+NAME = "find_pattern"
+call = functools.partial(find_args_support.call, name=NAME)
 
 
 def test_symbol_is_exported_and_declared(lib):
@@ -49,71 +32,48 @@ def test_symbol_is_exported_and_declared(lib):
 
 
 def test_a_pattern_of_no_or_too_many_bytes(lib):
-    for kw in (dict(pat=None), dict(plen=0), dict(pat=b"x" * 65), dict(plen=65), dict(plen=0xFFFFFFFF)):
-        for nblocks, raw_size in ((4, 4 * 4096), (0, 0)):
+    for kw in (dict(pattern=None), dict(plen=0), dict(pattern=b"x" * 65), dict(plen=65), dict(plen=0xFFFFFFFF)):
+        for nblocks, raw_size in LAYOUTS:
             rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, **kw)
             assert rc == HUFE_ARGUMENT and msg.startswith("find_pattern:") and "needs a context" not in msg, (kw, msg)
-    rc, msg = call(lib, pat=None)
+    rc, msg = call(lib, pattern=None)
     assert "pattern and d_totals are required" in msg
     rc, msg = call(lib, plen=65)
     assert "pattern_len 65" in msg
     for pat in (b"x", b"x" * 64):                        # the two ends of what is allowed reach the last check
-        rc, msg = call(lib, pat=pat)
+        rc, msg = call(lib, pattern=pat)
         assert rc == HUFE_ARGUMENT and "needs a context" in msg
 
 
-# ---- the cases of tests/test_find_args.py ----------------------------------------------------------------------------------
+# ---- the checks that every call shares (tests/find_args_cases.py), under the names they have always had here -----------------
 def test_valid_arguments_still_need_a_context(lib):
-    rc, msg = call(lib)
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg and msg.startswith("find_pattern:")
-    rc, msg = call(lib, pos=None, cap=0, counts=None)
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    rc, msg = call(lib, blocksize=0, nblocks=1)
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg
-    # nblocks = 0 is success only with a context to enqueue the zeroing of d_totals on
-    rc, msg = call(lib, stream=None, index=None, sub=None, errs=None, nblocks=0, raw_size=0)
-    assert rc == HUFE_ARGUMENT and "needs a context" in msg
+    cases.valid_arguments_still_need_a_context(lib, NAME, {})
 
 
-@pytest.mark.parametrize("missing", ["stream", "index", "errs"])
+@pytest.mark.parametrize("missing", cases.NULL_ARRAYS)
 def test_null_device_arrays(lib, missing):
-    rc, msg = call(lib, **{missing: None})
-    assert rc == HUFE_ARGUMENT and "are required" in msg and "needs a context" not in msg and msg.startswith("find_pattern:")
+    cases.null_device_arrays(lib, NAME, {}, missing)
 
 
 def test_null_totals(lib):
-    for nblocks, raw_size in ((4, 4 * 4096), (0, 0)):
-        rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, totals=None)
-        assert rc == HUFE_ARGUMENT and "pattern and d_totals are required" in msg
+    cases.null_totals(lib, NAME, {})
 
 
 def test_a_cap_without_positions(lib):
-    rc, msg = call(lib, pos=None, cap=1)
-    assert rc == HUFE_ARGUMENT and "needs d_pos" in msg and msg.startswith("find_pattern:")
+    cases.a_cap_without_its_outputs(lib, NAME, {})
 
 
 def test_missing_or_misaligned_sub_index(lib):
-    for sub in (None, 0x30004, 0x30001):
-        rc, msg = call(lib, sub=sub)
-        assert rc == HUFE_ARGUMENT and "8-byte aligned" in msg and msg.startswith("find_pattern:")
+    cases.missing_or_misaligned_sub_index(lib, NAME, {})
 
 
-@pytest.mark.parametrize("kw", [
-    dict(raw_size=5 * 4096),                            # five blocks
-    dict(raw_size=3 * 4096),                            # three
-    dict(raw_size=0),
-    dict(blocksize=0),                                  # one block
-    dict(nblocks=0),                                    # no blocks, but bytes
-    dict(blocksize=(1 << 38) + 1, raw_size=4 * ((1 << 38) + 1)),
-])
+@pytest.mark.parametrize("kw", cases.BAD_LAYOUTS)
 def test_a_layout_that_does_not_give_nblocks(lib, kw):
-    rc, msg = call(lib, **kw)
-    assert rc == HUFE_ARGUMENT and "must be those of the encode" in msg and msg.startswith("find_pattern:")
+    cases.a_layout_that_does_not_give_nblocks(lib, NAME, {}, kw)
 
 
 def test_find_bytes_keeps_its_wording(lib):
-    rc = lib.hufgpu_find_bytes(None, STREAM, 1000, INDEX, 4, SUB, 4 * 4096, 4096, None, POS, 16, COUNTS, TOTALS, ERRS, 0, None)
-    assert rc == HUFE_ARGUMENT and lib.hufgpu_last_error(None).decode() == "find_bytes: the set and d_totals are required"
+    cases.the_call_keeps_its_wording(lib, "find_bytes")
 
 
 # ---- the model -----------------------------------------------------------------------------------------------------------

@@ -1,12 +1,10 @@
-"""hufgpu_find_records_select: the symbol, its declaration, its argument checks, the NumPy model of its results
-(tests/find_select_model.py) and the `invert` / `line_numbers` keywords of GpuCodec (no GPU needed).
-
-As for the older find calls argument errors are found before anything is enqueued and before the context is looked at, so
-they can be provoked with a NULL context and made-up device pointers (never dereferenced); hufgpu_last_error(NULL) says which
-check spoke.  Every argument case of hufgpu_find_records_any (tests/test_find_any_args.py) is repeated here with the
-`find_records_select:` wording.  The model is checked against plain Python: `re` / split over `bytes` for the records - the
-non-empty pieces without a match are the inverted answer - and data[:s].count(delimiter) for the numbers.
+"""hufgpu_find_records_select: its declaration, the checks of the arguments of its own, the NumPy model of its results
+(tests/find_select_model.py) and the `invert` / `line_numbers` keywords of GpuCodec (no GPU needed).  The checks it shares
+with the other calls of the search family, plain and inverted, are the functions of tests/find_args_cases.py.  The model is checked
+against plain Python: `re` / split over `bytes` for the records - the non-empty pieces without a match are the inverted
+answer - and data[:s].count(delimiter) for the numbers.
 """
+import functools
 import inspect
 import os
 import re
@@ -14,37 +12,18 @@ import re
 import numpy as np
 import pytest
 
+import find_args_cases as cases
+import find_args_support
 from find_any_model import find_any_records_model
-from find_model import byte_set
+from find_args_support import HUFE_ARGUMENT, LAYOUTS, ROOT, bracket, lib, random_case, regex, valid
 from find_select_model import NO_UNKNOWN, find_select_model
 from libhuffman_amd import _native
 from libhuffman_amd.codec import GpuCodec
-from test_find_any_args import ALTS, DEFAULT, EMPTY, FULL, LAYOUTS, NEWLINE, alts_of, bracket, regex
 
-HUFE_OK, HUFE_ARGUMENT = 0, 2
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STREAM, INDEX, SUB, POS, LEN, NO, COUNTS, TOTALS, ERRS = 0x10000, 0x20000, 0x30008, 0x40000, 0x48000, 0x4c000, 0x50000, 0x60000, 0x70000
 WHO = "find_records_select:"
 AnyOf = GpuCodec.AnyOf
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _native.load()
-
-
-def call(lib, stream=STREAM, stream_len=1000, index=INDEX, nblocks=4, sub=SUB, raw_size=4 * 4096, blocksize=4096, delims=NEWLINE,
-         alts=ALTS, cls=DEFAULT, lens=DEFAULT, n=DEFAULT, select=0, pos=POS, rlens=LEN, no=NO, cap=16, max_len=128, counts=COUNTS,
-         totals=TOTALS, errs=ERRS, flags=0):
-    cls, lens, n = (alts[0] if cls is DEFAULT else cls, alts[1] if lens is DEFAULT else lens, alts[2] if n is DEFAULT else n)
-    rc = lib.hufgpu_find_records_select(None, stream, stream_len, index, nblocks, sub, raw_size, blocksize, delims, cls, lens, n, select,
-                                        pos, rlens, no, cap, max_len, counts, totals, errs, flags, None)
-    return rc, lib.hufgpu_last_error(None).decode()
-
-
-def valid(rc, msg):
-    """every check but the last has passed"""
-    return rc == HUFE_ARGUMENT and "needs a context" in msg and msg.startswith(WHO)
+NAME = "find_records_select"
+call = functools.partial(find_args_support.call, name=NAME)
 
 
 # ---- the symbol ----------------------------------------------------------------------------------------------------------
@@ -80,141 +59,80 @@ def test_an_unknown_select_bit(lib, select):
 @pytest.mark.parametrize("select", [0, 1])
 def test_the_numbers_are_optional(lib, select):
     for kw in (dict(no=None), dict(no=None, cap=0, pos=None, rlens=None), dict(cap=0), dict(cap=0, pos=None, rlens=None), dict()):
-        assert valid(*call(lib, select=select, **kw)), kw
+        assert valid(*call(lib, select=select, **kw), WHO), kw
     rc, msg = call(lib, select=select, pos=None)                # the numbers stand in for neither of the two other outputs
     assert rc == HUFE_ARGUMENT and "needs d_rec_pos and d_rec_len" in msg and msg.startswith(WHO)
 
 
-# ---- every argument case of hufgpu_find_records_any, with no context at all ---------------------------------------------------
+# ---- the checks that every call shares (tests/find_args_cases.py), under the names they have always had here -----------------
 SELECTS = pytest.mark.parametrize("select", [0, 1], ids=["plain", "invert"])
+BOTH_SELECTS = (dict(select=0), dict(select=1))
 
 
 @SELECTS
 def test_null_arrays_and_counts_of_0_and_65(lib, select):
-    for kw in (dict(cls=None), dict(lens=None), dict(cls=None, lens=None), dict(n=0), dict(n=65), dict(n=0xFFFFFFFF),
-               dict(alts=alts_of(*[[b"x"]] * 65))):
-        for nblocks, raw_size in LAYOUTS:
-            rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, select=select, **kw)
-            assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "needs a context" not in msg, (kw, msg)
-    for kw in (dict(cls=None), dict(lens=None)):
-        assert "classes, alt_lens and d_totals are required" in call(lib, select=select, **kw)[1]
-    assert "n_alts 0 is not 1 to 64" in call(lib, select=select, n=0)[1]
-    assert "n_alts 65 is not 1 to 64" in call(lib, select=select, alts=alts_of(*[[b"x"]] * 65))[1]
-    for alts in (alts_of([b"xy"]), alts_of([b"xy"] * 64), alts_of(*[[b"xy"]] * 64), alts_of([b"x"] * 31, [b"y"] * 33),
-                 alts_of([b"x"], [b"y"] * 63)):
-        assert valid(*call(lib, select=select, alts=alts))
+    cases.null_arrays_and_counts_of_0_and_65(lib, NAME, dict(select=select))
 
 
-@pytest.mark.parametrize("lens,at", [([0], 0), ([3, 0, 2], 1), ([1, 1, 0], 2), ([1] * 63 + [0], 63), ([0, 70], 0)])
+@pytest.mark.parametrize("lens,at", cases.LENGTHS_OF_0)
 def test_an_alternative_of_length_0(lib, lens, at):
-    cls = b"".join([byte_set(b"ab")] * 64)
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, cls=cls, lens=np.array(lens, np.uint32).tobytes(), n=len(lens))
-        assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "needs a context" not in msg, msg
-        assert f"alternative {at} has length 0" in msg
+    cases.an_alternative_of_length_0(lib, NAME, {}, lens, at)
 
 
-@pytest.mark.parametrize("lens", [[65], [64, 1], [32, 33], [1] * 63 + [2], [2, 5, 33, 25], [0xFFFFFFFF, 2], [0x80000000, 0x80000000]])
+@pytest.mark.parametrize("lens", cases.TOTALS_ABOVE_64)
 def test_a_total_above_64(lib, lens):
-    cls = b"".join([byte_set(b"ab")] * 64)
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, cls=cls, lens=np.array(lens, np.uint32).tobytes(), n=len(lens))
-        assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "needs a context" not in msg, msg
-        assert f"sum to {sum(lens)}" in msg and "above 64" in msg
+    cases.a_total_above_64(lib, NAME, {}, lens)
 
 
-@pytest.mark.parametrize("lens,j,k", [([5], 0, 0), ([5], 0, 4), ([2, 5, 33], 1, 2), ([2, 5, 33], 2, 32), ([31, 33], 1, 0), ([1] * 64, 63, 0),
-                                      ([1, 63], 1, 62), ([32, 32], 0, 31)])
+@pytest.mark.parametrize("lens,j,k", cases.EMPTY_CLASSES[:8])
 def test_an_empty_class(lib, lens, j, k):
-    alts = [[b"ab"] * m for m in lens]
-    alts[j][k] = b""
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, alts=alts_of(*alts))
-        assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "is empty" in msg and "needs a context" not in msg, msg
-        assert f"class {k} of alternative {j} " in msg
+    cases.an_empty_class(lib, NAME, {}, lens, j, k)
 
 
-@pytest.mark.parametrize("lens,j,k", [([5], 0, 0), ([2, 5, 33], 1, 4), ([2, 5, 33], 2, 0), ([31, 33], 1, 32), ([1] * 64, 40, 0), ([1, 63], 0, 0)])
+@pytest.mark.parametrize("lens,j,k", cases.DELIMITER_CLASSES[:6])
 def test_a_class_that_meets_the_delimiter_set(lib, lens, j, k):
-    alts = [[b"ab"] * m for m in lens]
-    alts[j][k] = b"a\nz"
-    for nblocks, raw_size in LAYOUTS:
-        for select in (0, 1):
-            rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, alts=alts_of(*alts), select=select)
-            assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "holds a delimiter" in msg, msg
-            assert "needs a context" not in msg and f"class {k} of alternative {j} " in msg and "(value 10)" in msg
-        assert valid(*call(lib, nblocks=nblocks, raw_size=raw_size, alts=alts_of(*alts), delims=byte_set(b"\r\x00")))
-    rc, msg = call(lib, alts=alts_of([b"a"], [b"b", [3, 255]]), delims=byte_set([255]))
-    assert rc == HUFE_ARGUMENT and "class 1 of alternative 1 holds a delimiter (value 255)" in msg
+    for kw in BOTH_SELECTS:
+        cases.a_class_that_meets_the_delimiter_set(lib, NAME, kw, lens, j, k)
 
 
 def test_the_full_class_and_the_delimiter_set(lib):
-    for cls, j, k in (((FULL + byte_set(b"a"), np.array([1, 1], np.uint32).tobytes(), 2), 0, 0),
-                      ((byte_set(b"a") + byte_set(b"b") + FULL, np.array([1, 2], np.uint32).tobytes(), 2), 1, 1)):
-        for nblocks, raw_size in LAYOUTS:
-            rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, alts=cls, select=1)
-            assert rc == HUFE_ARGUMENT and "holds a delimiter" in msg and f"class {k} of alternative {j} " in msg and "(value 10)" in msg
-            assert "needs a context" not in msg
-        assert valid(*call(lib, alts=cls, delims=EMPTY, select=1))      # the empty delimiter set: valid
+    cases.the_full_class_and_the_delimiter_set(lib, NAME, dict(select=1))
 
 
 def test_a_null_delimiter_set(lib):
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, delims=None, select=1)
-        assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "delim_set is required" in msg, msg
-        assert "needs a context" not in msg
-    assert valid(*call(lib, delims=EMPTY))
-    assert "classes, alt_lens and d_totals are required" in call(lib, delims=byte_set(range(256)), cls=None)[1]
+    for kw in BOTH_SELECTS:
+        cases.a_null_delimiter_set(lib, NAME, kw)
 
 
 def test_a_cap_without_both_outputs(lib):
-    for kw in (dict(pos=None), dict(rlens=None), dict(pos=None, rlens=None)):
-        for cap in (1, 16):
-            rc, msg = call(lib, cap=cap, **kw)
-            assert rc == HUFE_ARGUMENT and msg.startswith(WHO) and "needs d_rec_pos and d_rec_len" in msg, (kw, msg)
-            assert f"rec_cap {cap}" in msg and "needs a context" not in msg
-        assert valid(*call(lib, cap=0, **kw))
+    cases.a_cap_without_its_outputs(lib, NAME, {})
 
 
 @SELECTS
 def test_valid_arguments_still_need_a_context(lib, select):
-    assert valid(*call(lib, select=select))
-    assert valid(*call(lib, select=select, pos=None, rlens=None, no=None, cap=0, counts=None))
-    assert valid(*call(lib, select=select, max_len=0))
-    assert valid(*call(lib, select=select, blocksize=0, nblocks=1))
-    assert valid(*call(lib, select=select, stream=None, index=None, sub=None, errs=None, nblocks=0, raw_size=0))
+    cases.valid_arguments_still_need_a_context(lib, NAME, dict(select=select))
 
 
-@pytest.mark.parametrize("missing", ["stream", "index", "errs"])
+@pytest.mark.parametrize("missing", cases.NULL_ARRAYS)
 def test_null_device_arrays(lib, missing):
-    rc, msg = call(lib, **{missing: None})
-    assert rc == HUFE_ARGUMENT and "are required" in msg and "needs a context" not in msg and msg.startswith(WHO)
+    cases.null_device_arrays(lib, NAME, {}, missing)
 
 
 def test_null_totals(lib):
-    for nblocks, raw_size in LAYOUTS:
-        rc, msg = call(lib, nblocks=nblocks, raw_size=raw_size, totals=None)
-        assert rc == HUFE_ARGUMENT and "classes, alt_lens and d_totals are required" in msg and msg.startswith(WHO)
+    cases.null_totals(lib, NAME, {})
 
 
 def test_missing_or_misaligned_sub_index(lib):
-    for sub in (None, 0x30004, 0x30001):
-        rc, msg = call(lib, sub=sub)
-        assert rc == HUFE_ARGUMENT and "8-byte aligned" in msg and msg.startswith(WHO)
+    cases.missing_or_misaligned_sub_index(lib, NAME, {})
 
 
-@pytest.mark.parametrize("kw", [dict(raw_size=5 * 4096), dict(raw_size=3 * 4096), dict(raw_size=0), dict(blocksize=0), dict(nblocks=0),
-                                dict(blocksize=(1 << 38) + 1, raw_size=4 * ((1 << 38) + 1))])
+@pytest.mark.parametrize("kw", cases.BAD_LAYOUTS)
 def test_a_layout_that_does_not_give_nblocks(lib, kw):
-    rc, msg = call(lib, **kw)
-    assert rc == HUFE_ARGUMENT and "must be those of the encode" in msg and msg.startswith(WHO)
+    cases.a_layout_that_does_not_give_nblocks(lib, NAME, {}, kw)
 
 
 def test_the_any_of_call_keeps_its_wording(lib):
-    rc = lib.hufgpu_find_records_any(None, STREAM, 1000, INDEX, 4, SUB, 4 * 4096, 4096, NEWLINE, None, None, 1, POS, LEN, 1, 0, COUNTS,
-                                     TOTALS, ERRS, 0, None)
-    assert rc == HUFE_ARGUMENT
-    assert lib.hufgpu_last_error(None).decode() == "find_records_any: the classes, alt_lens and d_totals are required"
+    cases.the_call_keeps_its_wording(lib, "find_records_any")
 
 
 # ---- the Python keywords -------------------------------------------------------------------------------------------------
@@ -309,28 +227,6 @@ def test_the_model_by_hand():
 
 
 MIXES = [(1,), (64,), (2, 5, 33), (32, 32)]
-
-
-def random_case(rng, mix, alphabet, trial):
-    values = np.array([97, 98, 99, 10]) if alphabet == "four letters" else np.arange(256)
-    n, bs = int(rng.integers(1, 700)), int(rng.integers(0, 90))
-    data = (rng.choice(values, n, p=[0.30, 0.30, 0.30, 0.10]) if values.size == 4 else rng.choice(values, n)).astype(np.uint8)
-    if values.size == 256:
-        data[rng.integers(0, n, n // 6 + 1)] = 10           # lines, and now and then two delimiters in a row
-    if trial % 3 == 0:
-        data[0] = 10                                        # a delimiter as byte 0
-    data[n - 1] = 10 if trial % 2 else 97                   # the data ends with and without one
-    alts = []
-    wide = trial % 2 == 0
-    for m in mix:
-        if alphabet == "four letters":
-            narrow = rng.integers(0, max(m // 3, 1), m) == 0
-            sets = [sorted(set(int(v) for v in rng.choice(values[:3], 1 if m <= 5 and not wide else 2, replace=False))) if narrow[k]
-                    else [97, 98, 99] for k in range(m)]
-        else:
-            sets = [[v for v in range(256) if v != 10 and rng.integers(0, 64 if wide or m > 5 else 2)] or [1] for _ in range(m)]
-        alts.append(sets)
-    return data, alts, n, bs
 
 
 @pytest.mark.parametrize("mix", MIXES, ids=lambda m: "x".join(map(str, m)))

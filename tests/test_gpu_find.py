@@ -10,58 +10,15 @@ import numpy as np
 import pytest
 
 from find_model import block_lens, find_model
+from find_support import GUARD64, LEAD, OK, RW, TAIL, answer_or_not_served, check, codec, damaged, encoded, find, payload_start, torch_mod
 from libhuffman_amd import datagen
-from test_gpu_ranges import GUARD, Enc, dev
-from test_gpu_range_tiles import make
+from stream_support import GUARD, Enc, dev, make
 
 pytestmark = pytest.mark.gpu
 
-TILE, GROUP = 2048, 32
-OK, RW = 0, 3
-GUARD64 = int(np.array([GUARD] * 8, np.uint8).view(np.int64)[0])
-LEAD, TAIL = 3, 5
-BIG = 3 * (1 << 20) + 77
-SHAPES = {"bs4096": (4096, 5 * 4096 + 1500),            # two tiles a block
-          "bs4099": (4099, 6 * 4099),                   # every block ends in a 3-symbol group, no block start but the first is 32-aligned
-          "bs65536": (65536, 3 * 65536 + 77),           # exactly one chunk a block, a short last block
-          "oneblock": (0, BIG)}                         # several chunks, chunked encode
 CASES = [("zipf255", "bs4096"), ("zipf255", "bs4099"), ("zipf255", "bs65536"), ("zipf255", "oneblock"), ("two", "bs4099"),
          ("two", "bs65536"), ("l2", "bs4096"), ("l2", "bs65536"), ("long", "bs65536"), ("const41", "bs4096"),
          ("const41", "bs4099"), ("const41", "bs65536"), ("mix", "bs4096"), ("mix", "bs4099")]
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def codec(torch_mod):
-    from libhuffman_amd.codec import GpuCodec
-    c = GpuCodec(0)
-    yield c
-    c.close()
-
-
-_cache = {}
-
-
-def encoded(torch, codec, kind, shape):
-    """one encode per (input, shape) for the whole module; the tests never change it"""
-    if (kind, shape) not in _cache:
-        bs, n = SHAPES[shape]
-        if kind == "mix":                               # one-symbol and ordinary blocks alternate
-            data = datagen.zipf255(n, seed=4).copy()
-            for b in range(0, n, 2 * bs):
-                data[b:b + bs] = 41
-        else:
-            data = make(kind, n, bs)
-        enc = Enc(torch, codec, data, bs, sub=True)
-        enc.raw_size, enc.row_bs = enc.n, enc.bs
-        _cache[kind, shape] = enc
-    return _cache[kind, shape]
 
 
 def value_sets(data):
@@ -76,38 +33,9 @@ def value_sets(data):
     return sets
 
 
-def find(torch, codec, enc, values, cap, counts=True, sub=None, relaxed=False, raw_size=None, blocksize=None):
-    """one call; returns host arrays (the guarded position buffer or None, totals, errs, counts or None)"""
-    buf = torch.full((LEAD + cap + TAIL,), GUARD64, dtype=torch.int64, device="cuda") if cap else None
-    _, totals, errs, cnt = codec.find_bytes(enc.stream, enc.length, enc.offsets, enc.nb, enc.sub if sub is None else sub,
-                                            enc.raw_size if raw_size is None else raw_size,
-                                            enc.row_bs if blocksize is None else blocksize, values, max_positions=cap,
-                                            block_counts=counts, relaxed=relaxed, out=buf[LEAD:LEAD + cap] if cap else None)
-    return (buf.cpu().numpy() if cap else None, totals.cpu().numpy(), errs.cpu().numpy(),
-            cnt.cpu().numpy() if counts else None)
-
-
-def check(res, want, cap, what=""):
-    """the call's host arrays against the model's (positions, counts, totals): everything, and the guards"""
-    buf, totals, errs, cnt = res
-    pos, counts, wtotals = want
-    assert totals.tolist() == wtotals.tolist(), (what, totals, wtotals)
-    assert int(np.count_nonzero(errs)) == int(totals[2]), what
-    if cnt is not None:
-        assert np.array_equal(cnt, counts), (what, np.flatnonzero(cnt != counts)[:8])
-    if cap:
-        full = np.full(LEAD + cap + TAIL, GUARD64, np.int64)
-        full[LEAD:LEAD + pos.size] = pos
-        bad = np.flatnonzero(buf != full)
-        assert bad.size == 0, (what, "position words differ at", bad[:8] - LEAD, buf[bad[:8]], full[bad[:8]])
-
-
 def check_exact_or_not_served(enc, res, values, cap, what=""):
     """every block has status 0 and its exact count and positions, or a non-zero status and contributes nothing"""
-    errs = res[2]
-    assert set(errs.tolist()) <= {OK, RW}, what
-    check(res, find_model(enc.data, values, enc.bs, cap, served=errs == OK), cap, what)
-    return errs
+    return answer_or_not_served(lambda cap: res, lambda cap, served: find_model(enc.data, values, enc.bs, cap, served=served), cap, what)
 
 
 # ---- equality ----------------------------------------------------------------------------------------------------------
@@ -191,16 +119,6 @@ def test_sub_index_abuse(torch_mod, codec, kind, shape):
 
 
 # ---- damage ------------------------------------------------------------------------------------------------------------
-def damaged(enc, at, xor):
-    st = enc.stream.clone()
-    st[at] ^= xor
-    return enc.with_stream(st)
-
-
-def payload_start(enc, b):
-    bo = int(enc.h_offs[b])
-    tl = int.from_bytes(bytes(enc.stream[bo + 8:bo + 10].cpu().numpy()), "little")
-    return bo + 10 + 2 * tl
 
 
 def only_this_block(enc, res, values, cap, b):

@@ -16,18 +16,11 @@ import pytest
 from find_anchor_model import BOL, EOL, WORD, find_any_anchored_model, find_records_anchored_model
 from find_any_model import find_any_model
 from find_context_model import find_context_model
-from libhuffman_amd.codec import GpuCodec
-from test_gpu_find import GUARD64, LEAD, OK, RW, TAIL, check, damaged, payload_start
-from test_gpu_find_classes import SHAPES, TILE, psearch, same_arrays
-from test_gpu_find_context import GUARD8, check_context, context
-from test_gpu_find_pattern import encode
-from test_gpu_find_records import GUARD32
-from test_gpu_find_select import SEAMS, runs_input
+from find_support import (FOUR_SHAPES, GUARD32, GUARD64, OK, RW, SEAMS, AnyOf, W, check, codec, context, damaged, encode, exact_answer,
+                          literal, payload_start, positions, psearch, records, runs_input, same_arrays, torch_mod)
 
 pytestmark = pytest.mark.gpu
 
-AnyOf = GpuCodec.AnyOf
-W = GpuCodec.WORD_BYTES
 ANCHORS = [BOL, EOL, WORD, BOL | EOL, BOL | WORD, EOL | WORD, 7]
 NAMES = {BOL: "bol", EOL: "eol", WORD: "word", BOL | EOL: "x", BOL | WORD: "bol-word", EOL | WORD: "eol-word", 7: "all"}
 EVERY = pytest.mark.parametrize("anchors", ANCHORS, ids=[NAMES[a] for a in ANCHORS])
@@ -35,79 +28,13 @@ FILL = np.frombuffer(b". -", np.uint8)                   # neither a word byte n
 NEIGHBOURS = b"\n x"                                       # a delimiter, a boundary byte that is none, a word byte
 
 
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def codec(torch_mod):
-    c = GpuCodec(0)
-    yield c
-    c.close()
-
-
-# ---- the calls and the checks ------------------------------------------------------------------------------------------------
-def literal(word):
-    return [bytes([v]) for v in word]
-
-
-def positions(torch, codec, enc, alts, anchors, cap, delims=b"\n", words=W, counts=True, sub=None):
-    """one hufgpu_find_any_anchored call; host arrays (the guarded position buffer or None, totals, errs, counts or None)"""
-    classes, lens = GpuCodec.alt_classes(AnyOf(*alts))
-    buf = torch.full((LEAD + cap + TAIL,), GUARD64, dtype=torch.int64, device="cuda") if cap else None
-    totals = torch.empty(4, dtype=torch.int64, device="cuda")
-    errs = torch.empty(enc.nb, dtype=torch.int32, device="cuda")
-    cnt = torch.empty(enc.nb, dtype=torch.int64, device="cuda") if counts else None
-    sub = enc.sub if sub is None else sub
-    err = codec.lib.hufgpu_find_any_anchored(
-        codec._ctx, enc.stream.data_ptr(), enc.length, enc.offsets.data_ptr(), enc.nb, sub.data_ptr(), enc.raw_size, enc.row_bs,
-        classes.tobytes(), lens.tobytes(), len(lens), None if delims is None else GpuCodec.byte_set(delims),
-        None if words is None else GpuCodec.byte_set(words), anchors, buf[LEAD:].data_ptr() if cap else None, cap,
-        cnt.data_ptr() if counts else None, totals.data_ptr(), errs.data_ptr(), 0, codec._stream())
-    codec._check(err, "Failed to enqueue the search")
-    return (buf.cpu().numpy() if cap else None, totals.cpu().numpy(), errs.cpu().numpy(), cnt.cpu().numpy() if counts else None)
-
-
-def records(torch, codec, enc, alts, anchors, cap, delims=b"\n", words=W, max_len=0, invert=False, before=0, after=0, numbers=True,
-            flags=True, counts=True, sub=None):
-    """one hufgpu_find_records_anchored call; host arrays in the order of tests/test_gpu_find_context.py's `context`: (starts,
-    lengths, totals, errs, counts, numbers, flags)"""
-    classes, lens = GpuCodec.alt_classes(AnyOf(*alts))
-    pbuf = torch.full((LEAD + cap + TAIL,), GUARD64, dtype=torch.int64, device="cuda") if cap else None
-    lbuf = torch.full((LEAD + cap + TAIL,), GUARD32, dtype=torch.int32, device="cuda") if cap else None
-    nbuf = torch.full((LEAD + cap + TAIL,), GUARD64, dtype=torch.int64, device="cuda") if numbers else None
-    sbuf = torch.full((LEAD + cap + TAIL,), GUARD8, dtype=torch.uint8, device="cuda") if flags else None
-    totals = torch.empty(4, dtype=torch.int64, device="cuda")
-    errs = torch.empty(enc.nb, dtype=torch.int32, device="cuda")
-    cnt = torch.empty(enc.nb, dtype=torch.int64, device="cuda") if counts else None
-    sub = enc.sub if sub is None else sub
-    err = codec.lib.hufgpu_find_records_anchored(
-        codec._ctx, enc.stream.data_ptr(), enc.length, enc.offsets.data_ptr(), enc.nb, sub.data_ptr(), enc.raw_size, enc.row_bs,
-        GpuCodec.byte_set(delims), classes.tobytes(), lens.tobytes(), len(lens), None if words is None else GpuCodec.byte_set(words), anchors,
-        1 if invert else 0, before, after, pbuf[LEAD:].data_ptr() if cap else None, lbuf[LEAD:].data_ptr() if cap else None,
-        nbuf[LEAD:].data_ptr() if numbers else None, sbuf[LEAD:].data_ptr() if flags else None, cap, max_len,
-        cnt.data_ptr() if counts else None, totals.data_ptr(), errs.data_ptr(), 0, codec._stream())
-    codec._check(err, "Failed to enqueue the search")
-    return (pbuf.cpu().numpy() if cap else None, lbuf.cpu().numpy() if cap else None, totals.cpu().numpy(), errs.cpu().numpy(),
-            cnt.cpu().numpy() if counts else None, nbuf.cpu().numpy() if numbers else None, sbuf.cpu().numpy() if flags else None)
-
-
+# ---- the checks --------------------------------------------------------------------------------------------------------------
 def pos_exact(torch, codec, enc, alts, anchors, delims=b"\n", words=W, room=5, what="", sub=None, all_served=True):
     """the count alone and the positions, each the model's for the blocks with status 0; returns (the model's positions, statuses)"""
-    what = (what, "positions", anchors)
-    probe = positions(torch, codec, enc, alts, anchors, 0, delims, words, sub=sub)
-    errs = probe[2]
-    assert set(errs.tolist()) <= {OK, RW} and (not all_served or not errs.any()), (what, errs)
-    served = errs == OK
-    full = find_any_anchored_model(enc.data, alts, delims, words, anchors, enc.bs, enc.n, served)
-    check(probe, find_any_anchored_model(enc.data, alts, delims, words, anchors, enc.bs, 0, served), 0, (what, "count"))
-    cap = int(full[2][0]) + room
-    res = positions(torch, codec, enc, alts, anchors, cap, delims, words, sub=sub)
-    assert np.array_equal(res[2], errs), what
-    check(res, find_any_anchored_model(enc.data, alts, delims, words, anchors, enc.bs, cap, served), cap, what)
+    full, _, errs = exact_answer(lambda cap: positions(torch, codec, enc, alts, anchors, cap, delims, words, sub=sub),
+                          lambda cap, served: find_any_anchored_model(enc.data, alts, delims, words, anchors, enc.bs, cap, served),
+                          enc.n, room=room, what=(what, "positions", anchors), all_served=all_served,
+                          probe=lambda: positions(torch, codec, enc, alts, anchors, 0, delims, words, sub=sub))
     return full[0], errs
 
 
@@ -115,17 +42,11 @@ def rec_exact(torch, codec, enc, alts, anchors, delims=b"\n", words=W, before=0,
               sub=None, all_served=True):
     """... and the records call's four outputs; returns (the model's answer at a cap that holds every record, the statuses)"""
     kw = dict(invert=invert, before=before, after=after)
-    what = (what, "records", anchors, before, after, invert)
-    probe = records(torch, codec, enc, alts, anchors, 0, delims, words, numbers=False, flags=False, sub=sub, **kw)
-    errs = probe[3]
-    assert set(errs.tolist()) <= {OK, RW} and (not all_served or not errs.any()), (what, errs)
-    served = errs == OK
-    full = find_records_anchored_model(enc.data, alts, delims, words, anchors, enc.bs, enc.n, max_len, served, **kw)
-    check_context(probe, find_records_anchored_model(enc.data, alts, delims, words, anchors, enc.bs, 0, max_len, served, **kw), 0, (what, "count"))
-    cap = int(full[3][0]) + room
-    res = records(torch, codec, enc, alts, anchors, cap, delims, words, max_len, sub=sub, **kw)
-    assert np.array_equal(res[3], errs), what
-    check_context(res, find_records_anchored_model(enc.data, alts, delims, words, anchors, enc.bs, cap, max_len, served, **kw), cap, what)
+    full, _, errs = exact_answer(lambda cap: records(torch, codec, enc, alts, anchors, cap, delims, words, max_len, sub=sub, **kw),
+                          lambda cap, served: find_records_anchored_model(enc.data, alts, delims, words, anchors, enc.bs, cap, max_len,
+                                                                          served, **kw),
+                          enc.n, room=room, what=(what, "records", anchors, before, after, invert), all_served=all_served,
+                          probe=lambda: records(torch, codec, enc, alts, anchors, 0, delims, words, numbers=False, flags=False, sub=sub, **kw))
     return full, errs
 
 
@@ -143,10 +64,10 @@ def put(data, at, word, left, right):
 
 
 # ---- 1: the identity ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_no_anchor_is_the_older_call_word_for_word(torch_mod, codec, shape):
     torch = torch_mod
-    bs, n, starts = SHAPES[shape]
+    bs, n, starts = FOUR_SHAPES[shape]
     data = filler(n, 500)
     for i, s in enumerate(starts + SEAMS[shape]):
         if 0 < s and s + 4 < n:
@@ -163,14 +84,14 @@ def test_no_anchor_is_the_older_call_word_for_word(torch_mod, codec, shape):
                 got = records(torch, codec, enc, alts, 0, cap, b"\n", words, counts=counts, **kw)
                 assert same_arrays(got, context(torch, codec, enc, alts, b"\n", cap, counts=counts, **kw)), (shape, cap, kw)
     assert int(got[2][0]) > 0
-    check_context(records(torch, codec, enc, alts, 0, n), find_context_model(data, alts, b"\n", bs, n), n, shape)
+    check(records(torch, codec, enc, alts, 0, n), find_context_model(data, alts, b"\n", bs, n), n, shape)
 
 
 # ---- 2: dense random data, every anchor ----------------------------------------------------------------------------------------
 @EVERY
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_dense_random_data(torch_mod, codec, shape, anchors):
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     rng = np.random.default_rng(510 + anchors)
     data = rng.choice(np.frombuffer(b"abc\n x_", np.uint8), n, p=[0.2, 0.2, 0.2, 0.1, 0.15, 0.1, 0.05]).astype(np.uint8)
     enc = encode(torch_mod, codec, data, bs)
@@ -194,7 +115,7 @@ def test_dense_random_data(torch_mod, codec, shape, anchors):
 def test_word_bytes_and_delimiters_of_the_caller(torch_mod, codec):
     """a delimiter that is a word byte, D and the bytes that are no word byte without a byte in common, no word bytes at all,
     every byte a word byte, two delimiters"""
-    bs, n, _ = SHAPES["5x4099"]
+    bs, n, _ = FOUR_SHAPES["5x4099"]
     rng = np.random.default_rng(520)
     data = rng.choice(np.frombuffer(b"abc\n x_", np.uint8), n, p=[0.2, 0.2, 0.2, 0.1, 0.15, 0.1, 0.05]).astype(np.uint8)
     enc = encode(torch_mod, codec, data, bs)
@@ -209,13 +130,13 @@ def test_word_bytes_and_delimiters_of_the_caller(torch_mod, codec):
 
 # ---- 3: a hit and its neighbours at every seam ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("place", [1, 0, -2, -3], ids=["left-neighbour", "first-byte", "last-byte", "right-neighbour"])
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_a_hit_and_its_neighbours_at_every_seam(torch_mod, codec, shape, place):
     """the hit's left neighbour, its first byte, its last byte or its right neighbour is the first byte of a lane's word, a
     tile, a chunk, a block, a scan group; the two neighbours rotate through a delimiter, a boundary byte that is none and a
     word byte"""
     torch = torch_mod
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     word = b"abc"
     for rot in range(3):
         data = filler(n, 530 + rot)
@@ -232,12 +153,12 @@ def test_a_hit_and_its_neighbours_at_every_seam(torch_mod, codec, shape, place):
 
 
 # ---- 4: the data's two ends ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_hits_at_byte_0_and_at_the_data_s_end(torch_mod, codec, shape):
     """no byte in front of byte 0 and none behind the last one: neither stands in the way.  The word of five bytes that ends
     the data starts in front of the last tile where that one is shorter (3 symbols, 2 bytes of the last block of 200 x 3)"""
     torch = torch_mod
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     word, short = b"abcab", b"q"
     for last in (word, short, b"x" + short):                # ... and a word byte in front of the last byte
         data = filler(n, 540)
@@ -263,11 +184,11 @@ def test_hits_at_byte_0_and_at_the_data_s_end(torch_mod, codec, shape):
 
 
 # ---- 5: the shortest and the longest alternatives ------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_alternatives_of_1_2_and_63_positions(torch_mod, codec, shape):
     """63 positions and the boundary's: the 64 bits of the state, 63 edge bytes a tile"""
     torch = torch_mod
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     long = bytes(np.random.default_rng(550).choice(np.frombuffer(b"abc", np.uint8), 63).astype(np.uint8))
     data = filler(n, 551)
     at = [p - 31 for p in SEAMS[shape] if p - 31 >= 1 and p + 33 <= n] + [n - 63]
@@ -296,7 +217,7 @@ def test_one_symbol_blocks_next_to_ordinary_ones(torch_mod, codec, shape):
     front of it and one that starts just behind it; the alternatives of one byte lie INSIDE such blocks, where the one value is
     then its own neighbour"""
     torch = torch_mod
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     nb = (n + bs - 1) // bs
     data = filler(n, 560)
     for k, b in enumerate(range(1, nb - 1, 2 if nb < 10 else 7)):
@@ -367,7 +288,7 @@ def test_sub_index_abuse(torch_mod, codec, sub):
 # ---- 8: caps ---------------------------------------------------------------------------------------------------------------------
 def test_caps(torch_mod, codec):
     torch = torch_mod
-    bs, n, starts = SHAPES["5x4099"]
+    bs, n, starts = FOUR_SHAPES["5x4099"]
     data = filler(n, 580)
     for i, s in enumerate(starts[1:]):
         put(data, s, b"abc", NEIGHBOURS[i % 2], NEIGHBOURS[(i // 2) % 2])
@@ -387,7 +308,7 @@ def test_caps(torch_mod, codec):
         for cap in (0, 1, total - 1, total):
             for numbers, flags, max_len in ((True, True, 0), (False, True, 7), (True, False, 1), (False, False, 0)):
                 res = records(torch, codec, enc, alts, BOL, cap, max_len=max_len, numbers=numbers, flags=flags, **kw)
-                check_context(res, find_records_anchored_model(data, alts, b"\n", W, BOL, bs, cap, max_len, **kw), cap, (invert, cap, numbers, flags))
+                check(res, find_records_anchored_model(data, alts, b"\n", W, BOL, bs, cap, max_len, **kw), cap, (invert, cap, numbers, flags))
 
 
 # ---- 9: one context, call after call ---------------------------------------------------------------------------------------------
@@ -395,7 +316,7 @@ def test_eight_calls_back_to_back(torch_mod, codec):
     """anchored and older calls alternate without a synchronise in between: each gives its own model's answer, and the third
     mask, the boundary mask in the delimiters' place and the longer table of one call leave nothing behind for the next"""
     torch = torch_mod
-    bs, n, starts = SHAPES["5x4099"]
+    bs, n, starts = FOUR_SHAPES["5x4099"]
     data = filler(n, 590)
     for i, s in enumerate(starts[1:] + SEAMS["5x4099"]):
         put(data, s, b"abc", NEIGHBOURS[i % 3], NEIGHBOURS[(i // 3) % 3])

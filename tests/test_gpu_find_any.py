@@ -8,92 +8,34 @@ behind and is filled with the guard first: the words beyond totals[1] must still
 those of tests/test_gpu_find_classes.py: five blocks of 4 099 bytes (tiles of 2 048, 2 048 and 3 symbols), 300 blocks of 64
 bytes (two scan groups), 200 blocks of 3 bytes, one block of 3 x 65 536 + 77 bytes (three chunks).
 """
+import functools
 import re
 
 import numpy as np
 import pytest
 
+import find_support
 from find_any_model import find_any_model, find_any_records_model
 from find_classes_model import find_class_records_model, find_classes_model
 from find_model import find_model
 from find_pattern_model import find_pattern_model
+from find_support import (ANY, FOUR_SHAPES, GUARD32, GUARD64, LEAD, NOT_NL, OK, RW, TAIL, TILE, TILE_END, AnyOf, base_of, base_without,
+                          check, codec, damaged, encode, mixed_blocks, pattern_below_255, payload_start, planted, planted_each,
+                          psearch, rsearch, same_arrays, spellings, torch_mod, two_values, with_delimiters)
 from libhuffman_amd import datagen
 from libhuffman_amd.codec import GpuCodec
-from test_gpu_find import GUARD64, LEAD, OK, RW, TAIL, check, damaged, payload_start
-from test_gpu_find_classes import (ANY, NOT_NL, SHAPES, TILE, base_of, pattern_of, planted_each, psearch, rsearch, same_arrays,
-                                   spellings, two_values)
-from test_gpu_find_pattern import encode, mixed_blocks, planted
-from test_gpu_find_records import GUARD32, base_without, with_delimiters
-from test_gpu_find_records import check as check_records
 
 pytestmark = pytest.mark.gpu
 
-AnyOf = GpuCodec.AnyOf
 MIXES = [(2, 5, 33), (31, 33), (32, 32), (1, 63)]
 MIX_IDS = ["x".join(map(str, m)) for m in MIXES]
-# a tile's end inside each shape, away from the shapes' planted starts: a short alternative is put right in front of it
-TILE_END = {"5x4099": 4 * 4099 + TILE, "300x64": 21 * 64, "200x3": 51 * 3, "3chunks": 5 * TILE}
 
 
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def codec(torch_mod):
-    c = GpuCodec(0)
-    yield c
-    c.close()
-
-
-# ---- calls and checks ------------------------------------------------------------------------------------------------------
-def exact(torch, codec, enc, alts, must=(), must_not=(), room=7, what="", model=None, **kw):
-    """all blocks served and everything equal to the model; `must` / `must_not`: starts the model is seen to hold / lack.
-    `model`: the alternatives the model gets when the call gets something else (literals with ignore_case).  Returns
-    (total, the call's host arrays)"""
-    model = alts if model is None else model
-    pos, counts, totals = find_any_model(enc.data, model, enc.bs, enc.n)
-    total = int(totals[0])
-    assert 0 < total < enc.n, (what, "the planted input has", total, "matches")
-    found = set(pos.tolist())
-    assert found >= set(must) and not found & set(must_not), (what, sorted(set(must) - found), sorted(found & set(must_not)))
-    res = psearch(torch, codec, enc, AnyOf(*alts), total + room, **kw)
-    assert not res[2].any(), (what, np.flatnonzero(res[2])[:8])
-    check(res, find_any_model(enc.data, model, enc.bs, total + room), total + room, what)
-    return total, res
-
-
-def records_exact(torch, codec, enc, alts, delims=b"\n", must=(), must_not=(), room=7, max_len=0, what="", model=None, **kw):
-    model = alts if model is None else model
-    pos, lens, counts, totals = find_any_records_model(enc.data, model, delims, enc.bs, enc.n, max_len)
-    total = int(totals[0])
-    assert total > 0, (what, "the planted input has no matching record")
-    found = set(pos.tolist())
-    assert found >= set(must) and not found & set(must_not), (what, sorted(set(must) - found), sorted(found & set(must_not)))
-    res = rsearch(torch, codec, enc, AnyOf(*alts), delims, total + room, max_len, **kw)
-    assert not res[3].any(), (what, np.flatnonzero(res[3])[:8])
-    check_records(res, find_any_records_model(enc.data, model, delims, enc.bs, total + room, max_len), total + room, what)
-    return pos, lens, res
-
-
-def exact_or_not_served(torch, codec, enc, alts, cap, sub=None, what=""):
-    """every block has status 0 or RW, and the answer is the model's for the blocks with status 0"""
-    res = psearch(torch, codec, enc, AnyOf(*alts), cap, sub=sub)
-    errs = res[2]
-    assert set(errs.tolist()) <= {OK, RW}, what
-    check(res, find_any_model(enc.data, alts, enc.bs, cap, served=errs == OK), cap, what)
-    return errs
-
-
-def records_exact_or_not_served(torch, codec, enc, alts, delims, cap, sub=None, max_len=0, what=""):
-    res = rsearch(torch, codec, enc, AnyOf(*alts), delims, cap, max_len, sub=sub)
-    errs = res[3]
-    assert set(errs.tolist()) <= {OK, RW}, what
-    check_records(res, find_any_records_model(enc.data, alts, delims, enc.bs, cap, max_len, served=errs == OK), cap, what)
-    return errs
+# ---- checks ----------------------------------------------------------------------------------------------------------------
+exact = functools.partial(find_support.exact_positions, find_any_model, find_support.any_of)
+exact_or_not_served = functools.partial(find_support.positions_exact_or_not_served, find_any_model, find_support.any_of)
+records_exact = functools.partial(find_support.exact_records, find_any_records_model, find_support.any_of)
+records_exact_or_not_served = functools.partial(find_support.records_exact_or_not_served, find_any_records_model, find_support.any_of)
 
 
 def widened(pat, every=3):
@@ -103,11 +45,11 @@ def widened(pat, every=3):
 
 # ---- identities, in the same process ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("length", [1, 2, 5, 33, 64])
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_one_alternative_is_the_class_call(torch_mod, codec, shape, length):
     """positions and records, word for word, with the pattern at every seam, at the data's end and one byte past it"""
-    bs, n, starts = SHAPES[shape]
-    pat = pattern_of(length, 100 + length)
+    bs, n, starts = FOUR_SHAPES[shape]
+    pat = pattern_below_255(length, 100 + length)
     classes = widened(pat)
     for last in (n - length, n - length + 1):
         data = planted(base_of(shape), pat, starts + [last])
@@ -119,14 +61,14 @@ def test_one_alternative_is_the_class_call(torch_mod, codec, shape, length):
         assert same_arrays(res, psearch(torch_mod, codec, enc, classes, total + 7)), (shape, length, "differs from find_classes")
         got = rsearch(torch_mod, codec, enc, AnyOf(classes), b"\n", 5, max_len=100)
         assert same_arrays(got, rsearch(torch_mod, codec, enc, classes, b"\n", 5, max_len=100)), (shape, length, "records differ")
-        check_records(got, find_class_records_model(data, classes, b"\n", bs, 5, 100), 5, (shape, length))
+        check(got, find_class_records_model(data, classes, b"\n", bs, 5, 100), 5, (shape, length))
 
 
 @pytest.mark.parametrize("count", [1, 3, 64])
 @pytest.mark.parametrize("shape", ["5x4099", "300x64"])
 def test_alternatives_of_one_position_are_find_bytes(torch_mod, codec, shape, count):
     torch = torch_mod
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     data = base_of(shape)
     enc = encode(torch, codec, data, bs)
     rng = np.random.default_rng(count)
@@ -144,9 +86,9 @@ def test_alternatives_of_one_position_are_find_bytes(torch_mod, codec, shape, co
     check(res, find_any_model(data, [[s] for s in sets], bs, cap), cap, count)
 
 
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_alternatives_are_the_union_of_their_class_calls(torch_mod, codec, shape):
-    bs, n, starts = SHAPES[shape]
+    bs, n, starts = FOUR_SHAPES[shape]
     words = [b"ERROR", b"Fatal", b"panic:", b"ERR"]         # (ERR lies wherever ERROR does: those starts count once)
     data = planted_each(base_of(shape), [words[i % 3] for i in range(len(starts))], starts)
     enc = encode(torch_mod, codec, data, bs)
@@ -165,13 +107,13 @@ def test_alternatives_are_the_union_of_their_class_calls(torch_mod, codec, shape
 
 # ---- mixed lengths ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mix", MIXES, ids=MIX_IDS)
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_mixed_lengths(torch_mod, codec, shape, mix):
     """every alternative at every lane, tile, chunk and block seam of the shape (the plants rotate through the starts); the
     shortest one right in front of a tile's end, where the longest does not fit - found once, by the seam kernel -; at
     n - len_short, where the longest would pass raw_size; and at n - len_short + 1, where nothing lies"""
-    bs, n, starts = SHAPES[shape]
-    lits = [pattern_of(m, 500 + 70 * j + m) for j, m in enumerate(mix)]
+    bs, n, starts = FOUR_SHAPES[shape]
+    lits = [pattern_below_255(m, 500 + 70 * j + m) for j, m in enumerate(mix)]
     alts = [widened(p) for p in lits]
     short = min(lits, key=len)
     tsym = min(bs or TILE, TILE)
@@ -191,7 +133,7 @@ def test_mixed_lengths(torch_mod, codec, shape, mix):
 # ---- the same start, and what one alternative must not do to another ---------------------------------------------------------
 @pytest.mark.parametrize("shape", ["5x4099", "300x64", "3chunks"])
 def test_two_alternatives_at_one_start_count_once(torch_mod, codec, shape):
-    bs, n, starts = SHAPES[shape]
+    bs, n, starts = FOUR_SHAPES[shape]
     base = base_of(shape).copy()
     base[base == ord("a")] = ord("e")                       # no `a` but the planted ones
     data = planted_each(base, [b"abc", b"abd"] * len(starts), starts)
@@ -205,7 +147,7 @@ def test_two_alternatives_at_one_start_count_once(torch_mod, codec, shape):
 @pytest.mark.parametrize("shape", ["5x4099", "300x64"])
 def test_no_cross_talk_between_alternatives(torch_mod, codec, shape):
     """`ab` and `cd` lie next to each other in the state: `ad`, `cb` and `bc` are no match, `abcd` is two"""
-    bs, n, starts = SHAPES[shape]
+    bs, n, starts = FOUR_SHAPES[shape]
     base = base_of(shape).copy()
     base[np.isin(base, list(b"abcd"))] = ord("e")
     plants = [b"ad", b"cb", b"bc", b"abcd"]
@@ -221,7 +163,7 @@ def test_no_cross_talk_between_alternatives(torch_mod, codec, shape):
 
 @pytest.mark.parametrize("shape", ["5x4099", "300x64"])
 def test_dense_random_data_over_four_letters(torch_mod, codec, shape):
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     rng = np.random.default_rng(77)
     letters = np.frombuffer(b"abcd", np.uint8)
     enc = encode(torch_mod, codec, rng.choice(letters, n).astype(np.uint8), bs)
@@ -233,7 +175,7 @@ def test_dense_random_data_over_four_letters(torch_mod, codec, shape):
 
 def test_the_longer_alternative_reaches_a_block_that_is_not_served(torch_mod, codec):
     torch = torch_mod
-    bs, n, starts = SHAPES["5x4099"]
+    bs, n, starts = FOUR_SHAPES["5x4099"]
     base = base_of("5x4099").copy()
     base[base == ord("a")] = ord("e")
     only_long, both = 2 * bs - 3, 3 * bs - 1                # `ab` ends inside block 1 / `ab` itself crosses into block 3
@@ -280,7 +222,7 @@ def test_one_symbol_blocks(torch_mod, codec):
 def test_one_symbol_and_ordinary_blocks_alternate(torch_mod, codec, bs):
     torch = torch_mod
     data = mixed_blocks(bs, 6, 26)
-    tail, head = pattern_of(6, 1), pattern_of(5, 2)
+    tail, head = pattern_below_255(6, 1), pattern_below_255(5, 2)
     out_of, into = b")" * 4 + tail, head + b")" * 3
     s_out, s_in = [bs - 4, 3 * bs - 4], [2 * bs - 5, 4 * bs - 5]
     data = planted(planted(data, out_of, s_out), into, s_in)
@@ -352,7 +294,7 @@ def test_sub_index_abuse(torch_mod, codec, sub):
 # ---- the caps --------------------------------------------------------------------------------------------------------------
 def test_caps(torch_mod, codec):
     torch = torch_mod
-    bs, n, starts = SHAPES["5x4099"]
+    bs, n, starts = FOUR_SHAPES["5x4099"]
     words = [b"Warning", b"Oops"]
     nl = [40, 1500, 2046, bs, 2 * bs + 2100, 2 * bs + 4090, 3 * bs + 3000]
     starts = starts + [starts[1] + 20, n - 7]               # (two matches in one record)
@@ -372,7 +314,7 @@ def test_caps(torch_mod, codec):
         for counts in (True, False):
             res = rsearch(torch, codec, enc, AnyOf(*words), b"\n", cap, counts=counts, ignore_case=True)
             assert not res[3].any() and int(res[2][0]) == rtotal
-            check_records(res, find_any_records_model(data, model, b"\n", bs, cap), cap, (cap, counts))
+            check(res, find_any_records_model(data, model, b"\n", bs, cap), cap, (cap, counts))
     totals, errs = codec.count_records(enc.stream, enc.length, enc.offsets, enc.nb, enc.sub, n, bs, AnyOf(*words), ignore_case=True)
     assert totals.cpu().tolist() == [rtotal, 0, 0, 0] and not errs.cpu().numpy().any()
     args = (enc.stream, enc.length, enc.offsets, enc.nb, enc.sub, n, bs)
@@ -426,7 +368,7 @@ def test_records_at_the_seams(torch_mod, codec):
 def test_one_record_over_all_blocks(torch_mod, codec, shape):
     """a match of one alternative or the other in every tile; the empty delimiter set and a delimiter that never occurs both
     give ONE entry, (0, n)"""
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     base = base_without(n, 42)
     nb = (n + bs - 1) // bs
     alts = [[b"Qq", b"Zz"], [b"Xx", b"Yy"], [b"Q", b"Y", b"Z"]]
@@ -436,10 +378,10 @@ def test_one_record_over_all_blocks(torch_mod, codec, shape):
         res = rsearch(torch_mod, codec, enc, AnyOf(*alts), delims, 3)
         assert res[2].tolist() == [1, 1, 0, 0] and not res[3].any(), (delims, res[2])
         assert res[0][LEAD] == 0 and int(res[1].view(np.uint32)[LEAD]) == n, delims
-        check_records(res, find_any_records_model(data, alts, delims, bs, 3), 3, delims)
+        check(res, find_any_records_model(data, alts, delims, bs, 3), 3, delims)
         assert res[4].tolist() == [1] + [0] * (nb - 1)
     res = rsearch(torch_mod, codec, enc, AnyOf([ANY, b"Zz"], [b"y"]), b"", 3)   # the full class with the empty delimiter set
-    check_records(res, find_any_records_model(data, [[ANY, b"Zz"], [b"y"]], b"", bs, 3), 3, "any")
+    check(res, find_any_records_model(data, [[ANY, b"Zz"], [b"y"]], b"", bs, 3), 3, "any")
 
 
 def test_grep_any_of_ignore_case(torch_mod, codec):
@@ -475,7 +417,7 @@ def test_calls_back_to_back(torch_mod, codec):
     without a synchronise in between: each gives its own model's answer, and the older calls the same after an any-of call
     as before it"""
     torch = torch_mod
-    bs, n, starts = SHAPES["5x4099"]
+    bs, n, starts = FOUR_SHAPES["5x4099"]
     words = [b"Segfault", b"abort"]
     nl = [40, 1500, 2046, bs, 2 * bs + 2100, 2 * bs + 4090, 3 * bs + 3000]
     plants = [spellings(words[i % 2], 2 + i, 5 + i)[-1] for i in range(len(starts))]
@@ -523,7 +465,7 @@ def test_calls_back_to_back(torch_mod, codec):
     for (kind, key), (cap, pbuf, lbuf), r in zip(jobs, bufs, res):
         if "records" in kind:
             got = (pbuf.cpu().numpy(), lbuf.cpu().numpy(), r[2].cpu().numpy(), r[3].cpu().numpy(), r[4].cpu().numpy())
-            check_records(got, model(kind, cap), cap, kind)
+            check(got, model(kind, cap), cap, kind)
         else:
             got = (pbuf.cpu().numpy(), r[1].cpu().numpy(), r[2].cpu().numpy(), r[3].cpu().numpy())
             check(got, model(kind, cap), cap, kind)

@@ -8,164 +8,39 @@ and behind and is filled with the guard first: the words beyond totals[1] must s
 tests/test_gpu_find_pattern.py, the smallest that reach every seam: five blocks of 4 099 bytes (tiles of 2 048, 2 048 and 3
 symbols), 300 blocks of 64 bytes (two scan groups), 200 blocks of 3 bytes, one block of 3 x 65 536 + 77 bytes (three chunks).
 """
+import functools
 import re
 
 import numpy as np
 import pytest
 
+import find_support
 from find_classes_model import find_class_records_model, find_classes_model
 from find_model import find_model
 from find_pattern_model import find_pattern_model
 from find_records_model import find_records_model
+from find_support import (ANY, CHUNK, FOUR_SHAPES, GUARD32, GUARD64, LEAD, NL, NOT_NL, OK, RW, TAIL, TILE, base_of, base_without, check,
+                          codec, damaged, encode, mixed_blocks, pattern_below_255, payload_start, planted, planted_each, psearch,
+                          rsearch, same_arrays, spellings, torch_mod, two_values, with_delimiters)
 from libhuffman_amd import datagen
 from libhuffman_amd.codec import GpuCodec
-from test_gpu_find import GUARD64, LEAD, OK, RW, TAIL, check, damaged, payload_start
-from test_gpu_find_pattern import encode, mixed_blocks, planted
-from test_gpu_find_records import GUARD32, base_without, with_delimiters
-from test_gpu_find_records import check as check_records
 
 pytestmark = pytest.mark.gpu
 
-TILE, CHUNK = 2048, 65536
-NL = 10
-ANY = GpuCodec.ANY
-NOT_NL = bytes(v for v in range(256) if v != NL)
-# shape -> (blocksize, bytes, starts that reach its seams: lane, tile, chunk, block, scan group; 64 bytes apart at least)
-SHAPES = {
-    "5x4099": (4099, 5 * 4099, [0, 1000, 2047, 4099 + 31, 4099 + 2 * TILE - 10, 2 * 4099 + 2000, 2 * 4099 + 4096, 3 * 4099 + 2047,
-                                3 * 4099 + 4098]),
-    "300x64": (64, 299 * 64 + 21, [1, 5 * 64, 10 * 64 + 40, 253 * 64 + 60, 255 * 64 + 1, 270 * 64 + 63]),
-    "200x3": (3, 200 * 3 - 1, [1, 70 * 3 + 2, 100 * 3]),
-    "3chunks": (0, 3 * CHUNK + 77, [31, TILE - 1, CHUNK - 10, CHUNK + TILE - 4, 2 * CHUNK - 63, 2 * CHUNK + 3 * TILE - 1]),
-}
 
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def codec(torch_mod):
-    c = GpuCodec(0)
-    yield c
-    c.close()
-
-
-_base = {}
-
-
-def base_of(shape):
-    """zipf-like bytes of the shape, made once; never changed (planted() copies)"""
-    if shape not in _base:
-        _base[shape] = datagen.zipf255(SHAPES[shape][1], seed=60 + len(_base))
-    return _base[shape]
-
-
-# ---- calls and checks ------------------------------------------------------------------------------------------------------
-def psearch(torch, codec, enc, pattern, cap, counts=True, sub=None, **kw):
-    """one find_pattern call; host arrays (the guarded position buffer or None, totals, errs, counts or None)"""
-    buf = torch.full((LEAD + cap + TAIL,), GUARD64, dtype=torch.int64, device="cuda") if cap else None
-    _, totals, errs, cnt = codec.find_pattern(enc.stream, enc.length, enc.offsets, enc.nb, enc.sub if sub is None else sub,
-                                              enc.raw_size, enc.row_bs, pattern, max_positions=cap, block_counts=counts,
-                                              out=buf[LEAD:LEAD + cap] if cap else None, **kw)
-    return (buf.cpu().numpy() if cap else None, totals.cpu().numpy(), errs.cpu().numpy(), cnt.cpu().numpy() if counts else None)
-
-
-def rsearch(torch, codec, enc, pattern, delims, cap, max_len=0, counts=True, sub=None, **kw):
-    """one find_records call; host arrays (the guarded buffers of starts and lengths or None, totals, errs, counts or None)"""
-    pbuf = torch.full((LEAD + cap + TAIL,), GUARD64, dtype=torch.int64, device="cuda") if cap else None
-    lbuf = torch.full((LEAD + cap + TAIL,), GUARD32, dtype=torch.int32, device="cuda") if cap else None
-    out = (pbuf[LEAD:LEAD + cap], lbuf[LEAD:LEAD + cap]) if cap else None
-    _, _, totals, errs, cnt = codec.find_records(enc.stream, enc.length, enc.offsets, enc.nb, enc.sub if sub is None else sub,
-                                                 enc.raw_size, enc.row_bs, pattern, delims, max_records=cap, max_len=max_len,
-                                                 block_counts=counts, out=out, **kw)
-    return (pbuf.cpu().numpy() if cap else None, lbuf.cpu().numpy() if cap else None, totals.cpu().numpy(), errs.cpu().numpy(),
-            cnt.cpu().numpy() if counts else None)
-
-
-def same_arrays(a, b):
-    return all((x is None and y is None) or np.array_equal(x, y) for x, y in zip(a, b))
-
-
-def exact(torch, codec, enc, classes, must=(), must_not=(), room=7, what="", literal=None, model=None, **kw):
-    """all blocks served and everything equal to the model; `must` / `must_not`: starts the model is seen to hold / lack;
-    `literal`: the string whose find_pattern answer on the GPU is the same, word for word.  `model`: the classes the model
-    gets when the call gets something else (a literal with ignore_case)"""
-    model = classes if model is None else model
-    pos, counts, totals = find_classes_model(enc.data, model, enc.bs, enc.n)
-    total = int(totals[0])
-    assert 0 < total < enc.n, (what, "the planted input has", total, "matches")
-    found = set(pos.tolist())
-    assert found >= set(must) and not found & set(must_not), (what, sorted(set(must) - found), sorted(found & set(must_not)))
-    res = psearch(torch, codec, enc, classes, total + room, **kw)
-    assert not res[2].any(), (what, np.flatnonzero(res[2])[:8])
-    check(res, find_classes_model(enc.data, model, enc.bs, total + room), total + room, what)
-    if literal is not None:
-        assert same_arrays(res, psearch(torch, codec, enc, literal, total + room)), (what, "differs from find_pattern")
-    return total
-
-
-def exact_or_not_served(torch, codec, enc, classes, cap, sub=None, what=""):
-    """every block has status 0 or RW, and the answer is the model's for the blocks with status 0"""
-    res = psearch(torch, codec, enc, classes, cap, sub=sub)
-    errs = res[2]
-    assert set(errs.tolist()) <= {OK, RW}, what
-    check(res, find_classes_model(enc.data, classes, enc.bs, cap, served=errs == OK), cap, what)
-    return errs
-
-
-def records_exact_or_not_served(torch, codec, enc, classes, delims, cap, sub=None, max_len=0, what=""):
-    res = rsearch(torch, codec, enc, classes, delims, cap, max_len, sub=sub)
-    errs = res[3]
-    assert set(errs.tolist()) <= {OK, RW}, what
-    check_records(res, find_class_records_model(enc.data, classes, delims, enc.bs, cap, max_len, served=errs == OK), cap, what)
-    return errs
-
-
-def records_exact(torch, codec, enc, classes, delims=b"\n", must=(), must_not=(), room=7, max_len=0, what="", model=None, **kw):
-    model = classes if model is None else model
-    pos, lens, counts, totals = find_class_records_model(enc.data, model, delims, enc.bs, enc.n, max_len)
-    total = int(totals[0])
-    assert total > 0, (what, "the planted input has no matching record")
-    found = set(pos.tolist())
-    assert found >= set(must) and not found & set(must_not), (what, sorted(set(must) - found), sorted(found & set(must_not)))
-    res = rsearch(torch, codec, enc, classes, delims, total + room, max_len, **kw)
-    assert not res[3].any(), (what, np.flatnonzero(res[3])[:8])
-    check_records(res, find_class_records_model(enc.data, model, delims, enc.bs, total + room, max_len), total + room, what)
-    return pos, lens
-
-
-def pattern_of(length, seed):
-    """`length` bytes that zipf-like data does not hold by chance (for 5 bytes and more), without a period and without the
-    value 255, which zipf255 lacks: a block of all 256 values would need HUFGPU_RELAXED_TREE"""
-    return bytes(np.random.default_rng(seed).integers(128, 255, length).astype(np.uint8))
-
-
-def spellings(word, count, seed):
-    """`count` mixed-case spellings of a word of letters, all different from each other while there are enough"""
-    rng = np.random.default_rng(seed)
-    out = [word.lower(), word.upper()]
-    while len(out) < count:
-        out.append(bytes(c ^ (0x20 * int(rng.integers(0, 2))) for c in word))
-    return out[:count]
-
-
-def planted_each(data, strings, starts):
-    data = np.array(data, dtype=np.uint8)
-    for s, at in zip(strings, starts):
-        data = planted(data, s, [at])
-    return data
+# ---- checks ----------------------------------------------------------------------------------------------------------------
+exact = functools.partial(find_support.exact_positions, find_classes_model, find_support.as_is)
+exact_or_not_served = functools.partial(find_support.positions_exact_or_not_served, find_classes_model, find_support.as_is)
+records_exact = functools.partial(find_support.exact_records, find_class_records_model, find_support.as_is)
+records_exact_or_not_served = functools.partial(find_support.records_exact_or_not_served, find_class_records_model, find_support.as_is)
 
 
 # ---- case 1: classes of one value are the literal, at every seam and at the data's end ---------------------------------------
 @pytest.mark.parametrize("length", [2, 5, 33, 64])
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_classes_of_one_value_are_find_pattern(torch_mod, codec, shape, length):
-    bs, n, starts = SHAPES[shape]
-    pat = pattern_of(length, 100 + length)
+    bs, n, starts = FOUR_SHAPES[shape]
+    pat = pattern_below_255(length, 100 + length)
     classes = [bytes([v]) for v in pat]
     enc = encode(torch_mod, codec, planted(base_of(shape), pat, starts + [n - length]), bs)
     exact(torch_mod, codec, enc, classes, must=starts + [n - length], literal=pat, what=(shape, "ends with it", length))
@@ -177,9 +52,9 @@ def test_classes_of_one_value_are_find_pattern(torch_mod, codec, shape, length):
 
 # ---- case 2: ignore case -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("word", [b"ErRoR", b"TheQuickBrownFoxJumpsOverTheLazyDo"[:33]], ids=["5", "33"])
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_ignore_case(torch_mod, codec, shape, word):
-    bs, n, starts = SHAPES[shape]
+    bs, n, starts = FOUR_SHAPES[shape]
     assert word.isalpha()
     starts = starts + [n - len(word)]
     words = spellings(word, len(starts), len(word))
@@ -205,12 +80,12 @@ def fill_any(rng, classes, pool):
 
 @pytest.mark.parametrize("length", [2, 7, 64])
 @pytest.mark.parametrize("where", ["middle", "first"])
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_the_full_class_in_the_middle_and_in_the_first_place(torch_mod, codec, shape, where, length):
     """the first place: every start is a candidate - the dense first class"""
-    bs, n, starts = SHAPES[shape]
+    bs, n, starts = FOUR_SHAPES[shape]
     rng = np.random.default_rng(length)
-    classes = [bytes([v]) for v in pattern_of(length, 200 + length)]
+    classes = [bytes([v]) for v in pattern_below_255(length, 200 + length)]
     holes = [0] if where == "first" else ([1] if length == 2 else [length // 2, length // 2 + 1, length - 2])
     if where == "middle" and length == 2:
         classes = classes + classes[:1]                    # (a middle needs three positions)
@@ -229,8 +104,8 @@ def test_the_full_class_in_the_last_place(torch_mod, codec, length):
     """... matches at n - len and not at n - len + 1; and when the wildcard's byte is the first byte of the next block the
     match depends on that block being served"""
     torch = torch_mod
-    bs, n, starts = SHAPES["5x4099"]
-    lit = pattern_of(length - 1, 300 + length)
+    bs, n, starts = FOUR_SHAPES["5x4099"]
+    lit = pattern_below_255(length - 1, 300 + length)
     classes = [bytes([v]) for v in lit] + [ANY]
     seam = 2 * bs - (length - 1)                            # the literal bytes end block 1, the wildcard's byte opens block 2
     starts = [s for s in starts if abs(s - seam) > 64] + [seam]
@@ -250,7 +125,7 @@ def test_the_full_class_in_the_last_place(torch_mod, codec, length):
 @pytest.mark.parametrize("shape", ["5x4099", "300x64"])
 def test_one_position_is_find_bytes(torch_mod, codec, shape):
     torch = torch_mod
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     data = base_of(shape)
     enc = encode(torch, codec, data, bs)
     frequent = int(np.bincount(data).argmax())
@@ -271,7 +146,7 @@ def test_one_position_is_find_bytes(torch_mod, codec, shape):
 def test_sixty_four_wide_classes(torch_mod, codec, shape):
     """64 positions of [128 .. 255] over bytes below 128 with runs of 64, 65 and 200 bytes of 128 and above: 1, 2 and 137
     matches a run, each run across a tile or a block seam"""
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     rng = np.random.default_rng(11)
     data = base_of(shape) & 0x7F
     at = {"5x4099": [2048 - 30, 4099 - 64, 2 * 4099 + 2048 - 100], "300x64": [64 * 7 + 10, 64 * 255 + 1, 64 * 100 - 5],
@@ -280,7 +155,7 @@ def test_sixty_four_wide_classes(torch_mod, codec, shape):
         data[s:s + run] = rng.integers(128, 256, run)
     enc = encode(torch_mod, codec, data, bs)
     classes = [bytes(range(128, 256))] * 64
-    total = exact(torch_mod, codec, enc, classes, must=[at[0], at[1], at[1] + 1, at[2], at[2] + 136],
+    total, _ = exact(torch_mod, codec, enc, classes, must=[at[0], at[1], at[1] + 1, at[2], at[2] + 136],
                   must_not=[at[0] + 1, at[1] + 2, at[2] + 137], what=shape)
     assert total == 1 + 2 + 137
 
@@ -307,7 +182,7 @@ def test_one_symbol_blocks(torch_mod, codec):
 def test_one_symbol_and_ordinary_blocks_alternate(torch_mod, codec, bs):
     torch = torch_mod
     data = mixed_blocks(bs, 6, 26)
-    tail, head = pattern_of(6, 1), pattern_of(5, 2)
+    tail, head = pattern_below_255(6, 1), pattern_below_255(5, 2)
     out_of, into = b")" * 4 + tail, head + b")" * 3
     s_out, s_in = [bs - 4, 3 * bs - 4], [2 * bs - 5, 4 * bs - 5]
     data = planted(planted(data, out_of, s_out), into, s_in)
@@ -324,9 +199,6 @@ def test_one_symbol_and_ordinary_blocks_alternate(torch_mod, codec, bs):
 
 
 # ---- case 7: blocks that are not served ------------------------------------------------------------------------------------------
-def two_values(n, seed):
-    """two byte values have the codes 00 and 01: a 1 at an even payload bit leaves the tree"""
-    return (np.random.default_rng(seed).integers(0, 2, n) * 200 + 7).astype(np.uint8)
 
 
 @pytest.mark.parametrize("damage", ["a payload bit", "block_len"])
@@ -353,7 +225,7 @@ def test_a_block_that_is_not_served(torch_mod, codec, damage):
         # ONE record (no delimiter occurs): any block that is not served leaves its extent unknown
         res = rsearch(torch, codec, bad, classes, b"\n", 3)
         assert res[2].tolist() == [0, 0, 1, 0]
-        check_records(res, find_class_records_model(enc.data, classes, b"\n", bs, 3, served=res[3] == OK), 3, (damage, b))
+        check(res, find_class_records_model(enc.data, classes, b"\n", bs, 3, served=res[3] == OK), 3, (damage, b))
 
 
 @pytest.mark.parametrize("sub", ["zeros", "random"])
@@ -380,7 +252,7 @@ def test_sub_index_abuse(torch_mod, codec, sub):
 # ---- case 8: the caps ----------------------------------------------------------------------------------------------------------
 def test_caps(torch_mod, codec):
     torch = torch_mod
-    bs, n, starts = SHAPES["5x4099"]
+    bs, n, starts = FOUR_SHAPES["5x4099"]
     word = b"Warning"
     nl = [40, 1500, 2046, bs, 2 * bs + 2100, 2 * bs + 4090, 3 * bs + 3000]
     starts = starts + [starts[1] + 20, n - len(word)]      # (two matches in one record)
@@ -399,7 +271,7 @@ def test_caps(torch_mod, codec):
         for counts in (True, False):
             res = rsearch(torch, codec, enc, word, b"\n", cap, counts=counts, ignore_case=True)
             assert not res[3].any() and int(res[2][0]) == rtotal
-            check_records(res, find_class_records_model(data, classes, b"\n", bs, cap), cap, (cap, counts))
+            check(res, find_class_records_model(data, classes, b"\n", bs, cap), cap, (cap, counts))
     totals, errs = codec.count_records(enc.stream, enc.length, enc.offsets, enc.nb, enc.sub, n, bs, word, ignore_case=True)
     assert totals.cpu().tolist() == [rtotal, 0, 0, 0] and not errs.cpu().numpy().any()
     args = (enc.stream, enc.length, enc.offsets, enc.nb, enc.sub, n, bs)
@@ -428,7 +300,7 @@ def test_records_ignore_case_at_the_seams(torch_mod, codec):
     data = planted_each(with_delimiters(base, nl), spellings(word, len(starts), 6), starts)
     classes = GpuCodec.byte_classes(word, ignore_case=True)
     enc = encode(torch, codec, data, bs)
-    pos, lens = records_exact(torch, codec, enc, word, must=[0, 301, bs + 1, 3 * bs, 4 * bs + 1, 4 * bs + 201], model=classes,
+    pos, lens, _ = records_exact(torch, codec, enc, word, must=[0, 301, bs + 1, 3 * bs, 4 * bs + 1, 4 * bs + 201], model=classes,
                               ignore_case=True, what="no end")
     assert pos[-1] + lens[-1] == n and lens[0] == 31
     records_exact(torch, codec, enc, [NOT_NL] + [bytes([c, c ^ 0x20]) for c in word[1:]], must=[301, bs + 1], must_not=[2502],
@@ -442,14 +314,14 @@ def test_records_ignore_case_at_the_seams(torch_mod, codec):
     data[0] = NL
     data[1:6] = np.frombuffer(b"ERROr", np.uint8)
     enc = encode(torch, codec, data, bs)
-    pos, lens = records_exact(torch, codec, enc, word, must=[1, 4 * bs + 201], must_not=[0], model=classes, ignore_case=True, what="an end")
+    pos, lens, _ = records_exact(torch, codec, enc, word, must=[1, 4 * bs + 201], must_not=[0], model=classes, ignore_case=True, what="an end")
     assert pos[-1] + lens[-1] == n - 1
 
 
 @pytest.mark.parametrize("shape", ["300x64", "200x3"])
 def test_one_record_over_all_blocks(torch_mod, codec, shape):
     """a match in every tile; the empty delimiter set and a delimiter that never occurs both give ONE entry, (0, n)"""
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     base = base_without(n, 42)
     nb = (n + bs - 1) // bs
     two = [b"Qq", b"Zz"]
@@ -459,10 +331,10 @@ def test_one_record_over_all_blocks(torch_mod, codec, shape):
         res = rsearch(torch_mod, codec, enc, two, delims, 3)
         assert res[2].tolist() == [1, 1, 0, 0] and not res[3].any(), (delims, res[2])
         assert res[0][LEAD] == 0 and int(res[1].view(np.uint32)[LEAD]) == n, delims
-        check_records(res, find_class_records_model(data, two, delims, bs, 3), 3, delims)
+        check(res, find_class_records_model(data, two, delims, bs, 3), 3, delims)
         assert res[4].tolist() == [1] + [0] * (nb - 1)
     res = rsearch(torch_mod, codec, enc, [ANY, b"Zz"], b"", 3)                  # the full class with the empty delimiter set
-    check_records(res, find_class_records_model(data, [ANY, b"Zz"], b"", bs, 3), 3, "any")
+    check(res, find_class_records_model(data, [ANY, b"Zz"], b"", bs, 3), 3, "any")
 
 
 def test_grep_ignore_case(torch_mod, codec):
@@ -498,7 +370,7 @@ def test_calls_back_to_back(torch_mod, codec):
     more - without a synchronise in between: each gives its own model's answer, and the literal calls the same after a class
     call as before it"""
     torch = torch_mod
-    bs, n, starts = SHAPES["5x4099"]
+    bs, n, starts = FOUR_SHAPES["5x4099"]
     word = b"Segfault"
     nl = [40, 1500, 2046, bs, 2 * bs + 2100, 2 * bs + 4090, 3 * bs + 3000]
     data = planted_each(with_delimiters(base_without(n, 72), nl), spellings(word, len(starts), 5), starts)
@@ -541,7 +413,7 @@ def test_calls_back_to_back(torch_mod, codec):
     for (kind, key), (cap, pbuf, lbuf), r in zip(jobs, bufs, res):
         if "records" in kind:
             got = (pbuf.cpu().numpy(), lbuf.cpu().numpy(), r[2].cpu().numpy(), r[3].cpu().numpy(), r[4].cpu().numpy())
-            check_records(got, model(kind, cap), cap, kind)
+            check(got, model(kind, cap), cap, kind)
         else:
             got = (pbuf.cpu().numpy(), r[1].cpu().numpy(), r[2].cpu().numpy(), r[3].cpu().numpy())
             check(got, model(kind, cap), cap, kind)

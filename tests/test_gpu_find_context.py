@@ -13,104 +13,39 @@ import re
 import numpy as np
 import pytest
 
+import find_support
 from find_context_model import find_context_model
 from find_records_model import find_records_model
 from find_select_model import NO_UNKNOWN, find_select_model
+from find_support import (CHUNK, FOUR_SHAPES, GUARD8, GUARD32, GUARD64, LEAD, NL, OK, RW, SEAMS, TAIL, TILE, AnyOf, base_without, check,
+                          codec, context, damaged, encode, literal, pattern_below_255, payload_start, planted, runs_input, same_arrays,
+                          select, torch_mod, with_delimiters)
 from libhuffman_amd import datagen
-from libhuffman_amd.codec import GpuCodec
-from test_gpu_find import GUARD64, LEAD, OK, RW, TAIL, damaged, payload_start
-from test_gpu_find_classes import CHUNK, SHAPES, TILE, pattern_of, same_arrays
-from test_gpu_find_pattern import encode, planted
-from test_gpu_find_records import GUARD32, base_without, with_delimiters
-from test_gpu_find_records import check as check_records
-from test_gpu_find_select import SEAMS, check_select, runs_input, select
 
 pytestmark = pytest.mark.gpu
 
-AnyOf = GpuCodec.AnyOf
-NL = 10
-GUARD8 = 0xA5
 FAR = 2**32 - 1
 DISTANCES = [(0, 1), (1, 0), (2, 2), (0, 5), (7, 0), (3, 40), (FAR, FAR)]
 
 
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def codec(torch_mod):
-    c = GpuCodec(0)
-    yield c
-    c.close()
-
-
-# ---- the call and the checks -------------------------------------------------------------------------------------------------
-def context(torch, codec, enc, alts, delims, cap, max_len=0, invert=False, before=0, after=0, numbers=True, flags=True, counts=True,
-            sub=None):
-    """one hufgpu_find_records_context call; host arrays (the guarded buffers of starts, lengths, numbers and flags or None,
-    totals, errs, counts or None) in the order (starts, lengths, totals, errs, counts, numbers, flags)"""
-    classes, lens = GpuCodec.alt_classes(AnyOf(*alts))
-    pbuf = torch.full((LEAD + cap + TAIL,), GUARD64, dtype=torch.int64, device="cuda") if cap else None
-    lbuf = torch.full((LEAD + cap + TAIL,), GUARD32, dtype=torch.int32, device="cuda") if cap else None
-    nbuf = torch.full((LEAD + cap + TAIL,), GUARD64, dtype=torch.int64, device="cuda") if numbers else None
-    sbuf = torch.full((LEAD + cap + TAIL,), GUARD8, dtype=torch.uint8, device="cuda") if flags else None
-    totals = torch.empty(4, dtype=torch.int64, device="cuda")
-    errs = torch.empty(enc.nb, dtype=torch.int32, device="cuda")
-    cnt = torch.empty(enc.nb, dtype=torch.int64, device="cuda") if counts else None
-    sub = enc.sub if sub is None else sub
-    err = codec.lib.hufgpu_find_records_context(
-        codec._ctx, enc.stream.data_ptr(), enc.length, enc.offsets.data_ptr(), enc.nb, sub.data_ptr(), enc.raw_size, enc.row_bs,
-        GpuCodec.byte_set(delims), classes.tobytes(), lens.tobytes(), len(lens), 1 if invert else 0, before, after,
-        pbuf[LEAD:].data_ptr() if cap else None, lbuf[LEAD:].data_ptr() if cap else None, nbuf[LEAD:].data_ptr() if numbers else None,
-        sbuf[LEAD:].data_ptr() if flags else None, cap, max_len, cnt.data_ptr() if counts else None, totals.data_ptr(), errs.data_ptr(), 0,
-        codec._stream())
-    codec._check(err, "Failed to enqueue the search")
-    return (pbuf.cpu().numpy() if cap else None, lbuf.cpu().numpy() if cap else None, totals.cpu().numpy(), errs.cpu().numpy(),
-            cnt.cpu().numpy() if counts else None, nbuf.cpu().numpy() if numbers else None, sbuf.cpu().numpy() if flags else None)
-
-
-def check_context(res, want, cap, what=""):
-    """the call's host arrays against the model's (starts, lengths, counts, totals, numbers, flags): everything, and the guards"""
-    check_select(res[:6], want[:5], cap, what)
-    if res[6] is not None:
-        full = np.full(LEAD + cap + TAIL, GUARD8, np.uint8)
-        full[LEAD:LEAD + want[5].size] = want[5]
-        bad = np.flatnonzero(res[6] != full)
-        assert bad.size == 0, (what, "flags differ at", bad[:8] - LEAD, res[6][bad[:8]], full[bad[:8]])
-
-
-def exact(torch, codec, enc, alts, delims=b"\n", before=0, after=0, invert=False, room=5, max_len=0, what="", sub=None, all_served=True):
+# ---- the checks --------------------------------------------------------------------------------------------------------------
+def context_exact(torch, codec, enc, alts, delims=b"\n", before=0, after=0, invert=False, room=5, max_len=0, what="", sub=None, all_served=True):
     """the answer without outputs and with all four, each equal to the model's for the blocks with status 0; returns (the
     model's answer at a cap that holds every record, the statuses)"""
     kw = dict(invert=invert, before=before, after=after)
-    what = (what, before, after, invert)
-    probe = context(torch, codec, enc, alts, delims, 0, numbers=False, flags=False, sub=sub, **kw)
-    errs = probe[3]
-    assert set(errs.tolist()) <= {OK, RW} and (not all_served or not errs.any()), (what, errs)
-    served = errs == OK
-    full = find_context_model(enc.data, alts, delims, enc.bs, enc.n, max_len, served, **kw)
-    check_context(probe, find_context_model(enc.data, alts, delims, enc.bs, 0, max_len, served, **kw), 0, (what, "count"))
-    cap = int(full[3][0]) + room
-    res = context(torch, codec, enc, alts, delims, cap, max_len, sub=sub, **kw)
-    assert np.array_equal(res[3], errs), what
-    check_context(res, find_context_model(enc.data, alts, delims, enc.bs, cap, max_len, served, **kw), cap, what)
+    full, _, errs = find_support.exact_answer(lambda cap: context(torch, codec, enc, alts, delims, cap, max_len, sub=sub, **kw),
+                                       lambda cap, served: find_context_model(enc.data, alts, delims, enc.bs, cap, max_len, served, **kw),
+                                       enc.n, room=room, what=(what, before, after, invert), all_served=all_served,
+                                       probe=lambda: context(torch, codec, enc, alts, delims, 0, numbers=False, flags=False, sub=sub, **kw))
     return full, errs
 
 
-def literal(word):
-    return [bytes([v]) for v in word]
-
-
 # ---- 1: the identity ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_no_distance_and_no_flags_is_the_select_call(torch_mod, codec, shape):
     torch = torch_mod
-    bs, n, starts = SHAPES[shape]
-    words = [pattern_of(5, 401), pattern_of(2, 402)]
+    bs, n, starts = FOUR_SHAPES[shape]
+    words = [pattern_below_255(5, 401), pattern_below_255(2, 402)]
     data = with_delimiters(base_without(n, 181), [p - 1 for p in SEAMS[shape]] + [n - 1])
     for i, s in enumerate(SEAMS[shape]):                    # (every third seam's record holds neither word)
         data = planted(data, words[i % 2], [s + 2 + i % 3] if i % 3 and s + 10 < n else [])
@@ -124,22 +59,22 @@ def test_no_distance_and_no_flags_is_the_select_call(torch_mod, codec, shape):
                 assert got[6] is None and same_arrays(got[:6], older), (shape, invert, numbers, cap)
                 assert int(got[2][0]) > 0
     res = context(torch, codec, enc, alts, b"\n", n)        # no distance, but the flags: every reported record is selected
-    check_context(res, find_context_model(data, alts, b"\n", bs, n), n, shape)
+    check(res, find_context_model(data, alts, b"\n", bs, n), n, shape)
     total = int(res[2][0])
     assert total > 0 and res[6][LEAD:LEAD + total].all()
 
 
 # ---- 2: one selected record at every seam ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("ba", [(1, 1), (3, 3)], ids=["1-1", "3-3"])
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_a_window_across_every_seam(torch_mod, codec, shape, ba):
     """a record of four bytes that holds the word starts at every seam p of the shape, records of four bytes on both sides:
     the window crosses the edge of a lane's word, a tile, a chunk, a block and a scan group.  Three ways that rotate through
     the seams: plain; a second delimiter at p - 2 (an empty record just in front of the seam: it is counted, so the window
     reaches one record less far); one at p + 5 (an empty record just behind)"""
     torch = torch_mod
-    bs, n, _ = SHAPES[shape]
-    word = pattern_of(2, 410)
+    bs, n, _ = FOUR_SHAPES[shape]
+    word = pattern_below_255(2, 410)
     for rot in range(3):
         nl, at = [], []
         for k, p in enumerate(SEAMS[shape]):
@@ -153,7 +88,7 @@ def test_a_window_across_every_seam(torch_mod, codec, shape, ba):
                 at.append(p + 1)
         data = planted(with_delimiters(base_without(n, 182 + rot), nl), word, at)
         enc = encode(torch, codec, data, bs)
-        full, _ = exact(torch, codec, enc, [literal(word)], before=ba[0], after=ba[1], what=(shape, rot))
+        full, _ = context_exact(torch, codec, enc, [literal(word)], before=ba[0], after=ba[1], what=(shape, rot))
         sel = set(full[0][full[5] == 1].tolist())
         assert {a - 1 for a in at} <= sel and int(full[3][0]) > len(sel) > 0, (shape, rot)
         assert full[4].tolist() == [bytes(data[:s]).count(b"\n") for s in full[0].tolist()]
@@ -165,46 +100,46 @@ def test_context_three_tiles_away(torch_mod, codec, shape):
     """long records: the hit's neighbours start three tiles in front of it and end three tiles behind it, and no tile between
     holds a selected record"""
     torch = torch_mod
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     tile = min(bs or TILE, TILE)
     a0 = {"5x4099": 1000, "300x64": 250 * 64 + 9, "3chunks": CHUNK - 3 * TILE - 500}[shape]
     h0 = a0 + 3 * tile + 10
     b0 = h0 + 30
     b1 = b0 + 3 * tile + 20
-    word = pattern_of(5, 420)
+    word = pattern_below_255(5, 420)
     data = planted(with_delimiters(base_without(n, 186), [a0 - 1, h0 - 1, b0 - 1, b1, b1 + 50]), word, [h0 + 7])
     enc = encode(torch, codec, data, bs)
     for ba, want in (((1, 1), [a0, h0, b0]), ((1, 0), [a0, h0]), ((0, 1), [h0, b0]), ((0, 2), [h0, b0, b1 + 1]), ((2, 0), [0, a0, h0])):
-        full, _ = exact(torch, codec, enc, [literal(word)], before=ba[0], after=ba[1], what=shape)
+        full, _ = context_exact(torch, codec, enc, [literal(word)], before=ba[0], after=ba[1], what=shape)
         assert full[0].tolist() == want and full[5].tolist() == [int(s == h0) for s in want], (shape, ba)
 
 
 @pytest.mark.parametrize("shape", ["5x4099", "300x64", "3chunks"])
 def test_a_window_of_forty_records_over_several_tiles(torch_mod, codec, shape):
     torch = torch_mod
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     step = 7 if shape == "300x64" else 150                  # 40 records: 280 bytes of 64-byte tiles, 6 000 of 2 048-byte ones
-    word = pattern_of(3, 430)
+    word = pattern_below_255(3, 430)
     nl = np.arange(step - 1, n, step)
     hits = [step * 70 + 2, step * 100 + 2, n - step * 20 + 2 - n % step]
     data = planted(with_delimiters(base_without(n, 187), nl), word, hits)
     enc = encode(torch, codec, data, bs)
     for ba in ((40, 40), (3, 40), (40, 0)):
-        full, _ = exact(torch, codec, enc, [literal(word)], before=ba[0], after=ba[1], what=shape)
+        full, _ = context_exact(torch, codec, enc, [literal(word)], before=ba[0], after=ba[1], what=shape)
         assert int(full[3][0]) > 40 and int(full[5].sum()) == 3
 
 
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_one_record_over_all_blocks(torch_mod, codec, shape):
     torch = torch_mod
-    bs, n, _ = SHAPES[shape]
-    word = pattern_of(2, 440)
+    bs, n, _ = FOUR_SHAPES[shape]
+    word = pattern_below_255(2, 440)
     for plants in ([], [n - 2]):
         enc = encode(torch, codec, planted(base_without(n, 188), word, plants), bs)
         for delims in (b"", b"\n"):
             for ba in ((1, 1), (FAR, FAR)):
                 for invert in (False, True):
-                    full, _ = exact(torch, codec, enc, [literal(word)], delims, ba[0], ba[1], invert, what=(shape, len(plants)))
+                    full, _ = context_exact(torch, codec, enc, [literal(word)], delims, ba[0], ba[1], invert, what=(shape, len(plants)))
                     if bool(plants) != invert:
                         assert [x.tolist() for x in full[:2]] == [[0], [n]] and full[4].tolist() == [0] and full[5].tolist() == [1]
                     else:
@@ -213,9 +148,9 @@ def test_one_record_over_all_blocks(torch_mod, codec, shape):
 
 # ---- 4: dense random data ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("ba", DISTANCES, ids=lambda ba: "%d-%d" % ba if ba[0] < FAR else "all")
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", list(FOUR_SHAPES))
 def test_dense_random_data(torch_mod, codec, shape, ba):
-    bs, n, _ = SHAPES[shape]
+    bs, n, _ = FOUR_SHAPES[shape]
     rng = np.random.default_rng(178)
     letters = np.frombuffer(b"abc", np.uint8)
     data = rng.choice(np.frombuffer(b"abc\n", np.uint8), n, p=[0.31, 0.31, 0.31, 0.07]).astype(np.uint8)
@@ -226,7 +161,7 @@ def test_dense_random_data(torch_mod, codec, shape, ba):
         alts = [[bytes(rng.choice(letters, int(rng.integers(1, 3)), replace=False).astype(np.uint8)) for _ in range(int(rng.integers(3, 7)))]
                 for _ in range(int(rng.integers(1, 7)))]
         for invert in (False, True):
-            full, _ = exact(torch_mod, codec, enc, alts, before=ba[0], after=ba[1], invert=invert, what=(shape, trial, alts))
+            full, _ = context_exact(torch_mod, codec, enc, alts, before=ba[0], after=ba[1], invert=invert, what=(shape, trial, alts))
             sizes.append((int(full[3][0]), int(full[5].sum())))
             if ba == (FAR, FAR) and sizes[-1][1]:
                 assert np.array_equal(full[0], every)
@@ -238,20 +173,20 @@ def test_one_symbol_blocks_between_ordinary_ones(torch_mod, codec):
     """200 x 3: blocks of three delimiters - three empty records each, counted and not reported - and of a leaf that is in no
     class, between ordinary blocks"""
     torch = torch_mod
-    bs, n, _ = SHAPES["200x3"]
+    bs, n, _ = FOUR_SHAPES["200x3"]
     data = base_without(n, 189)
     data[data == 41] = 42
     data = with_delimiters(data, np.arange(4, n, 9))        # (the one-symbol blocks below overwrite what falls into them)
     for b in range(5, 190, 20):
         data[b * bs:(b + 1) * bs] = NL                      # three empty records
         data[(b + 7) * bs:(b + 8) * bs] = 41                # a leaf that is in no class
-    word = pattern_of(2, 450)
+    word = pattern_below_255(2, 450)
     data = planted(data, word, [3 * 40 + 1 + 60 * k for k in range(8)])     # blocks 40, 60, ...: none of those
     assert sum(np.unique(data[o:o + bs]).size == 1 for o in range(0, n - 2, bs)) >= 20
     enc = encode(torch, codec, data, bs)
     for ba in ((1, 1), (2, 2), (0, 5), (7, 0)):
         for invert in (False, True):
-            full, _ = exact(torch, codec, enc, [literal(word)], before=ba[0], after=ba[1], invert=invert, what="200x3")
+            full, _ = context_exact(torch, codec, enc, [literal(word)], before=ba[0], after=ba[1], invert=invert, what="200x3")
             assert full[4].tolist() == [bytes(data[:s]).count(b"\n") for s in full[0].tolist()]
             assert (full[1] > 0).all() and 0 < int(full[5].sum()) < full[5].size
     narrow = find_context_model(data, [literal(word)], b"\n", bs, n, before=2, after=2)
@@ -266,7 +201,7 @@ def test_a_block_that_is_not_served(torch_mod, codec, damage):
     torch = torch_mod
     enc, delim, alts = runs_input(torch, codec)
     bs, n = enc.bs, enc.n
-    whole = {ba: exact(torch, codec, enc, alts, delim, ba[0], ba[1], what="undamaged")[0] for ba in ((2, 2), (0, 5), (7, 0))}
+    whole = {ba: context_exact(torch, codec, enc, alts, delim, ba[0], ba[1], what="undamaged")[0] for ba in ((2, 2), (0, 5), (7, 0))}
     for b in range(5):
         if damage == "a payload bit":
             bad = damaged(enc, payload_start(enc, b) + (2 * 3000) // 8, 0x80 >> ((2 * 3000) % 8))
@@ -274,7 +209,7 @@ def test_a_block_that_is_not_served(torch_mod, codec, damage):
             bad = damaged(enc, int(enc.h_offs[b]), 0x01)
         for ba in whole:
             for invert in (False, True):
-                full, errs = exact(torch, codec, bad, alts, delim, ba[0], ba[1], invert, what=(damage, b), all_served=False)
+                full, errs = context_exact(torch, codec, bad, alts, delim, ba[0], ba[1], invert, what=(damage, b), all_served=False)
                 assert errs.tolist() == [RW if j == b else OK for j in range(5)], (damage, b, errs)
                 sel = select(torch, codec, bad, alts, delim, n, invert=invert)
                 k = int(sel[2][0])
@@ -293,26 +228,26 @@ def test_a_block_that_is_not_served(torch_mod, codec, damage):
 def test_sub_index_abuse(torch_mod, codec, sub):
     torch = torch_mod
     bs = 4096
-    word = pattern_of(6, 460)
+    word = pattern_below_255(6, 460)
     data = planted(base_without(5 * bs + 1500, 190), word, [100, bs - 3, 2 * bs + 2045, 5 * bs + 1494])
     data = with_delimiters(data, np.arange(37, data.size, 601))
     enc = encode(torch, codec, data, bs)
     rng = np.random.default_rng(134)
     other = torch.zeros_like(enc.sub) if sub == "zeros" else torch.from_numpy(rng.integers(-2**62, 2**62, enc.sub.numel())).cuda()
     alts = [literal(word), literal(word[:2])]
-    exact(torch, codec, enc, alts, before=2, after=2, what="own")
-    _, errs = exact(torch, codec, enc, alts, before=2, after=2, sub=other, max_len=9, what=sub, all_served=False)
+    context_exact(torch, codec, enc, alts, before=2, after=2, what="own")
+    _, errs = context_exact(torch, codec, enc, alts, before=2, after=2, sub=other, max_len=9, what=sub, all_served=False)
     assert sub == "random" or errs.all()
     bad = damaged(enc, int(enc.h_offs[1]), 0x01)
-    exact(torch, codec, bad, [literal(word)], before=3, after=1, sub=other, what=(sub, "and a damaged block"), all_served=False)
-    exact(torch, codec, bad, [literal(word)], before=FAR, after=FAR, what="a damaged block, every distance", all_served=False)
+    context_exact(torch, codec, bad, [literal(word)], before=3, after=1, sub=other, what=(sub, "and a damaged block"), all_served=False)
+    context_exact(torch, codec, bad, [literal(word)], before=FAR, after=FAR, what="a damaged block, every distance", all_served=False)
 
 
 # ---- 7: caps and lengths -----------------------------------------------------------------------------------------------------
 def test_caps_and_lengths(torch_mod, codec):
     torch = torch_mod
     bs, n = 4099, 5 * 4099
-    word = pattern_of(5, 470)
+    word = pattern_below_255(5, 470)
     nl = [99, 2047, bs - 1, bs + 3000, 2 * bs + 4096, 3 * bs + 10, 4 * bs + 4000]
     data = planted(with_delimiters(base_without(n, 191), nl), word, [2100, n - 5])
     enc = encode(torch, codec, data, bs)
@@ -328,11 +263,11 @@ def test_caps_and_lengths(torch_mod, codec):
                     for flags in (True, False):             # d_rec_sel without d_rec_no, and the reverse
                         res = context(torch, codec, enc, alts, b"\n", cap, numbers=numbers, flags=flags, counts=counts, **kw)
                         assert int(res[2][0]) == total and not res[3].any()
-                        check_context(res, find_context_model(data, alts, b"\n", bs, cap, **kw), cap, (invert, cap, counts, numbers, flags))
+                        check(res, find_context_model(data, alts, b"\n", bs, cap, **kw), cap, (invert, cap, counts, numbers, flags))
         for max_len in sorted({1, 0} | {m + d for m in lens for d in (-1, 0, 1)}):        # below, at and above every length
             for cap in (total, 2):
                 res = context(torch, codec, enc, alts, b"\n", cap, max_len, **kw)
-                check_context(res, find_context_model(data, alts, b"\n", bs, cap, max_len, **kw), cap, (invert, max_len, cap))
+                check(res, find_context_model(data, alts, b"\n", bs, cap, max_len, **kw), cap, (invert, max_len, cap))
                 if cap == total:
                     assert int(res[2][3]) == sum(l > max_len for l in lens) * bool(max_len)
 
@@ -342,8 +277,8 @@ def test_calls_back_to_back(torch_mod, codec):
     """context, select, find_records, context with other distances, ... without a synchronise in between: each gives its own
     model's answer, so the second mask and its scan are the call's own each time"""
     torch = torch_mod
-    bs, n, starts = SHAPES["5x4099"]
-    word = pattern_of(6, 480)
+    bs, n, starts = FOUR_SHAPES["5x4099"]
+    word = pattern_below_255(6, 480)
     nl = sorted(set(range(40, n, 333)) | {bs, 2 * bs + 2100})
     data = planted(with_delimiters(base_without(n, 192), nl), word, [s for s in starts if s + 6 < n])
     enc = encode(torch, codec, data, bs)
@@ -382,9 +317,9 @@ def test_calls_back_to_back(torch_mod, codec):
         if kw:
             if widens:
                 assert r[-1].data_ptr() == sbuf[LEAD:].data_ptr() and r[-1].dtype == torch.uint8
-            check_context(got, model(kw, cap), cap, kw)
+            check(got, model(kw, cap), cap, kw)
         else:
-            check_records(got[:5], model(kw, cap), cap, kw)
+            check(got[:5], model(kw, cap), cap, kw)
         if not numbers:
             assert (nbuf.cpu().numpy() == GUARD64).all()
         if not widens:

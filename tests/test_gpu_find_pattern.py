@@ -7,87 +7,22 @@ front and behind and is filled with the guard first: the words beyond totals[1] 
 bytes with the pattern planted at chosen offsets - the smallest shapes that reach each seam (lane, tile, chunk, block, the
 256-tile scan group, the end of the data); after planting the model's count is seen to be neither 0 nor everything.
 """
+import functools
+
 import numpy as np
 import pytest
 
 from find_model import find_model
 from find_pattern_model import find_pattern_model
+from find_support import (CHUNK, GUARD64, LEAD, OK, RW, TAIL, TILE, as_is, check, codec, damaged, encode, exact_positions, mixed_blocks,
+                          pattern_upto_255, payload_start, planted, positions_exact_or_not_served, psearch, torch_mod)
 from libhuffman_amd import datagen
-from test_gpu_find import GUARD64, LEAD, OK, RW, TAIL, check, damaged, payload_start
-from test_gpu_range_tiles import make, max_code_len
-from test_gpu_ranges import Enc
+from stream_support import make, max_code_len
 
 pytestmark = pytest.mark.gpu
 
-TILE, CHUNK = 2048, 65536
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def codec(torch_mod):
-    from libhuffman_amd.codec import GpuCodec
-    c = GpuCodec(0)
-    yield c
-    c.close()
-
-
-# ---- inputs --------------------------------------------------------------------------------------------------------------
-def pattern_of(length, seed):
-    """`length` bytes that zipf-like data does not hold by chance (for 5 bytes and more), without a period"""
-    return bytes(np.random.default_rng(seed).integers(128, 256, length).astype(np.uint8))
-
-
-def planted(data, pattern, starts):
-    """a copy of data with the pattern at every start (cut at the end of the data: such a one cannot match)"""
-    data = np.array(data, dtype=np.uint8)
-    pat = np.frombuffer(pattern, np.uint8)
-    for s in starts:
-        k = min(pat.size, data.size - s)
-        data[s:s + k] = pat[:k]
-    return data
-
-
-def encode(torch, codec, data, bs):
-    enc = Enc(torch, codec, data, bs, sub=True)
-    enc.codec, enc.raw_size, enc.row_bs = codec, enc.n, enc.bs
-    return enc
-
-
-def search(torch, codec, enc, pattern, cap, counts=True, sub=None):
-    """one call; host arrays (the guarded position buffer or None, totals, errs, counts or None) as test_gpu_find.find"""
-    buf = torch.full((LEAD + cap + TAIL,), GUARD64, dtype=torch.int64, device="cuda") if cap else None
-    _, totals, errs, cnt = codec.find_pattern(enc.stream, enc.length, enc.offsets, enc.nb, enc.sub if sub is None else sub,
-                                              enc.raw_size, enc.row_bs, pattern, max_positions=cap, block_counts=counts,
-                                              out=buf[LEAD:LEAD + cap] if cap else None)
-    return (buf.cpu().numpy() if cap else None, totals.cpu().numpy(), errs.cpu().numpy(), cnt.cpu().numpy() if counts else None)
-
-
-def exact(torch, codec, enc, pattern, must=(), must_not=(), room=7, what=""):
-    """all blocks served and everything equal to the model; `must` / `must_not`: starts the model is seen to hold / lack"""
-    pos, counts, totals = find_pattern_model(enc.data, pattern, enc.bs, enc.n)
-    total = int(totals[0])
-    assert 0 < total < enc.n, (what, "the planted input has", total, "matches")
-    found = set(pos.tolist())
-    assert found >= set(must) and not found & set(must_not), (what, sorted(set(must) - found), sorted(found & set(must_not)))
-    res = search(torch, codec, enc, pattern, total + room)
-    assert not res[2].any(), (what, np.flatnonzero(res[2])[:8])
-    check(res, find_pattern_model(enc.data, pattern, enc.bs, total + room), total + room, what)
-    return total
-
-
-def exact_or_not_served(torch, codec, enc, pattern, cap, sub=None, what=""):
-    """every block has status 0 or RW, and the answer is the model's for the blocks with status 0"""
-    res = search(torch, codec, enc, pattern, cap, sub=sub)
-    errs = res[2]
-    assert set(errs.tolist()) <= {OK, RW}, what
-    check(res, find_pattern_model(enc.data, pattern, enc.bs, cap, served=errs == OK), cap, what)
-    return errs
+exact = functools.partial(exact_positions, find_pattern_model, as_is)
+exact_or_not_served = functools.partial(positions_exact_or_not_served, find_pattern_model, as_is)
 
 
 # ---- case 1: lane, tile and block seams; the two ends of the data --------------------------------------------------------
@@ -95,7 +30,7 @@ def exact_or_not_served(torch, codec, enc, pattern, cap, sub=None, what=""):
 def test_seams_of_blocks_of_4099_bytes(torch_mod, codec, length):
     """five blocks of 4 099 bytes = tiles of 2 048, 2 048 and 3 symbols; no block start but the first is 32-aligned"""
     bs, n = 4099, 5 * 4099
-    pat = pattern_of(length, length)
+    pat = pattern_upto_255(length, length)
     # in the block: the data's first byte, the middle of a tile, the tile seam | a lane seam, through the 3-byte tile into
     # the next block | the same from the 3-byte tile's first byte, two tiles | from the block's last byte, the tile seam
     starts = [0, 1000, 2047, bs + 31, bs + 2 * TILE - 10, 2 * bs + 2000, 2 * bs + 4096, 3 * bs + 2047, 3 * bs + 4098]
@@ -113,7 +48,7 @@ def test_blocks_of_64_bytes(torch_mod, codec):
     bs, nb = 64, 300
     n = (nb - 1) * bs + 21
     base = datagen.zipf255(n, seed=22)
-    p64, p33 = pattern_of(64, 64), pattern_of(33, 33)
+    p64, p33 = pattern_upto_255(64, 64), pattern_upto_255(33, 33)
     # 64 bytes over two blocks, in exactly one block, over the blocks 255 | 256 of two scan groups
     s64 = [1, 5 * bs, 255 * bs + 1, 270 * bs + 63]
     # 33 bytes over every seam of three neighbouring blocks, and in front of the short last block
@@ -132,7 +67,7 @@ def test_blocks_of_3_bytes(torch_mod, codec):
     bs, nb = 3, 200
     n = nb * bs - 1
     base = datagen.zipf255(n, seed=23)
-    p64, p7 = pattern_of(64, 3), pattern_of(7, 7)
+    p64, p7 = pattern_upto_255(64, 3), pattern_upto_255(7, 7)
     s64 = [1, 100 * bs, n - 64]
     s7 = [70, 80 * bs + 2, 90 * bs + 1]
     data = planted(planted(base, p64, s64), p7, s7)
@@ -149,7 +84,7 @@ def test_blocks_of_3_bytes(torch_mod, codec):
 def test_chunk_seams_of_one_block(torch_mod, codec):
     n = 3 * CHUNK + 77
     base = datagen.zipf255(n, seed=24)
-    p64, p5 = pattern_of(64, 4), pattern_of(5, 5)
+    p64, p5 = pattern_upto_255(64, 4), pattern_upto_255(5, 5)
     s64 = [CHUNK - 10, 2 * CHUNK - 63, 2 * CHUNK + 3 * TILE - 1, n - 64]
     s5 = [CHUNK - 70, 2 * CHUNK - 68, CHUNK + TILE - 4, 3 * CHUNK - 1]
     data = planted(planted(base, p64, s64), p5, s5)
@@ -166,14 +101,14 @@ def test_a_run_of_one_value(torch_mod, codec):
     enc = encode(torch, codec, np.full(n, 41, np.uint8), bs)
     want = find_pattern_model(enc.data, b")" * 7, bs, n + 3)
     assert np.array_equal(want[0], np.arange(n - 6)) and want[1].tolist() == [bs] * 4 + [bs - 6]
-    res = search(torch, codec, enc, b")" * 7, n + 3)
+    res = psearch(torch, codec, enc, b")" * 7, n + 3)
     assert not res[2].any()
     check(res, want, n + 3, "seven")
     for pat in (b")" * 64, b")"):
-        res = search(torch, codec, enc, pat, n)
+        res = psearch(torch, codec, enc, pat, n)
         check(res, find_pattern_model(enc.data, pat, bs, n), n, len(pat))
     for pat in (b")" * 6 + b"(", b"(" + b")" * 6, b")))()))"):
-        res = search(torch, codec, enc, pat, 4)
+        res = psearch(torch, codec, enc, pat, 4)
         assert not res[2].any()
         check(res, find_pattern_model(enc.data, pat, bs, 4), 4, pat)
         assert res[1].tolist() == [0, 0, 0, 0]
@@ -189,19 +124,11 @@ def test_a_run_inside_ordinary_blocks(torch_mod, codec):
         exact(torch_mod, codec, enc, pat, what=len(pat))
 
 
-def mixed_blocks(bs, nblocks, seed):
-    """one-symbol blocks (41) and ordinary ones alternate"""
-    data = datagen.zipf255(nblocks * bs, seed=seed).copy()
-    for b in range(0, nblocks, 2):
-        data[b * bs:(b + 1) * bs] = 41
-    return data
-
-
 @pytest.mark.parametrize("bs", [4096, 4099])
 def test_one_symbol_and_ordinary_blocks_alternate(torch_mod, codec, bs):
     torch = torch_mod
     data = mixed_blocks(bs, 6, 26)
-    out_of, into = b")" * 4 + pattern_of(6, 1), pattern_of(5, 2) + b")" * 3
+    out_of, into = b")" * 4 + pattern_upto_255(6, 1), pattern_upto_255(5, 2) + b")" * 3
     s_out, s_in = [bs - 4, 3 * bs - 4], [2 * bs - 5, 4 * bs - 5]
     data = planted(planted(data, out_of, s_out), into, s_in)
     data[5 * bs:5 * bs + 2] = 41                           # the last run goes on into the ordinary block behind it
@@ -220,7 +147,7 @@ def test_abab(torch_mod, codec):
     bs, n = 4099, 5 * 4099                                 # an odd block size: the blocks start with a and with b in turn
     data = np.frombuffer((b"ab" * (n // 2 + 1))[:n], np.uint8).copy()
     enc = encode(torch_mod, codec, data, bs)
-    total = exact(torch_mod, codec, enc, b"abab", what="abab")
+    total, _ = exact(torch_mod, codec, enc, b"abab", what="abab")
     assert total == (n - 4) // 2 + 1
     exact(torch_mod, codec, enc, b"ba" * 32, what="ba x 32")
 
@@ -248,7 +175,7 @@ def test_one_byte_is_find_bytes(torch_mod, codec):
             buf = torch.full((LEAD + cap + TAIL,), GUARD64, dtype=torch.int64, device="cuda")
             _, totals, errs, cnt = codec.find_bytes(enc.stream, enc.length, enc.offsets, enc.nb, enc.sub, enc.n, bs, [v],
                                                     max_positions=cap, block_counts=True, out=buf[LEAD:LEAD + cap])
-            res = search(torch, codec, enc, bytes([v]), cap)
+            res = psearch(torch, codec, enc, bytes([v]), cap)
             assert np.array_equal(res[0], buf.cpu().numpy()) and np.array_equal(res[1], totals.cpu().numpy())
             assert np.array_equal(res[2], errs.cpu().numpy()) and np.array_equal(res[3], cnt.cpu().numpy())
             check(res, find_model(data, [v], bs, cap), cap, v)
@@ -258,14 +185,14 @@ def test_one_byte_is_find_bytes(torch_mod, codec):
 def test_caps(torch_mod, codec):
     torch = torch_mod
     bs, n = 4099, 5 * 4099
-    pat = pattern_of(5, 8)
+    pat = pattern_upto_255(5, 8)
     starts = [0, 2047, bs - 2, 2 * bs + 4096, 3 * bs + 4098, n - 5]
     enc = encode(torch, codec, planted(datagen.zipf255(n, seed=29), pat, starts), bs)
     total = int(find_pattern_model(enc.data, pat, bs)[2][0])
     assert total == len(starts)
     for cap in (0, total, total - 1, 1, total + 100):
         for counts in (True, False):
-            res = search(torch, codec, enc, pat, cap, counts=counts)        # (cap 0: d_pos is NULL)
+            res = psearch(torch, codec, enc, pat, cap, counts=counts)        # (cap 0: d_pos is NULL)
             assert not res[2].any() and int(res[1][0]) == total
             check(res, find_pattern_model(enc.data, pat, bs, cap), cap, (cap, counts))
     totals, errs = codec.count_pattern(enc.stream, enc.length, enc.offsets, enc.nb, enc.sub, n, bs, pat)
@@ -296,7 +223,7 @@ def test_a_block_that_is_not_served(torch_mod, codec, damage):
     served = np.array([True, False, True, True, True])
     for p, cap in ((pat, 40), (pat[:3], n), (pat[:2], n)):
         want = find_pattern_model(enc.data, p, bs, cap, served=served)
-        res = search(torch, codec, bad, p, cap)
+        res = psearch(torch, codec, bad, p, cap)
         assert res[2].tolist() == [OK, RW, OK, OK, OK] and int(res[1][2]) == 1, (damage, res[2], res[1])
         check(res, want, cap, (damage, len(p)))
     found = set(find_pattern_model(enc.data, pat, bs, 40, served=served)[0].tolist())
@@ -308,7 +235,7 @@ def test_a_block_that_is_not_served(torch_mod, codec, damage):
 def test_sub_index_abuse(torch_mod, codec, shape):
     torch = torch_mod
     bs = 4096
-    pat = pattern_of(6, 10)
+    pat = pattern_upto_255(6, 10)
     if shape == "zipf":
         data = planted(datagen.zipf255(5 * bs + 1500, seed=31), pat, [100, bs - 3, 2 * bs + 2045, 5 * bs + 1494])
     else:
@@ -333,7 +260,7 @@ def test_calls_back_to_back(torch_mod, codec):
     bits of an earlier call must not show in a later one"""
     torch = torch_mod
     bs, n = 4099, 5 * 4099
-    p64 = pattern_of(64, 11)
+    p64 = pattern_upto_255(64, 11)
     a = encode(torch, codec, planted(datagen.zipf255(n, seed=34), p64, [5, 2047, bs - 1, 3 * bs + 4090]), bs)
     b = encode(torch, codec, planted(datagen.zipf255(3 * 64 + 9, seed=35), p64[:33], [40, 100]), 64)
     v = int(np.bincount(a.data).argmax())

@@ -12,16 +12,10 @@ from find_any_model import find_any_model, find_any_records_model
 from find_classes_model import find_classes_model
 from find_pattern_model import find_pattern_model
 from find_select_model import find_select_model
-from libhuffman_amd.codec import GpuCodec
-from test_gpu_find import GUARD64, LEAD, OK, RW, TAIL, check, damaged, payload_start
-from test_gpu_find_classes import TILE, psearch
-from test_gpu_find_pattern import encode
-from test_gpu_find_records import GUARD32
-from test_gpu_find_select import check_select
+from find_support import OK, RW, TILE, AnyOf, check, codec, damaged, encode, numbered, payload_start, psearch, torch_mod
 
 pytestmark = pytest.mark.gpu
 
-AnyOf = GpuCodec.AnyOf
 A, B = 7, 207               # the data's two byte values (codes 00 and 01: a 1 at an even payload bit leaves the tree);
 DELIMS = bytes([B])         # the literal is a run of A, so B may end the records
 LENGTHS = [2, 4, 64]
@@ -35,20 +29,6 @@ SHAPES = {
     "5x4099": (4099, 5, 2, 2 * 3000, [b * 4099 + TILE - 32 for b in (0, 1, 3)] + [2 * TILE - 1, 4099 + 4098],
                [4 * 4099 + TILE - 1, 4 * 4099 + 2 * TILE - 1, 4 * 4099 - 1]),
 }
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
-
-
-@pytest.fixture(scope="module")
-def codec(torch_mod):
-    c = GpuCodec(0)
-    yield c
-    c.close()
 
 
 @pytest.fixture(scope="module")
@@ -89,17 +69,6 @@ def crossed(pos, length, n, bs):
     """the model's matches cross a seam of every kind that the layout has"""
     for kind, at in seams(n, bs).items():
         assert any(np.any((pos < s) & (pos + length > s)) for s in at), ("no match of", length, "bytes crosses a seam of kind", kind)
-
-
-def numbered(torch, codec, enc, pattern, cap):
-    """one find_records(line_numbers=True) call - the select call; host arrays in check_select's order"""
-    pbuf = torch.full((LEAD + cap + TAIL,), GUARD64, dtype=torch.int64, device="cuda")
-    lbuf = torch.full((LEAD + cap + TAIL,), GUARD32, dtype=torch.int32, device="cuda")
-    nbuf = torch.full((LEAD + cap + TAIL,), GUARD64, dtype=torch.int64, device="cuda")
-    out = tuple(buf[LEAD:LEAD + cap] for buf in (pbuf, lbuf, nbuf))
-    _, _, totals, errs, cnt, _ = codec.find_records(enc.stream, enc.length, enc.offsets, enc.nb, enc.sub, enc.raw_size, enc.row_bs,
-                                                    pattern, DELIMS, max_records=cap, block_counts=True, out=out, line_numbers=True)
-    return (pbuf.cpu().numpy(), lbuf.cpu().numpy(), totals.cpu().numpy(), errs.cpu().numpy(), cnt.cpu().numpy(), nbuf.cpu().numpy())
 
 
 @pytest.mark.parametrize("length", LENGTHS)
@@ -149,8 +118,8 @@ def test_one_literal_through_every_route(torch_mod, codec, inputs, shape, damage
     check(res, find_any_model(enc.data, two, bs, cap2, served=served), cap2, (what, "two alternatives"))
 
     rcap = recs + 5
-    res = numbered(torch, codec, enc, lit, rcap)
+    res = numbered(torch, codec, enc, lit, DELIMS, rcap)
     assert np.array_equal(res[3], status), (what, "records")
     want = find_select_model(enc.data, [lit], DELIMS, bs, rcap, served=served)
     assert all(np.array_equal(x, y) for x, y in zip(want[:4], find_any_records_model(enc.data, [lit], DELIMS, bs, rcap, served=served))), what
-    check_select(res, want, rcap, (what, "records"))
+    check(res, want, rcap, (what, "records"))

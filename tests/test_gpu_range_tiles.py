@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from libhuffman_amd import datagen
-from test_gpu_ranges import GUARD, Enc, check_all_good, dev, slots_for, touched
+from stream_support import GUARD, Enc, dev, make, max_code_len
+from test_gpu_ranges import check_all_good, slots_for, touched
 
 pytestmark = pytest.mark.gpu
 
@@ -34,58 +35,6 @@ def codec(torch_mod):
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------
-def by_counts(n, bs, counts, seed):
-    """every block a permutation of the same multiset: value v counts[v] times (cut for a short last block)"""
-    rng = np.random.default_rng(seed)
-    block = np.repeat(np.arange(len(counts), dtype=np.uint8), counts)
-    assert block.size == (bs or n), (block.size, bs, n)
-    parts = [rng.permutation(block) for _ in range(0, n, block.size)]
-    return np.concatenate(parts)[:n]
-
-
-def halving(size):
-    """counts size/2, size/4, ..., 1, 1: code lengths 2 .. log2(size) + 1 (the root's bit included)"""
-    c = [size >> (k + 1) for k in range(size.bit_length() - 1)]
-    return c + [1]
-
-
-def fibonacci(size):
-    """Fibonacci counts (the deepest trees a block of `size` bytes can have), the most frequent value takes the rest"""
-    f = [1, 1]
-    while sum(f) + f[-1] + f[-2] <= size // 2:
-        f.append(f[-1] + f[-2])
-    return f + [size - sum(f)]
-
-
-def make(kind, n, bs):
-    if kind == "zipf255":
-        return datagen.zipf255(n, seed=3)
-    if kind == "two":                                   # two byte values: about one bit a symbol
-        return (np.random.default_rng(5).integers(0, 2, n) * 200 + 7).astype(np.uint8)
-    if kind == "l2":                                    # codes of 13 bits and more: the second-level table
-        return by_counts(n, bs, halving(bs) if bs else halving_for(n), 7)
-    if kind == "long":                                  # codes beyond 18 bits: the binary search over the leaves
-        return by_counts(n, bs, fibonacci(bs) if bs else fibonacci(n), 8)
-    if kind == "uniform256":
-        return datagen.uniform256(n, seed=1)
-    if kind == "const41":
-        return datagen.const_bytes(n)
-    raise ValueError(kind)
-
-
-def halving_for(n):
-    """halving counts for a block of any size: powers of two from 2^14 down, the most frequent value takes the rest"""
-    c = [1 << k for k in range(14, -1, -1)]
-    return [n - sum(c)] + c
-
-
-def max_code_len(enc):
-    """the longest claimed code length of the sub-index (its last nblocks x 256 bytes are the lengths by byte value)"""
-    b = enc.sub.cpu().numpy().view(np.uint8)
-    nbytes = enc.codec.sub_index_bytes(enc.n, enc.bs)
-    return int(b[nbytes - 256 * enc.nb:nbytes].max())
-
-
 def encode(torch, codec, kind, n, bs):
     enc = Enc(torch, codec, make(kind, n, bs), bs, sub=True)
     enc.codec, enc.kind = codec, kind

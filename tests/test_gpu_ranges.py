@@ -13,10 +13,10 @@ import pytest
 
 import sub_index_ref as sref
 from libhuffman_amd import datagen
+from stream_support import GUARD, Enc, dev
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0xA5
 HUFE_OK, HUFE_MEMORY, HUFE_OVERFLOW = 0, 1, 5
 TREE_STRICT, TREE_MAX = 1024, 1025
 
@@ -34,37 +34,6 @@ def codec(torch_mod):
     c = GpuCodec(0)
     yield c
     c.close()
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).cuda()
-
-
-class Enc:
-    """an encoded input and what the tests know about it: P = where each block's bytes start in the raw data"""
-
-    def __init__(self, torch, codec, data, bs, sub=False, stream=None, offsets=None, block_lens=None):
-        self.data, self.bs, self.n = data, bs, int(data.size)
-        self.sub = None
-        if stream is None:
-            self.sub = codec.new_sub_index(self.n, bs) if sub else None
-            stream, offsets, _ = codec.encode(dev(torch, data), bs, sub_index=self.sub)
-            nb = codec.block_count(self.n, bs)
-            block_lens = [min(bs or self.n, self.n - b * (bs or self.n)) for b in range(nb)]
-        self.stream, self.offsets = stream, offsets
-        self.length = int(stream.numel())
-        self.nb = len(block_lens)
-        self.P = np.concatenate([[0], np.cumsum(block_lens)]).astype(np.int64)
-        self.h_offs = offsets.cpu().numpy().astype(np.int64)
-
-    def with_stream(self, stream):
-        other = object.__new__(Enc)
-        other.__dict__.update(self.__dict__)
-        other.stream = stream
-        return other
-
-    def sub_args(self):
-        return {} if self.sub is None else dict(sub_index=self.sub, raw_size=self.n, blocksize=self.bs)
 
 
 def slots_for(ranges, n, gaps=(13, 0, 7, 1, 16, 3), lead=5, shrink=None):

@@ -16,26 +16,15 @@ The tool asserts that (i) returns the same records as (ii) and that (i) takes no
 
 Every workload runs in a process of its own under `timeout -k 10`; the first one that fails ends the run.
 """
-import argparse
-import os
 import statistics
-import subprocess
-import sys
 import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from libhuffman_amd import datagen  # noqa: E402
-from libhuffman_amd.codec import GpuCodec  # noqa: E402
+from find_timing import GpuCodec, Workload, alternate, fmt, main
 
-WORKLOADS = [("logtext, blocks of 1 MiB", "logtext", 1 << 20), ("zipf255, blocks of 64 KiB", "zipf255", 65536)]
-STEP_SECONDS = 420
-
-
-def fmt(ts):
-    return f"{statistics.median(ts) * 1e3:8.3f} ms [{min(ts) * 1e3:.3f}, {max(ts) * 1e3:.3f}]"
+HEADER = ("{mib} MiB, delimiter newline, word bytes [A-Za-z0-9_], caps = the exact counts, "
+          "median of {runs} warm runs [min, max], the calls alternating in one process per workload")
 
 
 def among(sorted_pos, q):
@@ -47,25 +36,10 @@ def among(sorted_pos, q):
 
 
 def one_workload(k, runs, mib):
-    what, kind, bs = WORKLOADS[k]
-    codec = GpuCodec(0)
-    n = mib << 20
-    if kind == "logtext":
-        tile = min(n, 16 << 20)
-        page = datagen.logtext(tile)
-        data = torch.from_numpy(page).cuda().repeat(n // tile)
-        frequent, rare = b"ERROR", bytes(page[11:23])       # 12:MM:SS.mmm of the first line
-    else:
-        data = codec.fill(torch.empty(n, dtype=torch.uint8, device="cuda"), kind)
-        hist = torch.bincount(data[:1 << 24].int(), minlength=256)
-        hist[10] = 0                                        # (a pattern holds no delimiter)
-        frequent = bytes([int(hist.argmax())]) * 5
-        rare = bytes(11 if v == 10 else v for v in data[1000:1004].cpu().tolist())
-    sub = codec.new_sub_index(n, bs)
-    stream, offs, length = codec.encode(data, bs, sub_index=sub)
-    nb = codec.block_count(n, bs)
-    del data
-    args = (stream, length, offs, nb, sub, n, bs)
+    w = Workload(k, mib)
+    what, codec, n = w.what, w.codec, w.n
+    frequent, rare = w.frequent(delimiter=10), w.rare()
+    args = w.encode()
     not_word = bytes(v for v in range(256) if v not in GpuCodec.WORD_BYTES)
     bounds = {}
     for name, values in (("word", not_word), ("whole_line", b"\n")):
@@ -119,11 +93,7 @@ def one_workload(k, runs, mib):
             assert int(errs.abs().max()) == 0 and t == [cap, cap, 0, 0] and want.numel() == cap, (t, cap, want.numel())
             assert torch.equal(pos, want) and torch.equal(lens, want_lens)
             del want, want_lens, pos, lens
-            ti, ty, ts = [], [], []
-            for _ in range(runs):
-                for acc, f in ((ti, lambda: anchored()[0]), (ty, lambda: recipe()[0]), (ts, plain)):
-                    torch.cuda.synchronize()
-                    acc.append(f())
+            ti, ty, ts = alternate(runs, lambda: anchored()[0], lambda: recipe()[0], plain)
             mi, my, ms = (statistics.median(x) for x in (ti, ty, ts))
             print(f"{what:26s} {pname:18s} {anchor:10s} {pcap:9d} starts {bcap:10d} boundary bytes {mcap:9d} records with the pattern "
                   f"{cap:9d} selected\n"
@@ -134,37 +104,5 @@ def one_workload(k, runs, mib):
     codec.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--mib", type=int, default=1024)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--workload", type=int, default=-1, help="run this workload only, in this process")
-    a = ap.parse_args()
-    if a.workload >= 0:
-        one_workload(a.workload, a.runs, a.mib)
-        return
-    lines = [f"time_find_anchors.py: {a.mib} MiB, delimiter newline, word bytes [A-Za-z0-9_], caps = the exact counts, median of "
-             f"{a.runs} warm runs [min, max], the calls alternating in one process per workload"]
-    print(lines[0], flush=True)
-    ok = True
-    for k in range(len(WORKLOADS)):
-        p = subprocess.run(["timeout", "-k", "10", str(STEP_SECONDS), sys.executable, os.path.abspath(__file__), "--workload", str(k),
-                            "--runs", str(a.runs), "--mib", str(a.mib)], stdout=subprocess.PIPE, text=True)
-        sys.stdout.write(p.stdout)
-        sys.stdout.flush()
-        lines += p.stdout.splitlines()
-        if p.returncode != 0:
-            lines.append(f"workload {k} ended with status {p.returncode}: nothing further is run")
-            print(lines[-1], flush=True)
-            ok = False
-            break
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    sys.exit(0 if ok else 1)
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, HEADER, one_workload)

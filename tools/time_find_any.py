@@ -20,42 +20,27 @@ and that the one call takes less time than the K calls.
 
 Every workload runs in a process of its own under `timeout -k 10`; the first one that fails ends the run.
 """
-import argparse
-import os
 import statistics
-import subprocess
-import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from libhuffman_amd import datagen  # noqa: E402
-from libhuffman_amd.codec import GpuCodec  # noqa: E402
+from find_timing import GpuCodec, Workload, alternate, fmt, main
 
-WORKLOADS = [("logtext, blocks of 1 MiB", "logtext", 1 << 20), ("zipf255, blocks of 64 KiB", "zipf255", 65536)]
-STEP_SECONDS = 420
 LOG_WORDS = [b"ERROR", b"WARN", b"retrying", b"DEBUG", b"heartbeat", b"flushed", b"cache miss", b"status=5"]
 ZIPF_LENGTHS = [5, 3, 8, 4, 6, 7, 5, 4]
-
-
-def fmt(ts):
-    return f"{statistics.median(ts) * 1e3:8.3f} ms [{min(ts) * 1e3:.3f}, {max(ts) * 1e3:.3f}]"
+HEADER = ("{mib} MiB, caps = the exact counts, "
+          "median of {runs} warm runs [min, max], from the first enqueue to one synchronize, the rows alternating in one process per workload")
 
 
 def one_workload(k, runs, mib):
-    what, kind, bs = WORKLOADS[k]
-    codec = GpuCodec(0)
-    n = mib << 20
+    load = Workload(k, mib)
+    what, kind, codec = load.what, load.kind, load.codec
     if kind == "logtext":
-        tile = min(n, 16 << 20)
-        data = torch.from_numpy(datagen.logtext(tile)).cuda().repeat(n // tile)
         words = LOG_WORDS
     else:
-        data = codec.fill(torch.empty(n, dtype=torch.uint8, device="cuda"), kind)
-        top = torch.bincount(data[:1 << 24].int(), minlength=256).argsort(descending=True)[:4].tolist()
+        top = load.histogram().argsort(descending=True)[:4].tolist()
         rng = np.random.default_rng(38)
         words = [bytes([top[0]] * 5)]
         while len(words) < 8:
@@ -63,11 +48,7 @@ def one_workload(k, runs, mib):
             if w not in words:
                 words.append(w)
     assert sum(len(w) for w in words) <= 64
-    sub = codec.new_sub_index(n, bs)
-    stream, offs, length = codec.encode(data, bs, sub_index=sub)
-    nb = codec.block_count(n, bs)
-    del data
-    args = (stream, length, offs, nb, sub, n, bs)
+    args = load.encode()
 
     rows = []                                               # (name, K, the patterns of one timing)
     for K in (3, 8):
@@ -100,11 +81,7 @@ def one_workload(k, runs, mib):
         assert one.numel() == union.numel() and torch.equal(one, union), f"the one call and the union of the {K} class calls differ"
     del answers
 
-    times = {job[0]: [] for job in jobs}
-    for _ in range(runs):
-        for job in jobs:
-            torch.cuda.synchronize()
-            times[job[0]].append(timed(job)[0])
+    times = dict(zip([job[0] for job in jobs], alternate(runs, *[lambda job=job: timed(job)[0] for job in jobs])))
     for name, K, pats, caps, outs in jobs:
         m, base = statistics.median(times[name]), statistics.median(times[f"longest of {K} alone"])
         longest = max(len(w) for w in words[:K])
@@ -118,37 +95,5 @@ def one_workload(k, runs, mib):
     codec.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--mib", type=int, default=1024)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--workload", type=int, default=-1, help="run this workload only, in this process")
-    a = ap.parse_args()
-    if a.workload >= 0:
-        one_workload(a.workload, a.runs, a.mib)
-        return
-    lines = [f"time_find_any.py: {a.mib} MiB, caps = the exact counts, median of {a.runs} warm runs [min, max], from the first "
-             "enqueue to one synchronize, the rows alternating in one process per workload"]
-    print(lines[0], flush=True)
-    ok = True
-    for k in range(len(WORKLOADS)):
-        p = subprocess.run(["timeout", "-k", "10", str(STEP_SECONDS), sys.executable, os.path.abspath(__file__), "--workload", str(k),
-                            "--runs", str(a.runs), "--mib", str(a.mib)], stdout=subprocess.PIPE, text=True)
-        sys.stdout.write(p.stdout)
-        sys.stdout.flush()
-        lines += p.stdout.splitlines()
-        if p.returncode != 0:
-            lines.append(f"workload {k} ended with status {p.returncode}: nothing further is run")
-            print(lines[-1], flush=True)
-            ok = False
-            break
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    sys.exit(0 if ok else 1)
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, HEADER, one_workload)

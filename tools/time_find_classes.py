@@ -23,39 +23,25 @@ calls find together what the one class call finds, and that the one class call t
 
 Every workload runs in a process of its own under `timeout -k 10`; the first one that fails ends the run.
 """
-import argparse
 import itertools
-import os
 import statistics
-import subprocess
-import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from libhuffman_amd import datagen  # noqa: E402
-from libhuffman_amd.codec import GpuCodec  # noqa: E402
+from find_timing import GpuCodec, Workload, alternate, fmt, main
 
-WORKLOADS = [("logtext, blocks of 1 MiB", "logtext", 1 << 20), ("zipf255, blocks of 64 KiB", "zipf255", 65536)]
-STEP_SECONDS = 420
 HEX = b"0123456789abcdef"
-
-
-def fmt(ts):
-    return f"{statistics.median(ts) * 1e3:8.3f} ms [{min(ts) * 1e3:.3f}, {max(ts) * 1e3:.3f}]"
+HEADER = ("{mib} MiB, caps = the exact counts, "
+          "median of {runs} warm runs [min, max], from the first enqueue to one synchronize, the rows alternating in one process per workload")
 
 
 def one_workload(k, runs, mib):
-    what, kind, bs = WORKLOADS[k]
-    codec = GpuCodec(0)
-    n = mib << 20
+    w = Workload(k, mib)
+    what, kind, codec, n, bs, data = w.what, w.kind, w.codec, w.n, w.bs, w.data
     rows = []                                               # (name, the patterns of one timing, ignore_case)
     if kind == "logtext":
-        tile = min(n, 16 << 20)
-        data = torch.from_numpy(datagen.logtext(tile)).cuda().repeat(n // tile)
         key = b"req-1a2b3c4d-" + bytes(np.random.default_rng(36).integers(128, 255, 23).astype(np.uint8))
         assert len(key) == 36
         places = [n // 2 + 12345] + [(j * (n // bs // 5) + 1) * bs - d for j, d in zip(range(1, 5), (1, 18, 35, 7))]
@@ -71,16 +57,11 @@ def one_workload(k, runs, mib):
                 ("first full .RROR", [[GpuCodec.ANY] + [bytes([c]) for c in b"RROR"]], False),
                 ("32 literals of error", spellings, False)]
     else:
-        data = codec.fill(torch.empty(n, dtype=torch.uint8, device="cuda"), kind)
-        hist = torch.bincount(data[:1 << 24].int(), minlength=256)
-        frequent = bytes([int(hist.argmax())]) * 5
+        frequent = w.frequent()
         rows = [("literal, 5 bytes", [frequent], False), ("one value, 5 bytes", [[bytes([c]) for c in frequent]], False),
                 ("wide, 5 x [64..191]", [[bytes(range(64, 192))] * 5], False)]
-    sub = codec.new_sub_index(n, bs)
-    stream, offs, length = codec.encode(data, bs, sub_index=sub)
-    nb = codec.block_count(n, bs)
     del data
-    args = (stream, length, offs, nb, sub, n, bs)
+    args = w.encode()
 
     jobs = []
     for name, pats, ic in rows:
@@ -110,11 +91,7 @@ def one_workload(k, runs, mib):
         assert answers["hex key, 36 bytes"][0] == 5
     del answers, lit, one
 
-    times = {job[0]: [] for job in jobs}
-    for _ in range(runs):
-        for job in jobs:
-            torch.cuda.synchronize()
-            times[job[0]].append(timed(job)[0])
+    times = dict(zip([job[0] for job in jobs], alternate(runs, *[lambda job=job: timed(job)[0] for job in jobs])))
     base = statistics.median(times[rows[0][0]])
     for name, pats, ic, caps, outs in jobs:
         m = statistics.median(times[name])
@@ -127,37 +104,5 @@ def one_workload(k, runs, mib):
     codec.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--mib", type=int, default=1024)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--workload", type=int, default=-1, help="run this workload only, in this process")
-    a = ap.parse_args()
-    if a.workload >= 0:
-        one_workload(a.workload, a.runs, a.mib)
-        return
-    lines = [f"time_find_classes.py: {a.mib} MiB, caps = the exact counts, median of {a.runs} warm runs [min, max], from the first "
-             "enqueue to one synchronize, the rows alternating in one process per workload"]
-    print(lines[0], flush=True)
-    ok = True
-    for k in range(len(WORKLOADS)):
-        p = subprocess.run(["timeout", "-k", "10", str(STEP_SECONDS), sys.executable, os.path.abspath(__file__), "--workload", str(k),
-                            "--runs", str(a.runs), "--mib", str(a.mib)], stdout=subprocess.PIPE, text=True)
-        sys.stdout.write(p.stdout)
-        sys.stdout.flush()
-        lines += p.stdout.splitlines()
-        if p.returncode != 0:
-            lines.append(f"workload {k} ended with status {p.returncode}: nothing further is run")
-            print(lines[-1], flush=True)
-            ok = False
-            break
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    sys.exit(0 if ok else 1)
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, HEADER, one_workload)

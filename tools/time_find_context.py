@@ -17,49 +17,23 @@ than (ii) on any row.
 
 Every workload runs in a process of its own under `timeout -k 10`; the first one that fails ends the run.
 """
-import argparse
-import os
 import statistics
-import subprocess
-import sys
 import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from libhuffman_amd import datagen  # noqa: E402
-from libhuffman_amd.codec import GpuCodec  # noqa: E402
+from find_timing import GpuCodec, Workload, alternate, fmt, main
 
-WORKLOADS = [("logtext, blocks of 1 MiB", "logtext", 1 << 20), ("zipf255, blocks of 64 KiB", "zipf255", 65536)]
 CONTEXTS = (2, 20)
-STEP_SECONDS = 420
-
-
-def fmt(ts):
-    return f"{statistics.median(ts) * 1e3:8.3f} ms [{min(ts) * 1e3:.3f}, {max(ts) * 1e3:.3f}]"
+HEADER = ("{mib} MiB, delimiter newline, caps = the exact counts, "
+          "median of {runs} warm runs [min, max], the calls alternating in one process per workload")
 
 
 def one_workload(k, runs, mib):
-    what, kind, bs = WORKLOADS[k]
-    codec = GpuCodec(0)
-    n = mib << 20
-    if kind == "logtext":
-        tile = min(n, 16 << 20)
-        page = datagen.logtext(tile)
-        data = torch.from_numpy(page).cuda().repeat(n // tile)
-        frequent, rare = b"ERROR", bytes(page[11:23])       # 12:MM:SS.mmm of the first line
-    else:
-        data = codec.fill(torch.empty(n, dtype=torch.uint8, device="cuda"), kind)
-        hist = torch.bincount(data[:1 << 24].int(), minlength=256)
-        hist[10] = 0                                        # (a pattern holds no delimiter)
-        frequent = bytes([int(hist.argmax())]) * 5
-        rare = bytes(11 if v == 10 else v for v in data[1000:1004].cpu().tolist())
-    sub = codec.new_sub_index(n, bs)
-    stream, offs, length = codec.encode(data, bs, sub_index=sub)
-    nb = codec.block_count(n, bs)
-    del data
-    args = (stream, length, offs, nb, sub, n, bs)
+    w = Workload(k, mib)
+    what, codec, n = w.what, w.codec, w.n
+    frequent, rare = w.frequent(delimiter=10), w.rare()
+    args = w.encode()
     nl_cap = int(codec.count_bytes(*args, b"\n")[0][0])
     nl_pos = torch.empty(nl_cap, dtype=torch.int64, device="cuda")
     zero, end = torch.zeros(1, dtype=torch.int64, device="cuda"), torch.full((1,), n, dtype=torch.int64, device="cuda")
@@ -112,11 +86,7 @@ def one_workload(k, runs, mib):
             assert torch.equal(pos, want) and torch.equal(lens.long(), want_lens)
             assert torch.equal(numbers, want_no) and torch.equal(flags.bool(), want_flags) and int(flags.sum()) == mcap
             del want, want_lens, want_no, want_flags, pos, lens, numbers, flags
-            ti, ty, ts = [], [], []
-            for _ in range(runs):
-                for acc, f in ((ti, lambda: context()[0]), (ty, lambda: recipe()[0]), (ts, select)):
-                    torch.cuda.synchronize()
-                    acc.append(f())
+            ti, ty, ts = alternate(runs, lambda: context()[0], lambda: recipe()[0], select)
             mi, my, ms = (statistics.median(x) for x in (ti, ty, ts))
             print(f"{what:26s} {name:18s} context {c:2d} {nl_cap:9d} newlines {mcap:9d} matching {cap:9d} reported records\n"
                   f"    (i)   context, numbers, flags   {fmt(ti)}\n"
@@ -126,37 +96,5 @@ def one_workload(k, runs, mib):
     codec.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--mib", type=int, default=1024)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--workload", type=int, default=-1, help="run this workload only, in this process")
-    a = ap.parse_args()
-    if a.workload >= 0:
-        one_workload(a.workload, a.runs, a.mib)
-        return
-    lines = [f"time_find_context.py: {a.mib} MiB, delimiter newline, caps = the exact counts, median of {a.runs} warm runs "
-             "[min, max], the calls alternating in one process per workload"]
-    print(lines[0], flush=True)
-    ok = True
-    for k in range(len(WORKLOADS)):
-        p = subprocess.run(["timeout", "-k", "10", str(STEP_SECONDS), sys.executable, os.path.abspath(__file__), "--workload", str(k),
-                            "--runs", str(a.runs), "--mib", str(a.mib)], stdout=subprocess.PIPE, text=True)
-        sys.stdout.write(p.stdout)
-        sys.stdout.flush()
-        lines += p.stdout.splitlines()
-        if p.returncode != 0:
-            lines.append(f"workload {k} ended with status {p.returncode}: nothing further is run")
-            print(lines[-1], flush=True)
-            ok = False
-            break
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    sys.exit(0 if ok else 1)
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, HEADER, one_workload)

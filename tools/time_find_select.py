@@ -17,47 +17,23 @@ The tool asserts that (i) returns the same records as (ii) and that (i) takes no
 
 Every workload runs in a process of its own under `timeout -k 10`; the first one that fails ends the run.
 """
-import argparse
-import os
 import statistics
-import subprocess
-import sys
 import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from libhuffman_amd import datagen  # noqa: E402
-from libhuffman_amd.codec import GpuCodec  # noqa: E402
+from find_timing import GpuCodec, Workload, alternate, fmt, main
 
-WORKLOADS = [("logtext, blocks of 1 MiB", "logtext", 1 << 20), ("zipf255, blocks of 64 KiB", "zipf255", 65536)]
-STEP_SECONDS = 420
-
-
-def fmt(ts):
-    return f"{statistics.median(ts) * 1e3:8.3f} ms [{min(ts) * 1e3:.3f}, {max(ts) * 1e3:.3f}]"
+HEADER = ("{mib} MiB, delimiter newline, caps = the exact counts, "
+          "median of {runs} warm runs [min, max], the calls alternating in one process per workload")
 
 
 def one_workload(k, runs, mib):
-    what, kind, bs = WORKLOADS[k]
-    codec = GpuCodec(0)
-    n = mib << 20
-    if kind == "logtext":
-        tile = min(n, 16 << 20)
-        data = torch.from_numpy(datagen.logtext(tile)).cuda().repeat(n // tile)
-        frequent = b"ERROR"
-    else:
-        data = codec.fill(torch.empty(n, dtype=torch.uint8, device="cuda"), kind)
-        hist = torch.bincount(data[:1 << 24].int(), minlength=256)
-        hist[10] = 0                                    # (a pattern holds no delimiter)
-        frequent = bytes([int(hist.argmax())]) * 5
-    absent = frequent[:4] + (b"\xff" if kind == "zipf255" else b"\x00")
-    sub = codec.new_sub_index(n, bs)
-    stream, offs, length = codec.encode(data, bs, sub_index=sub)
-    nb = codec.block_count(n, bs)
-    del data
-    args = (stream, length, offs, nb, sub, n, bs)
+    w = Workload(k, mib)
+    what, codec, n = w.what, w.codec, w.n
+    frequent = w.frequent(delimiter=10)
+    absent = w.absent(frequent)
+    args = w.encode()
     nl_cap = int(codec.count_bytes(*args, b"\n")[0][0])
     nl_pos = torch.empty(nl_cap, dtype=torch.int64, device="cuda")
     zero, end = torch.zeros(1, dtype=torch.int64, device="cuda"), torch.full((1,), n, dtype=torch.int64, device="cuda")
@@ -104,12 +80,8 @@ def one_workload(k, runs, mib):
         _, (pos2, lens2, totals2, _, _) = select(True, False)
         assert torch.equal(pos2, want) and torch.equal(lens2.long(), want_lens) and totals2.cpu().tolist() == t
         del want, want_lens, pos, lens, numbers, pos2, lens2
-        ti, tn, ty, ta, tan = [], [], [], [], []
-        for _ in range(runs):
-            for ts, f in ((ti, lambda: select(True, False)[0]), (tn, lambda: select(True, True)[0]), (ty, lambda: recipe()[0]),
-                          (ta, records_any), (tan, lambda: select(False, True)[0])):
-                torch.cuda.synchronize()
-                ts.append(f())
+        ti, tn, ty, ta, tan = alternate(runs, lambda: select(True, False)[0], lambda: select(True, True)[0], lambda: recipe()[0],
+                                        records_any, lambda: select(False, True)[0])
         mi, mn, my, ma, man = (statistics.median(x) for x in (ti, tn, ty, ta, tan))
         print(f"{what:26s} {name:18s} {nl_cap:9d} newlines {mcap:9d} matching {cap:9d} inverted records\n"
               f"    (i)     select, invert          {fmt(ti)}\n"
@@ -121,37 +93,5 @@ def one_workload(k, runs, mib):
     codec.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--mib", type=int, default=1024)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--workload", type=int, default=-1, help="run this workload only, in this process")
-    a = ap.parse_args()
-    if a.workload >= 0:
-        one_workload(a.workload, a.runs, a.mib)
-        return
-    lines = [f"time_find_select.py: {a.mib} MiB, delimiter newline, caps = the exact counts, median of {a.runs} warm runs "
-             "[min, max], the calls alternating in one process per workload"]
-    print(lines[0], flush=True)
-    ok = True
-    for k in range(len(WORKLOADS)):
-        p = subprocess.run(["timeout", "-k", "10", str(STEP_SECONDS), sys.executable, os.path.abspath(__file__), "--workload", str(k),
-                            "--runs", str(a.runs), "--mib", str(a.mib)], stdout=subprocess.PIPE, text=True)
-        sys.stdout.write(p.stdout)
-        sys.stdout.flush()
-        lines += p.stdout.splitlines()
-        if p.returncode != 0:
-            lines.append(f"workload {k} ended with status {p.returncode}: nothing further is run")
-            print(lines[-1], flush=True)
-            ok = False
-            break
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    sys.exit(0 if ok else 1)
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, HEADER, one_workload)
