@@ -731,6 +731,75 @@ int hufgpu_find_records_anchored(hufgpu_ctx_t *ctx, const void *d_stream, uint64
                                  uint32_t flags, void *stream);
 
 /*
+ * FIND, ALL OF SEVERAL TERMS: grep A | grep B and grep 'A.*B'.  The records that hold EVERY one of up to
+ * HUFGPU_FIND_TERMS_MAX terms - "ERROR" and "timeout" in one line -, or that hold them one behind the other, in ONE walk of
+ * the stream: no call a term, no intersection of start lists on the host, and one not-served rule for the whole answer.
+ * hufgpu_find_records_terms() is hufgpu_find_records_context() - the contract holds word for word: d_sub_index (the caller
+ * vouches for NOTHING), every output, cap and total, `select`, d_rec_no, before / after, d_rec_sel, the known-extent rule,
+ * one-symbol blocks served, flags, batch geometry, nblocks = 0, enqueue-only without a host write or a wait, every argument
+ * error (worded "find_records_terms: ...") in the older call's order - but for which records are SELECTED.  There is no CPU
+ * path.
+ *
+ *   a term        : what hufgpu_find_records_any() calls the whole pattern: one or more alternatives, each a pattern of
+ *                   classes.  The terms' alternatives stand one behind the other in `classes` / `alt_lens` and share the 64
+ *                   bits of the matcher's state: the lengths of ALL alternatives of ALL terms sum to at most
+ *                   HUFGPU_FIND_PATTERN_MAX.  No class may hold a delimiter, so every occurrence lies inside one record.
+ *   term_alts     : a HOST array of n_terms counts, read before the call returns.  Term 0 is the first term_alts[0]
+ *                   alternatives, term 1 the next term_alts[1], and so on; the counts sum to n_alts.
+ *   n_terms       : 1 to HUFGPU_FIND_TERMS_MAX.  The maximum rests on the walk kernel's registers - a mask word a term next
+ *                   to the matcher's state - and on the workspace: a match mask and a record mask of raw_size / 8 bytes each
+ *                   for every term.
+ *   an occurrence : a pair (p, j) as hufgpu_find_any() defines a match of alternative j at p.
+ *   terms_mode    : how a record [s, e) of known extent SATISFIES the call.
+ *                     HUFGPU_TERMS_ALL      for every term t the record holds an occurrence of one of t's alternatives.
+ *                                           Occurrences of different terms may overlap or be the same bytes: the terms
+ *                                           ("ab", "abc") are satisfied by one "abc", as grep ab | grep abc is.
+ *                     HUFGPU_TERMS_ORDERED  the record holds occurrences (p_1, j_1) ... (p_T, j_T), j_t an alternative of
+ *                                           term t, with p_t + len_{j_t} <= p_{t+1}: T1.*T2.* ... .*TT with '.' any byte that
+ *                                           is no delimiter.  "abc" does not satisfy ("ab", "bc"), "abbc" does; "aaa" does
+ *                                           not satisfy ("aa", "aa"), "aaaa" does.  In this mode all alternatives of ONE term
+ *                                           must have one length (terms may differ): then the leftmost occurrence of a term is
+ *                                           also the one that ends first, and taking each term's first occurrence at or
+ *                                           behind the end of the one before is exact.  With unequal lengths a later, shorter
+ *                                           occurrence may end earlier - the terms ("abcd" or "bc", "d") in "abcd" -, and
+ *                                           the walk would have to try every occurrence of every term.
+ *   what is reported: S is the satisfying records; with HUFGPU_SELECT_INVERT the non-empty records of known extent that do
+ *                   NOT satisfy - a record of known extent lies in exactly one of the two answers.  From S on everything is
+ *                   hufgpu_find_records_context()'s: d_rec_no, before / after, d_rec_sel, rec_cap, max_len, d_totals[0..3],
+ *                   d_block_counts, d_block_errs.
+ *
+ * Found on the host, before anything is enqueued and before the context is looked at, behind the `select` check and in front
+ * of the older call's checks, and HUF_ERROR_INVALID_ARGUMENT are besides the older call's errors:
+ *
+ *   - a terms_mode above HUFGPU_TERMS_ORDERED (the message names the value);
+ *   - a NULL term_alts;
+ *   - an n_terms of 0 or above HUFGPU_FIND_TERMS_MAX (the message names it);
+ *   - a term of 0 alternatives (the message names the term);
+ *   - counts that do not sum to n_alts (the message names both);
+ *   - HUFGPU_TERMS_ORDERED and a term whose alternatives differ in length (the message names the term and two lengths).
+ *
+ * The identity: n_terms = 1, in either mode, enqueues exactly what hufgpu_find_records_context() enqueues for the same
+ * arguments, and the eleven older calls launch what they always did.  With more terms the walk keeps a mask word and a count
+ * a term, the records' marking kernel runs once a term, one kernel ANDs the terms' record masks and - ordered - one more
+ * walks the terms' match masks a candidate record; then the context call's kernels run as they are.  Measured in DESIGN.md 5.22.
+ *
+ * OUT OF SCOPE: anchors together with terms (hufgpu_find_records_anchored() has one term); unequal lengths inside a term of
+ * an ordered call; a positions call - a conjunction has no natural "start" -; and which occurrences satisfied a record.
+ */
+#define HUFGPU_FIND_TERMS_MAX 4
+#define HUFGPU_TERMS_ALL      0u
+#define HUFGPU_TERMS_ORDERED  1u
+int hufgpu_find_records_terms(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                              const uint64_t *d_block_offsets, uint64_t nblocks,
+                              const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                              const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                              const uint32_t *term_alts, uint32_t n_terms, uint32_t terms_mode,
+                              uint32_t select, uint32_t before, uint32_t after,
+                              uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no, uint8_t *d_rec_sel, uint64_t rec_cap, uint32_t max_len,
+                              uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                              uint32_t flags, void *stream);
+
+/*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from
  * another rank, or encoded here by a caller that did not keep the 7 % of side data.  hufgpu_encode_sub() writes the
  * sub-index as a by-product of packing; these three rebuild exactly that - the same entries, entry for entry

@@ -41,6 +41,8 @@ RANGES_TILES = 4                # hufgpu_decode_ranges only: cut blocks by the s
 SELECT_INVERT = 1               # HUFGPU_SELECT_INVERT: hufgpu_find_records_select reports the records WITHOUT a match
 ANCHOR_BOL, ANCHOR_EOL, ANCHOR_WORD = 1, 2, 4   # HUFGPU_ANCHOR_*: the anchored calls' '^', '$' and -w
 FIND_PATTERN_MAX = 64           # HUFGPU_FIND_PATTERN_MAX: the bytes of a hufgpu_find_pattern pattern
+FIND_TERMS_MAX = 4              # HUFGPU_FIND_TERMS_MAX: the terms of a hufgpu_find_records_terms call
+TERMS_ALL, TERMS_ORDERED = 0, 1  # HUFGPU_TERMS_*: every term somewhere in the record, or one behind the other
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t))
@@ -79,7 +81,8 @@ hufgpu_batch_geometry hufgpu_encode_batch hufgpu_decode_batch hufgpu_decode_rang
 hufgpu_sub_index_from_raw hufgpu_decode_build_sub hufgpu_build_sub_index hufgpu_update_ranges
 hufgpu_append hufgpu_truncate hufgpu_ranges_counters hufgpu_gather hufgpu_find_bytes hufgpu_find_pattern hufgpu_find_records
 hufgpu_find_classes hufgpu_find_records_classes hufgpu_find_any hufgpu_find_records_any
-hufgpu_find_records_select hufgpu_find_records_context hufgpu_find_any_anchored hufgpu_find_records_anchored""".split()
+hufgpu_find_records_select hufgpu_find_records_context hufgpu_find_any_anchored hufgpu_find_records_anchored
+hufgpu_find_records_terms""".split()
 
 
 def so_path() -> str:
@@ -215,6 +218,9 @@ def load() -> C.CDLL:
     L.hufgpu_find_records_anchored.restype = C.c_int      # hufgpu_find_records_context's with (word_set, anchors) behind n_alts
     L.hufgpu_find_records_anchored.argtypes = (L.hufgpu_find_records_context.argtypes[:12] + [vp, C.c_uint32] +
                                                L.hufgpu_find_records_context.argtypes[12:])
+    L.hufgpu_find_records_terms.restype = C.c_int         # hufgpu_find_records_context's with (term_alts, n_terms, terms_mode) behind n_alts
+    L.hufgpu_find_records_terms.argtypes = (L.hufgpu_find_records_context.argtypes[:12] + [vp, C.c_uint32, C.c_uint32] +
+                                            L.hufgpu_find_records_context.argtypes[12:])
     _LIB = L
     return L
 

@@ -468,6 +468,63 @@ class GpuCodec:
         def __repr__(self):
             return "AnyOf(" + ", ".join(repr(a) for a in self.alternatives) + ")"
 
+    class _Terms:
+        """What AllOf and Seq share: 1 to FIND_TERMS_MAX items, each a bytes-like literal, a list / tuple of classes or an
+        AnyOf - one TERM of hufgpu_find_records_terms."""
+        __slots__ = ("items",)
+
+        def __init__(self, *items):
+            self.items = tuple(items)
+
+        def __len__(self):
+            return len(self.items)
+
+        def __iter__(self):
+            return iter(self.items)
+
+        def __repr__(self):
+            return type(self).__name__ + "(" + ", ".join(repr(a) for a in self.items) + ")"
+
+    class AllOf(_Terms):
+        """A `pattern` of find_records / count_records / grep: the records that hold EVERY item, anywhere and in any order,
+        overlapping or not (grep A | grep B), in one walk of the stream (hufgpu_find_records_terms, HUFGPU_TERMS_ALL)."""
+        __slots__ = ()
+
+    class Seq(_Terms):
+        """A `pattern` of find_records / count_records / grep: the records that hold the items one BEHIND the other without
+        overlap, anything that is no delimiter between them (grep 'A.*B'; HUFGPU_TERMS_ORDERED).  The alternatives of an
+        AnyOf item must have one length."""
+        __slots__ = ()
+
+    @staticmethod
+    def _find_terms(pattern, ignore_case, delimiters, anchors):
+        """(key, st, term_alts, n_terms, mode) of hufgpu_find_records_terms for an AllOf / Seq of two items or more: the
+        any-of table of all items' alternatives, one behind the other, as _find_route makes it, the delimiters' byte_set,
+        and the host array of the alternatives a term.  Raises ValueError for no item or more than FIND_TERMS_MAX, for any
+        of `bol` / `eol` / `whole_line` / `word` and for a Seq item whose alternatives differ in length; TypeError for an
+        AllOf / Seq inside another one."""
+        bol, eol, whole_line, word, word_bytes = anchors
+        name = type(pattern).__name__
+        if bol or eol or whole_line or word or word_bytes is not None:
+            raise ValueError(f"`bol`, `eol`, `whole_line` and `word` do not go with {name}: an anchored search has one term")
+        if not 1 <= len(pattern) <= _native.FIND_TERMS_MAX:
+            raise ValueError(f"{name} has 1 to {_native.FIND_TERMS_MAX} items, not {len(pattern)}")
+        flat, counts = [], []
+        for t, item in enumerate(pattern):
+            if isinstance(item, GpuCodec._Terms):
+                raise TypeError(f"item {t} of {name} is {type(item).__name__}: AllOf and Seq do not nest")
+            alts = list(item) if isinstance(item, GpuCodec.AnyOf) else [item]
+            if not alts:
+                raise ValueError(f"item {t} of {name} has no alternative: no record would hold it")
+            if isinstance(pattern, GpuCodec.Seq) and len({len(a) for a in alts if not isinstance(a, str)}) > 1:
+                raise ValueError(f"item {t} of Seq has alternatives of the lengths {sorted({len(a) for a in alts})}: "
+                                 "'A.*B' needs one length an item")
+            flat += alts
+            counts.append(len(alts))
+        _, key, st = GpuCodec._find_route(GpuCodec.AnyOf(*flat), ignore_case, delimiters, True)
+        mode = _native.TERMS_ORDERED if isinstance(pattern, GpuCodec.Seq) else _native.TERMS_ALL
+        return key, st, np.array(counts, np.uint32).tobytes(), len(counts), mode
+
     @staticmethod
     def alt_classes(anyof, ignore_case: bool = False):
         """The two host arrays of hufgpu_find_any for an AnyOf: (classes uint8 [total][32] - the alternatives' byte_classes
@@ -481,8 +538,8 @@ class GpuCodec:
             raise ValueError(f"an AnyOf has 1 to {_native.FIND_PATTERN_MAX} alternatives, not {n}")
         rows = []
         for j, alt in enumerate(anyof):
-            if isinstance(alt, str):
-                raise TypeError("an alternative is a bytes-like object or a list / tuple of classes, not a str")
+            if isinstance(alt, (str, GpuCodec._Terms)):
+                raise TypeError(f"an alternative is a bytes-like object or a list / tuple of classes, not a {type(alt).__name__}")
             if len(alt) == 0:
                 raise ValueError(f"alternative {j} has length 0: it would match everywhere")
             try:
@@ -597,7 +654,10 @@ class GpuCodec:
         of `word_bytes` ([A-Za-z0-9_] when not given).  The reported position is still the pattern's own start.  `delimiters`
         matters with `bol`, `eol` or `whole_line` only; with none of the five set the call is the one it always was.  Raises
         ValueError for `word_bytes` without `word`, and with `eol`, `whole_line` or `word` for alternatives whose lengths plus
-        one each exceed FIND_PATTERN_MAX."""
+        one each exceed FIND_PATTERN_MAX.  An AllOf or a Seq is a TypeError: a conjunction has no position of its own."""
+        if isinstance(pattern, GpuCodec._Terms):
+            raise TypeError(f"{type(pattern).__name__} selects records: find_records, count_records and grep take it, a search for "
+                            "positions does not")
         route, key, st, (anchors, ws) = self._find_route(pattern, ignore_case, anchors=(bol, eol, whole_line, word, word_bytes))
         max_positions = int(max_positions)
         pos = self._find_buffer(out, max_positions, torch.int64)
@@ -661,12 +721,28 @@ class GpuCodec:
         ([A-Za-z0-9_] when not given).  Every overlapping occurrence is tested, so `word` selects b"foofoo foo" for b"foo" as
         GNU grep does.  Any of them makes the call hufgpu_find_records_anchored; everything else - `invert`, `line_numbers`,
         the distances, what is returned - applies to that selection unchanged.  `word_bytes` without `word` is a ValueError,
-        and so are, with `eol`, `whole_line` or `word`, alternatives whose lengths plus one each exceed FIND_PATTERN_MAX."""
+        and so are, with `eol`, `whole_line` or `word`, alternatives whose lengths plus one each exceed FIND_PATTERN_MAX.
+        A GpuCodec.AllOf pattern selects the records that hold EVERY one of its 1 to FIND_TERMS_MAX items (grep A | grep B), a
+        GpuCodec.Seq pattern those that hold them one behind the other without overlap (grep 'A.*B'), still in one walk
+        (hufgpu_find_records_terms); an item is a bytes-like literal, a list / tuple of classes or an AnyOf, and all items'
+        alternatives together share the FIND_PATTERN_MAX positions.  `ignore_case`, `invert`, `line_numbers` and the distances
+        apply to that selection unchanged; one item makes the call that the item alone makes.  ValueError: any of `bol`, `eol`,
+        `whole_line`, `word` next to them, more than FIND_TERMS_MAX items, and a Seq item whose alternatives differ in
+        length; TypeError: an AllOf or a Seq inside another one or inside an AnyOf."""
         before, after = self._find_context(before, after, context)
         widens = bool(before or after)
         select = bool(invert) or bool(line_numbers) or widens
-        route, key, st, (anchors, ws) = self._find_route(pattern, ignore_case, delimiters, select,
-                                                         (bol, eol, whole_line, word, word_bytes))
+        terms = None
+        if isinstance(pattern, GpuCodec._Terms):
+            terms = self._find_terms(pattern, ignore_case, delimiters, (bol, eol, whole_line, word, word_bytes))
+            if terms[3] == 1:                                           # one item: the call that it makes today
+                (pattern,), terms = pattern, None
+        if terms is not None:
+            key, st, term_alts, n_terms, mode = terms
+            anchors, ws = 0, None
+        else:
+            route, key, st, (anchors, ws) = self._find_route(pattern, ignore_case, delimiters, select,
+                                                             (bol, eol, whole_line, word, word_bytes))
         max_records, max_len = int(max_records), int(max_len)
         out = tuple(out) if out is not None else (None, None)
         numbers = self._find_buffer(out[2] if len(out) > 2 else None, max_records, torch.int64) if line_numbers else None
@@ -677,7 +753,12 @@ class GpuCodec:
         head, tail, totals, errs, counts = self._find_args(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
                                                            block_counts, relaxed)
         ptrs = (pos.data_ptr() if max_records else None, lens.data_ptr() if max_records else None)
-        if anchors:
+        if terms is not None:
+            err = self.lib.hufgpu_find_records_terms(*head, st, *key, term_alts, n_terms, mode, _native.SELECT_INVERT if invert else 0,
+                                                     before, after, *ptrs, numbers.data_ptr() if line_numbers and max_records else None,
+                                                     selected.data_ptr() if widens and max_records else None, max_records, max_len,
+                                                     *tail)
+        elif anchors:
             err = self.lib.hufgpu_find_records_anchored(*head, st, *key, ws, anchors, _native.SELECT_INVERT if invert else 0, before,
                                                         after, *ptrs, numbers.data_ptr() if line_numbers and max_records else None,
                                                         selected.data_ptr() if widens and max_records else None, max_records, max_len,

@@ -136,6 +136,13 @@ struct hufgpu_ctx {
      * the tile counts that find_sub_kernel writes next to it (nobody reads them); no other call allocates them */
     uint64_t faws_words, faws_tiles;
     uint32_t *d_fabits, *d_fatcnt;
+    /* hufgpu_find_records_terms with two terms or more: a match mask and a record mask a term with their tile counts,
+     * term-major (the capacities count terms x words and terms x tiles), sixteen words for the totals of the terms' scans,
+     * and - an ordered call only - a scan of the match counts a term; no other call allocates them */
+    uint64_t ftws_words, ftws_tiles, ftsws_tiles[FIND_TERMS_MAX];
+    uint32_t *d_ftmbits, *d_ftrbits, *d_ftmcnt, *d_ftrcnt;
+    uint64_t *d_fttotals;
+    TwoLevel fterm_scan[FIND_TERMS_MAX];
 
     /* the sub-index builders (kernels/sub_build.hpp): what their kernels hand to one another, per block and per chunk */
     uint64_t sbws_blocks, sbws_chunks;
@@ -276,6 +283,9 @@ static const ws_buf WS_FIND_CTX_WORDS[] = {DEV(d_fcbits, n * sizeof(uint32_t))};
 static const ws_buf WS_FIND_CTX_TILES[] = {DEV(d_fccnt, n * sizeof(uint32_t)), DEV(d_fctotals, 4 * sizeof(uint64_t))};
 static const ws_buf WS_FIND_ANC_WORDS[] = {DEV(d_fabits, n * sizeof(uint32_t))};
 static const ws_buf WS_FIND_ANC_TILES[] = {DEV(d_fatcnt, n * sizeof(uint32_t))};
+static const ws_buf WS_FIND_TERM_WORDS[] = {DEV(d_ftmbits, n * sizeof(uint32_t)), DEV(d_ftrbits, n * sizeof(uint32_t))};
+static const ws_buf WS_FIND_TERM_TILES[] = {DEV(d_ftmcnt, n * sizeof(uint32_t)), DEV(d_ftrcnt, n * sizeof(uint32_t)),
+                                            DEV(d_fttotals, 4 * FIND_TERMS_MAX * sizeof(uint64_t))};
 static const ws_buf WS_SB_BLOCKS[] = {DEV(d_sb_state, n * sizeof(uint32_t)), DEV(d_sb_pay, n * sizeof(uint64_t))};
 static const ws_buf WS_SB_CHUNKS[] = {DEV(d_sb_chunk_tot, n * sizeof(uint64_t)), DEV(d_sb_chunk_bits, n * sizeof(uint64_t))};
 static const ws_buf WS_UPD_BLOCKS[] = {
@@ -289,7 +299,8 @@ static const ws_buf WS_UPD_PIECES[] = {DEV(d_upiece, n * sizeof(uint32_t))};
  * block of many MiB and the range scratch take what they are asked for (grow_range_scratch adds its own eighth).
  * Soft groups report nothing: the caller has another way, or words the error itself. */
 enum { G_FIXED, G_ENCODE, G_CHUNK, G_DECODE, G_DISC_WGS, G_DISC_CANDS, G_BIG_LANES, G_BIG_SUB, G_BSTAGE, G_BATCH, G_RANGE,
-       G_RSCRATCH, G_GATHER_BLOCKS, G_GATHER_PARTS, G_FIND_WORDS, G_FIND_TILES, G_FIND_EDGES, G_FIND_REC_WORDS, G_FIND_REC_TILES, G_FIND_SEL, G_FIND_CTX_WORDS, G_FIND_CTX_TILES, G_FIND_ANC_WORDS, G_FIND_ANC_TILES, G_SB_BLOCKS, G_SB_CHUNKS, G_UPD_BLOCKS,
+       G_RSCRATCH, G_GATHER_BLOCKS, G_GATHER_PARTS, G_FIND_WORDS, G_FIND_TILES, G_FIND_EDGES, G_FIND_REC_WORDS, G_FIND_REC_TILES, G_FIND_SEL, G_FIND_CTX_WORDS, G_FIND_CTX_TILES, G_FIND_ANC_WORDS, G_FIND_ANC_TILES,
+       G_FIND_TERM_WORDS, G_FIND_TERM_TILES, G_FIND_TERM_SCAN0, G_FIND_TERM_SCAN1, G_FIND_TERM_SCAN2, G_FIND_TERM_SCAN3, G_SB_BLOCKS, G_SB_CHUNKS, G_UPD_BLOCKS,
        G_UPD_PIECES, G_COUNT };
 #define ROWS(a) a, (int)(sizeof(a) / sizeof(a[0]))
 #define CAP(member) {offsetof(hufgpu_ctx, member), WS_NO_CAP}
@@ -321,6 +332,12 @@ static const ws_group WS[G_COUNT] = {
     {"find context tiles", ROWS(WS_FIND_CTX_TILES), CAP(fcws_tiles), WS_DOUBLE, false, SCAN_AT(fctx_scan)},
     {"find anchor words", ROWS(WS_FIND_ANC_WORDS), CAP(faws_words), WS_DOUBLE, false, NO_SCAN},
     {"find anchor tiles", ROWS(WS_FIND_ANC_TILES), CAP(faws_tiles), WS_DOUBLE, false, NO_SCAN},
+    {"find term words", ROWS(WS_FIND_TERM_WORDS), CAP(ftws_words), WS_DOUBLE, false, NO_SCAN},
+    {"find term tiles", ROWS(WS_FIND_TERM_TILES), CAP(ftws_tiles), WS_DOUBLE, false, NO_SCAN},
+    {"find term scan 0", NULL, 0, CAP(ftsws_tiles[0]), WS_DOUBLE, false, SCAN_AT(fterm_scan[0])},      /* (a scan and nothing else) */
+    {"find term scan 1", NULL, 0, CAP(ftsws_tiles[1]), WS_DOUBLE, false, SCAN_AT(fterm_scan[1])},
+    {"find term scan 2", NULL, 0, CAP(ftsws_tiles[2]), WS_DOUBLE, false, SCAN_AT(fterm_scan[2])},
+    {"find term scan 3", NULL, 0, CAP(ftsws_tiles[3]), WS_DOUBLE, false, SCAN_AT(fterm_scan[3])},
     {"sub-build blocks", ROWS(WS_SB_BLOCKS), CAP(sbws_blocks), WS_EIGHTH, false, NO_SCAN},
     {"sub-build chunks", ROWS(WS_SB_CHUNKS), CAP(sbws_chunks), WS_EIGHTH, false, NO_SCAN},
     {"update blocks", ROWS(WS_UPD_BLOCKS), CAP(uws_blocks), WS_EIGHTH, false, NO_SCAN},

@@ -3,7 +3,8 @@
    patterns; hufgpu_find_records, hufgpu_find_records_classes, hufgpu_find_records_any and hufgpu_find_records_select give
    the records - the pieces between delimiters - that hold one (or do not), and their numbers; hufgpu_find_records_context
    gives the records around them as well; hufgpu_find_any_anchored and hufgpu_find_records_anchored are hufgpu_find_any and
-   the context call for the matches that begin or end at a record's or a word's edge.  All enqueue-only.  A
+   the context call for the matches that begin or end at a record's or a word's edge; hufgpu_find_records_terms is the
+   context call for the records that hold all of several terms, or all of them in order.  All enqueue-only.  A
    wrapper describes its call in three structs; find_call checks them (find_check, no HIP call), fills the kernels'
    arguments and grows the workspace (find_fill) and enqueues the chain of kernels/find.hpp (find_enqueue).
    Part of hufgpu_api.hip (one translation unit). */
@@ -11,6 +12,7 @@
 
 static_assert(FIND_PAT_MAX == HUFGPU_FIND_PATTERN_MAX, "kernels/find.hpp and include/huffman_gpu.h");
 static_assert(FIND_REC_NO_UNKNOWN == HUFGPU_REC_NO_UNKNOWN, "kernels/find.hpp and include/huffman_gpu.h");
+static_assert(FIND_TERMS_MAX == HUFGPU_FIND_TERMS_MAX, "kernels/find.hpp and include/huffman_gpu.h");
 
 /* an argument is wrong: the words for it, and the status */
 template <typename... A>
@@ -65,6 +67,13 @@ struct FindAncCall {
     uint8_t behind[32];                     /* EOL / WORD: ... and behind one */
 };
 
+/* what hufgpu_find_records_terms has beyond the context call, with two terms or more: the kernels' description of the terms
+ * (find_term_split fills the host's part of it, find_fill the workspace's) and the mode */
+struct FindTermCall {
+    FindTerms t;
+    bool ordered;
+};
+
 /* What is looked for: `who` words the errors, `key` is the set (plen = 0) or the pattern of plen bytes, `key_name` its name;
  * rec is NULL but for the records' calls.  cls is NULL but for the class calls: then `key` is the caller's array of plen
  * classes, which find_call only checks for NULL and never reads - its wrapper has read it -, and cls is the table made
@@ -73,7 +82,9 @@ struct FindAncCall {
  * sel is NULL but for the select and the context call: the any-of records' call with up to three launches more.
  * cx is NULL but for the context call, which is the select call with a dilation of the selected records' mask.
  * anc is NULL but for the anchored calls with an anchor: then alt's table holds one position more an alternative when
- * the byte behind a match is tested, and find_anchor_kernel runs when the byte in front is. */
+ * the byte behind a match is tested, and find_anchor_kernel runs when the byte in front is.
+ * term is NULL but for the terms' call with two terms or more: the walk and the seam kernel then keep a mask a term, and
+ * find_rec_mark_kernel runs once a term in front of find_rec_all_kernel (and find_rec_seq_kernel). */
 struct FindKey {
     const char *who, *key_name;
     const uint8_t *key;
@@ -84,6 +95,7 @@ struct FindKey {
     const FindSelCall *sel;
     const FindCtxCall *cx;
     const FindAncCall *anc;
+    FindTermCall *term;
 };
 
 /* does the context call widen the answer: with both distances 0 it is the select call, maybe with flags */
@@ -153,6 +165,8 @@ static int find_fill(hufgpu_ctx_t *ctx, const FindStream &in, const FindOut &out
     if (!rc && find_anc_third(k)) rc = grow_ws2(ctx, G_FIND_ANC_WORDS, nwords, G_FIND_ANC_TILES, ntiles);
     if (!rc && k.sel && k.sel->d_rec_no && out.cap > 0) rc = grow_ws(ctx, G_FIND_SEL, 1);
     if (!rc && find_widens(k)) rc = grow_ws2(ctx, G_FIND_CTX_WORDS, nwords, G_FIND_CTX_TILES, ntiles);
+    if (!rc && k.term) rc = grow_ws2(ctx, G_FIND_TERM_WORDS, k.term->t.n_terms * nwords, G_FIND_TERM_TILES, k.term->t.n_terms * ntiles);
+    for (uint32_t t = 0; !rc && k.term && k.term->ordered && t < k.term->t.n_terms; t++) rc = grow_ws(ctx, G_FIND_TERM_SCAN0 + (int)t, ntiles);
     if (rc) return rc;
     memset(&ra, 0, sizeof(ra));
     FindPatArgs &pa = ra.p;
@@ -191,6 +205,14 @@ static int find_fill(hufgpu_ctx_t *ctx, const FindStream &in, const FindOut &out
         ra.dbits = ctx->d_frdbits;
         ra.dcnt = ctx->d_frdcnt;
     }
+    if (k.term) {
+        FindTerms &tm = k.term->t;
+        tm.mbits = ctx->d_ftmbits;
+        tm.mcnt = ctx->d_ftmcnt;
+        tm.rbits = ctx->d_ftrbits;
+        tm.rcnt = ctx->d_ftrcnt;
+        tm.nwords = nwords;
+    }
     return HUFE_OK;
 }
 
@@ -200,7 +222,15 @@ static void find_enqueue_walk(hufgpu_ctx_t *ctx, const FindKey &k, const FindRec
 {
     const dim3 wt(FIND_THREADS), st(FIND_SEAM_THREADS);
     const bool rec = k.rec != NULL, seam = k.plen > 1;
-    if (k.alt) {
+    if (k.term) {
+        /* a mask a term, and a kernel for each number of terms: a mask that is not needed still costs registers */
+        k.alt->r = ra;
+        const FindTermArgs ta = {*k.alt, k.term->t};
+        if (ta.t.n_terms == 2) find_rec_term_sub_kernel<2><<<walk, wt, 0, s>>>(ta);
+        else if (ta.t.n_terms == 3) find_rec_term_sub_kernel<3><<<walk, wt, 0, s>>>(ta);
+        else find_rec_term_sub_kernel<FIND_TERMS_MAX><<<walk, wt, 0, s>>>(ta);
+        if (seam) find_term_seam_kernel<<<seams, st, 0, s>>>(ta);
+    } else if (k.alt) {
         k.alt->r = ra;
         const bool front = find_anc_front(k), third = find_anc_third(k);
         if (rec || front) find_rec_alt_sub_kernel<<<walk, wt, 0, s>>>(*k.alt);
@@ -247,8 +277,11 @@ static int find_enqueue(hufgpu_ctx_t *ctx, const FindOut &out, const FindKey &k,
     HIP_OK(ctx, hipMemsetAsync(out.d_totals, 0, 4 * sizeof(uint64_t), s));
     const bool widens = find_widens(k);
     if (k.rec) {
-        HIP_OK(ctx, hipMemsetAsync(ra.rbits, 0, nblocks * fa.wpb * sizeof(uint32_t), s));
-        HIP_OK(ctx, hipMemsetAsync(ra.rcnt, 0, fa.ntiles * sizeof(uint32_t), s));
+        /* the terms' call: mark writes a mask and counts a term, and find_rec_all_kernel stores every word of ra's */
+        const uint64_t nt = k.term ? k.term->t.n_terms : 1;
+        HIP_OK(ctx, hipMemsetAsync(k.term ? k.term->t.rbits : ra.rbits, 0, nt * nblocks * fa.wpb * sizeof(uint32_t), s));
+        HIP_OK(ctx, hipMemsetAsync(k.term ? k.term->t.rcnt : ra.rcnt, 0, nt * fa.ntiles * sizeof(uint32_t), s));
+        if (k.term && k.term->ordered) HIP_OK(ctx, hipMemsetAsync(ctx->d_fttotals, 0, 4 * FIND_TERMS_MAX * sizeof(uint64_t), s));
         if (widens) HIP_OK(ctx, hipMemsetAsync(ctx->d_fctotals, 0, 4 * sizeof(uint64_t), s));
     }
     find_enqueue_walk(ctx, k, ra, walk, seams, tiles, s);
@@ -264,7 +297,32 @@ static int find_enqueue(hufgpu_ctx_t *ctx, const FindOut &out, const FindKey &k,
         } else {
             find_rec_dscan_kernel<<<groups, dim3(SCAN_GROUP), 0, s>>>(ra);
         }
-        find_rec_mark_kernel<<<tiles, et, 0, s>>>(ra);
+        if (k.term) {
+            /* mark as it is, once a term, from term t's match words and counts into term t's record mask and counts; then
+             * the records that every term marked, and of those - ordered - the ones that hold the terms one behind the other */
+            const FindTerms &tm = k.term->t;
+            FindSeqArgs qa = {ra, tm, {}};
+            for (uint32_t t = 0; t < tm.n_terms; t++) {
+                FindRecArgs ta = ra;
+                ta.p.f.bitmap = tm.mbits + t * tm.nwords;
+                ta.p.f.tcnt = tm.mcnt + t * fa.ntiles;
+                ta.rbits = tm.rbits + t * tm.nwords;
+                ta.rcnt = tm.rcnt + t * fa.ntiles;
+                find_rec_mark_kernel<<<tiles, et, 0, s>>>(ta);
+                if (k.term->ordered) {                              /* the term's match counts into a scan and totals of the workspace's own */
+                    FindArgs sfa = ta.p.f;
+                    sfa.scan = ctx->fterm_scan[t];
+                    sfa.scan.total = sfa.totals = ctx->d_fttotals + 4 * t;
+                    find_scan_kernel<<<groups, dim3(SCAN_GROUP), 0, s>>>(sfa);
+                    qa.tscan[t] = sfa.scan;
+                }
+            }
+            const FindAllArgs aa = {ra, tm};
+            find_rec_all_kernel<<<tiles, et, 0, s>>>(aa);
+            if (k.term->ordered) find_rec_seq_kernel<<<tiles, et, 0, s>>>(qa);
+        } else {
+            find_rec_mark_kernel<<<tiles, et, 0, s>>>(ra);
+        }
         if (k.sel && (k.sel->select & HUFGPU_SELECT_INVERT)) find_rec_invert_kernel<<<tiles, et, 0, s>>>(ra);   /* over mark's words and counts */
         fa.tcnt = ra.rcnt;
         if (widens) {
@@ -471,17 +529,36 @@ static int find_alt_table(hufgpu_ctx_t *ctx, const char *who, const uint8_t *cla
     return HUFE_OK;
 }
 
-/* the six any-of wrappers' call: the table, when both arrays are there (find_check words a missing one), then find_call */
+/* The terms of a table that find_alt_table has made, term_alts[t] alternatives each in the table's order: the start bits a
+ * term, the term's index into bits 6 and 7 of its alternatives' hl (a hi is 0 to 63, a length sits from bit 8 on), and the
+ * length of the term's first alternative - of all of them in an ordered call, which find_term_check has seen to. */
+static void find_term_split(FindAltArgs *t, const uint32_t *alt_lens, const uint32_t *term_alts, FindTermCall *term)
+{
+    FindTerms &tm = term->t;
+    uint32_t j = 0;
+    for (uint32_t q = 0; q < tm.n_terms; q++) {
+        tm.len[q] = alt_lens[j];
+        for (const uint32_t end = j + term_alts[q]; j < end; j++) {
+            const uint32_t hi = t->hl[j] & 63u;
+            tm.starts[q][hi >> 5] |= 1u << (hi & 31u);
+            t->hl[j] = (uint16_t)(t->hl[j] | (q << 6));
+        }
+    }
+}
+
+/* the seven any-of wrappers' call: the table, when both arrays are there (find_check words a missing one), then find_call */
 static int find_alt_call(hufgpu_ctx_t *ctx, const char *who, const FindStream &in, const FindOut &out, const uint8_t *classes,
                          const uint32_t *alt_lens, uint32_t n_alts, const FindRecCall *rec, const FindSelCall *sel, const FindCtxCall *cx,
-                         uint32_t flags, void *stream, const FindAncCall *anc = NULL)
+                         uint32_t flags, void *stream, const FindAncCall *anc = NULL, FindTermCall *term = NULL,
+                         const uint32_t *term_alts = NULL)
 {
     FindAltArgs t;
     uint32_t maxlen = 0;
     const bool both = classes && alt_lens;
     const uint8_t *behind = anc && (anc->anchors & (HUFGPU_ANCHOR_EOL | HUFGPU_ANCHOR_WORD)) ? anc->behind : NULL;
     if (both && find_alt_table(ctx, who, classes, alt_lens, n_alts, rec ? rec->delim_set : NULL, &t, &maxlen, behind)) return HUFE_ARGUMENT;
-    const FindKey k = {who, "classes, alt_lens", both ? classes : NULL, maxlen, rec, &t.t, &t, sel, cx, anc};
+    if (both && term) find_term_split(&t, alt_lens, term_alts, term);
+    const FindKey k = {who, "classes, alt_lens", both ? classes : NULL, maxlen, rec, &t.t, &t, sel, cx, anc, term};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -597,4 +674,59 @@ extern "C" int hufgpu_find_records_anchored(hufgpu_ctx_t *ctx, const void *d_str
     const bool plain = (before | after) == 0u && !d_rec_sel;        /* the select call, by its launches */
     return find_alt_call(ctx, "find_records_anchored", in, out, classes, alt_lens, n_alts, &rec, &sel, plain ? NULL : &cx, flags, stream,
                          anchors ? &anc : NULL);
+}
+
+/* hufgpu_find_records_terms' own checks, behind the `select` check and in front of the older calls': the mode, the array,
+ * the number of terms, a term without alternatives, counts that do not sum to n_alts and - ordered - a term whose
+ * alternatives differ in length.  The lengths are looked at only where the older checks would read them too: both arrays
+ * there and n_alts within its bounds; whatever else is wrong with them is the older checks' to word. */
+static int find_term_check(hufgpu_ctx_t *ctx, const char *who, const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                           const uint32_t *term_alts, uint32_t n_terms, uint32_t terms_mode)
+{
+    if (terms_mode > HUFGPU_TERMS_ORDERED)
+        return find_bad(ctx, "%s: terms_mode %u is neither HUFGPU_TERMS_ALL (0) nor HUFGPU_TERMS_ORDERED (1)", who, terms_mode);
+    if (!term_alts) return find_bad(ctx, "%s: term_alts is required (one term: an array of the one count, n_alts)", who);
+    if (n_terms == 0 || n_terms > HUFGPU_FIND_TERMS_MAX)
+        return find_bad(ctx, "%s: n_terms %u is not 1 to %d", who, n_terms, HUFGPU_FIND_TERMS_MAX);
+    uint64_t total = 0;
+    for (uint32_t t = 0; t < n_terms; t++) {
+        if (term_alts[t] == 0) return find_bad(ctx, "%s: term %u has no alternative: no record would hold it", who, t);
+        total += term_alts[t];
+    }
+    if (total != n_alts)
+        return find_bad(ctx, "%s: the %u terms have %llu alternatives, and n_alts is %u", who, n_terms, (unsigned long long)total, n_alts);
+    if (terms_mode != HUFGPU_TERMS_ORDERED || !classes || !alt_lens || n_alts > HUFGPU_FIND_PATTERN_MAX) return HUFE_OK;
+    for (uint32_t t = 0, j = 0; t < n_terms; j += term_alts[t++]) {
+        for (uint32_t i = 1; i < term_alts[t]; i++) {
+            if (alt_lens[j + i] != alt_lens[j])
+                return find_bad(ctx, "%s: the alternatives of term %u have the lengths %u and %u: an ordered call needs one length a term",
+                                who, t, alt_lens[j], alt_lens[j + i]);
+        }
+    }
+    return HUFE_OK;
+}
+
+extern "C" int hufgpu_find_records_terms(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                         uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                         const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                                         const uint32_t *term_alts, uint32_t n_terms, uint32_t terms_mode, uint32_t select,
+                                         uint32_t before, uint32_t after, uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no,
+                                         uint8_t *d_rec_sel, uint64_t rec_cap, uint32_t max_len, uint64_t *d_block_counts,
+                                         uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream)
+{
+    if (select & ~HUFGPU_SELECT_INVERT)
+        return find_bad(ctx, "find_records_terms: select 0x%x has a bit other than HUFGPU_SELECT_INVERT", select);
+    if (find_term_check(ctx, "find_records_terms", classes, alt_lens, n_alts, term_alts, n_terms, terms_mode)) return HUFE_ARGUMENT;
+    const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
+    const FindOut out = {d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs};
+    const FindRecCall rec = {delim_set, d_rec_len, max_len};
+    const FindSelCall sel = {select, d_rec_no};
+    const FindCtxCall cx = {before, after, d_rec_sel};
+    const bool plain = (before | after) == 0u && !d_rec_sel;        /* the select call, by its launches */
+    FindTermCall term;
+    memset(&term, 0, sizeof(term));
+    term.t.n_terms = n_terms;
+    term.ordered = terms_mode == HUFGPU_TERMS_ORDERED;
+    return find_alt_call(ctx, "find_records_terms", in, out, classes, alt_lens, n_alts, &rec, &sel, plain ? NULL : &cx, flags, stream, NULL,
+                         n_terms > 1 ? &term : NULL, term_alts);              /* (one term: the context call, by its launches) */
 }

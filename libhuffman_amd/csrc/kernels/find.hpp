@@ -28,9 +28,14 @@
                                    find_anchor on the delimiters' mask, behind the seam kernel and in front of dscan / mark.
                                    WORD: find_sub walks the stream a second time, behind find_rec_alt_sub, for a third mask -
                                    the bytes that may stand in front of a match -, which find_anchor takes
+   hufgpu_find_records_terms       n_terms = 1: the context call's chain.  2 to 4 terms: find_rec_term_sub -> find_term_seam ->
+                                   dscan -> find_rec_mark ONCE A TERM (term t's match mask into term t's record mask) ->
+                                   find_rec_all (the AND of the record masks, into the mask that mark leaves for the other
+                                   calls) [-> find_scan once a term (of the terms' match counts, into scans of their own) ->
+                                   find_rec_seq: ORDERED only], then the context call's chain from [find_rec_invert] on
    RECORDS = find_rec_dscan -> find_rec_mark -> find_scan -> find_finish [-> find_rec_emit]; no seam kernel for 1 byte
 
-   The walk: find_sub_body, the seven *_sub kernels
+   The walk: find_sub_body, the seven *_sub kernels and find_rec_term_sub_kernel
      Workgroup = one (block, chunk of 65 536 symbols), decode_sub_kernel's geometry with eight waves; a wave takes the
      chunk's tiles wave, wave + 8, ...  The header is parsed and its length must be the layout's, the tables come from
      dsub_fast_tables (the claimed code lengths checked against the stream's tree), and EVERY tile of EVERY chunk is the
@@ -56,6 +61,9 @@
                  alternative fits in the tile, whichever alternative lies there;
        records   next to all that a DELIMITER mask word a group - the lane's 32 bytes against the delimiter set in
                  LDS - and the tile's delimiter count;
+       terms     the any-of records' walk with the alternatives in 2 to 4 TERMS: the start bits are kept apart by term
+                 (FindTerms::starts), and a match mask word a group and a count a tile leave the workgroup for EVERY term,
+                 term-major; plen, the edges and the walk / seam split are the longest alternative's of all terms;
        anchored  no walk kernel of its own.  The byte BEHIND a match needs no kernel: it is one position more an
                  alternative in the table - its class the delimiters, the bytes that are no word byte, or both -, plen is
                  the longest alternative + 1, and edges, warm-up and the walk / seam split follow it as they always did.
@@ -112,7 +120,8 @@
                            find_ctx_emit_no_kernel are the emit kernels with a flag a record: is it one of the selected.
 
    Invariants
-     Zeroed by the host before the first kernel: the statuses d_block_errs, d_totals, and for the records rbits and rcnt.
+     Zeroed by the host before the first kernel: the statuses d_block_errs, d_totals, and for the records rbits and rcnt
+     (the terms' call: every term's rbits and rcnt in their place - find_rec_all_kernel writes the call's own with plain stores).
      Every other word that a later kernel reads is written by the walk: the mask word of every group and the count of every
      tile of every block whose header parses (the rest is never read: every reader looks at the status first).
      Any failed check of any chunk raises the block's status to HUF_ERROR_READ_WRITE (atomic max, find_raise); nothing is
@@ -287,6 +296,26 @@ struct FindAltArgs {
 };
 static_assert(sizeof(FindAltArgs) <= 4096, "a kernel's arguments end at 4 KiB");
 
+/* hufgpu_find_records_terms: the alternatives of the any-of table in 2 to FIND_TERMS_MAX TERMS, a term the alternatives
+ * j with bits 6 and 7 of hl[j] equal to its index.  starts[t] has the start bits of term t's alternatives only, so
+ * (state & starts[t]) != 0 says "a match of term t starts at this byte"; len[t] is the one length of an ordered call's term.
+ * The walk and the seam kernel write a match mask and tile counts a term, find_rec_mark_kernel makes a record mask and
+ * counts a term of them: all term-major, [n_terms][nwords] words and [n_terms][ntiles] counts (ntiles is the FindArgs'). */
+#define FIND_TERMS_MAX 4                    /* = HUFGPU_FIND_TERMS_MAX (include/huffman_gpu.h) */
+struct FindTerms {
+    uint32_t n_terms;
+    uint32_t len[FIND_TERMS_MAX];
+    uint32_t starts[FIND_TERMS_MAX][2];     /* ([0] the low half) */
+    uint32_t *mbits, *mcnt;                 /* the terms' match starts and how many a tile holds */
+    uint32_t *rbits, *rcnt;                 /* the terms' record starts and how many a tile holds; zero when the first kernel starts */
+    uint64_t nwords;                        /* nblocks * wpb */
+};
+struct FindTermArgs {
+    FindAltArgs a;                          /* a.r.p.f.bitmap / tcnt are not looked at: the terms have their own */
+    FindTerms t;
+};
+static_assert(sizeof(FindTermArgs) <= 4096, "a kernel's arguments end at 4 KiB");
+
 #define FIND_CLS_WORDS 512                  /* the table's words in LDS: m[v] at words 2 v and 2 v + 1 */
 
 /* one byte of the Shift-And automaton that runs over the REVERSED pattern, from high addresses to low ones: bit 63 - k of
@@ -337,16 +366,48 @@ __device__ __forceinline__ uint32_t find_cls_lane(const uint32_t *tile_words, co
     return mine == 0u ? 0u : (mine < 32u ? m & ((1u << mine) - 1u) : m);
 }
 
+/* find_cls_lane<true> with a mask word a TERM: the automaton is the same one, and in the place of "any start bit" the lane
+ * asks NT times "a start bit of term t".  NT, the number of terms, is the kernel's at compile time: the masks stay in registers. */
+template <uint32_t NT>
+__device__ __forceinline__ void find_term_lane(const uint32_t *tile_words, const uint32_t (&w)[8], const uint32_t *s_m, uint32_t first_lo,
+                                               uint32_t first_hi, uint32_t plen, uint32_t tsym, uint32_t lane, const FindTerms &tm,
+                                               uint32_t (&m)[NT])
+{
+    uint32_t lo = 0, hi = 0;
+    for (uint32_t k = (plen + 2u) >> 2; k-- > 0u;) {                /* the words that hold the plen - 1 bytes behind the lane's */
+        const uint32_t x = tile_words[dmin<uint32_t>(8u * lane + 8u + k, HUF_SUB_TILE / 4 - 1u)];
+#pragma unroll
+        for (int i = 3; i >= 0; i--) find_cls_step(lo, hi, s_m, first_lo, first_hi, (x >> (8 * i)) & 0xffu);
+    }
+#pragma unroll
+    for (uint32_t t = 0; t < NT; t++) m[t] = 0;
+#pragma unroll
+    for (int j = 7; j >= 0; j--) {
+#pragma unroll
+        for (int i = 3; i >= 0; i--) {
+            find_cls_step(lo, hi, s_m, first_lo, first_hi, (w[j] >> (8 * i)) & 0xffu);
+#pragma unroll
+            for (uint32_t t = 0; t < NT; t++) m[t] = (m[t] << 1) | dmin<uint32_t>((hi & tm.starts[t][1]) | (lo & tm.starts[t][0]), 1u);
+        }
+    }
+    const uint32_t mine = find_fit(plen, tsym, lane);
+#pragma unroll
+    for (uint32_t t = 0; t < NT; t++) m[t] = mine == 0u ? 0u : (mine < 32u ? m[t] & ((1u << mine) - 1u) : m[t]);
+}
+
 /* the body of the seven walk kernels, grid nblocks * cpb, in one piece: the key into LDS, the header, then either the
  * branch of a block of one byte value or the tables and the loop over the chunk's tiles.  PAT = false: the bytes' call, p
  * is not looked at.  REC: r's delimiter masks and counts next to the pattern's work.  CLS: the class table
  * ct in the place of the pattern's bytes.  ALT: ct holds several alternatives, alt says where they start, and p->plen is
- * the longest one's length. */
-template <bool PAT, bool REC = false, bool CLS = false, bool ALT = false>
+ * the longest one's length.  NT != 0 (find_rec_term_sub_kernel): the alternatives stand in NT terms, and what leaves the
+ * workgroup is a match mask word a group and a count a tile for every TERM, into tm's term-major arrays, in the place of the one
+ * mask and count: the delimiter mask, the edges, the checks and the status are as they are. */
+template <bool PAT, bool REC = false, bool CLS = false, bool ALT = false, uint32_t NT = 0>
 __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatArgs *p, const FindRecArgs *r = nullptr, const FindClsTable *ct = nullptr,
-                                              [[maybe_unused]] const FindAltArgs *alt = nullptr)
+                                              [[maybe_unused]] const FindAltArgs *alt = nullptr, [[maybe_unused]] const FindTerms *tm = nullptr)
 {
     static_assert(PAT || !REC, "the records' route is the pattern's");
+    static_assert(NT == 0 || (ALT && REC && NT <= FIND_TERMS_MAX), "the terms' route is the any-of records'");
     static_assert(PAT || !CLS, "the classes' route is the pattern's");
     static_assert(CLS || !ALT, "the alternatives' route is the classes'");
     constexpr uint32_t KEY_WORDS = CLS ? FIND_CLS_WORDS : (PAT ? FIND_PAT_MAX / 4 : 8);      /* the delimiter set lies behind them */
@@ -387,6 +448,7 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
         /* ---- one byte value: every symbol is a 0 bit (decode.hpp); the chunk's bits are seen to be 0 ---- */
         if (blen > v.pay_bits) return find_raise(a, b, threadIdx.x == 0);
         bool match;
+        [[maybe_unused]] bool tmatch[NT ? NT : 1];                  /* NT: ... of at least one alternative of term t */
         uint32_t plen = 1;
         if constexpr (PAT) {
             /* the pattern is plen copies of the leaf, or it starts nowhere in this block; as for other blocks only
@@ -401,6 +463,10 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
                 uint32_t lo = 0, hi = 0;
                 for (uint32_t k = 0; k < plen; k++) find_cls_step(lo, hi, s_set, ct->first[0], ct->first[1], (uint32_t)leaf);
                 match = ((hi & alt->starts[1]) | (lo & alt->starts[0])) != 0u;
+                if constexpr (NT != 0) {
+#pragma unroll
+                    for (uint32_t k = 0; k < NT; k++) tmatch[k] = ((hi & tm->starts[k][1]) | (lo & tm->starts[k][0])) != 0u;
+                }
             } else if constexpr (CLS) {                             /* ... the leaf is in every class, or there is no start */
                 match = (s_set[2u * (uint32_t)leaf] & ct->full[0]) == ct->full[0] && (s_set[2u * (uint32_t)leaf + 1u] & ct->full[1]) == ct->full[1];
             } else {
@@ -423,11 +489,23 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
                 const uint64_t tend = dmin<uint64_t>(blen, (g / 64u + 1u) * HUF_SUB_TILE), s0 = 32ull * g + plen;
                 nsym = s0 > tend ? 0u : (uint32_t)dmin<uint64_t>(DSUB_SPL, tend - s0 + 1u);
             }
-            row[g] = match ? find_low_bits(nsym) : 0u;
+            if constexpr (NT != 0) {
+#pragma unroll
+                for (uint32_t k = 0; k < NT; k++)
+                    tm->mbits[k * tm->nwords + b * a.wpb + g] = tmatch[k] ? find_low_bits(nsym) : 0u;
+            } else {
+                row[g] = match ? find_low_bits(nsym) : 0u;
+            }
         }
         for (uint64_t t = sym0 / HUF_SUB_TILE + threadIdx.x; t * HUF_SUB_TILE < sym1; t += FIND_THREADS) {
             const uint32_t tsym = find_tile_syms(blen, t);
-            trow[t] = match ? (tsym >= plen ? tsym - plen + 1u : 0u) : 0u;
+            if constexpr (NT != 0) {
+#pragma unroll
+                for (uint32_t k = 0; k < NT; k++)
+                    tm->mcnt[k * a.ntiles + b * a.tpb + t] = tmatch[k] ? (tsym >= plen ? tsym - plen + 1u : 0u) : 0u;
+            } else {
+                trow[t] = match ? (tsym >= plen ? tsym - plen + 1u : 0u) : 0u;
+            }
             if constexpr (REC) r->dcnt[b * a.tpb + t] = delim ? tsym : 0u;
         }
         if constexpr (PAT) {                                        /* the tiles' edges: the leaf */
@@ -463,9 +541,11 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
         const uint4 hi4 = *reinterpret_cast<const uint4 *>(tile_words + 8u * lane + 4u);
         const uint32_t w[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
         uint32_t m = 0;
+        [[maybe_unused]] uint32_t mt[NT ? NT : 1];
         if constexpr (PAT) {
             const uint32_t tsym = find_tile_syms(blen, t), plen = p->plen;
-            if constexpr (ALT) m = find_cls_lane<true>(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane, alt->starts[0], alt->starts[1]);
+            if constexpr (NT != 0) find_term_lane<NT>(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane, *tm, mt);
+            else if constexpr (ALT) m = find_cls_lane<true>(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane, alt->starts[0], alt->starts[1]);
             else if constexpr (CLS) m = find_cls_lane(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane);
             else m = find_pat_lane(tile_words, w, s_set, plen, tsym, lane);         /* (0 for a lane without symbols) */
             /* the edges: the tile's first and last min(tsym, plen - 1) bytes */
@@ -504,9 +584,18 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
             }
             m = nsym == 0u ? 0u : (nsym < 32u ? m & ((1u << nsym) - 1u) : m);    /* (bytes behind a short group are stale) */
         }
-        if (nsym != 0u) row[t * 64u + lane] = m;
-        const uint32_t cnt = wave_total_u32((uint32_t)__popc(m));
-        if (lane == 0) trow[t] = cnt;
+        if constexpr (NT != 0) {
+#pragma unroll
+            for (uint32_t k = 0; k < NT; k++) {
+                if (nsym != 0u) tm->mbits[k * tm->nwords + b * a.wpb + t * 64u + lane] = mt[k];
+                const uint32_t cnt = wave_total_u32((uint32_t)__popc(mt[k]));
+                if (lane == 0) tm->mcnt[k * a.ntiles + b * a.tpb + t] = cnt;
+            }
+        } else {
+            if (nsym != 0u) row[t * 64u + lane] = m;
+            const uint32_t cnt = wave_total_u32((uint32_t)__popc(m));
+            if (lane == 0) trow[t] = cnt;
+        }
     }
     find_raise(a, b, !good && lane == 0);
 }
@@ -518,6 +607,12 @@ __global__ __launch_bounds__(FIND_THREADS) void find_cls_sub_kernel(FindClsArgs 
 __global__ __launch_bounds__(FIND_THREADS) void find_rec_cls_sub_kernel(FindClsArgs a) { find_sub_body<true, true, true>(a.r.p.f, &a.r.p, &a.r, &a.t); }
 __global__ __launch_bounds__(FIND_THREADS) void find_alt_sub_kernel(FindAltArgs a) { find_sub_body<true, false, true, true>(a.r.p.f, &a.r.p, nullptr, &a.t, &a); }
 __global__ __launch_bounds__(FIND_THREADS) void find_rec_alt_sub_kernel(FindAltArgs a) { find_sub_body<true, true, true, true>(a.r.p.f, &a.r.p, &a.r, &a.t, &a); }
+/* hufgpu_find_records_terms with two terms or more: NT is the call's n_terms, a kernel each */
+template <uint32_t NT>
+__global__ __launch_bounds__(FIND_THREADS) void find_rec_term_sub_kernel(FindTermArgs ta)
+{
+    find_sub_body<true, true, true, true, NT>(ta.a.r.p.f, &ta.a.r.p, &ta.a.r, &ta.a.t, &ta.a, &ta.t);
+}
 
 /* ---- the seams: the matches that leave their tile (launched for plen >= 2 only) ---------------------------------------- */
 
@@ -660,6 +755,38 @@ __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_alt_seam_kernel(FindAl
  * an alternative whose boundary position would be the byte AT raw_size is asked for without it (len_j >= 1 positions are
  * left).  Every other start is find_alt_seam_kernel's word for word. */
 __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_anc_seam_kernel(FindAltArgs aa) { find_alt_seam_body<true>(aa); }
+
+/* hufgpu_find_records_terms: find_alt_seam_kernel with a hit a TERM.  A lane goes through the alternatives as there, each
+ * with its own seam rule, and an alternative is asked for until ITS term has a hit at the lane's start; then find_seam_end
+ * once a term, into that term's mask words and counts. */
+__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_term_seam_kernel(FindTermArgs ta)
+{
+    __shared__ uint32_t s_key[FIND_CLS_WORDS];
+    __shared__ uint32_t s_hl[FIND_PAT_MAX];
+    const FindAltArgs &aa = ta.a;
+    const FindPatArgs &pa = aa.r.p;
+    if (threadIdx.x < FIND_PAT_MAX) s_hl[threadIdx.x] = aa.hl[threadIdx.x];
+    find_seam_key<true>(pa, &aa.t, s_key);
+    const uint64_t i = find_tile_index<FIND_SEAM_THREADS>();
+    if (i >= pa.f.ntiles) return;
+    const FindTile tl = find_tile(pa.f, i);
+    if (tl.t * HUF_SUB_TILE >= tl.blen || pa.f.errs[tl.b] != HUFE_OK) return;
+    const FindSeam m = find_seam_lane(pa, i, tl);
+    const uint32_t at = m.lane < m.ne ? pa.edges[m.i * FIND_EDGE_SLOT + 64u + m.lane] : 0u;     /* the byte AT the start, read once */
+    const uint32_t m0 = s_key[2u * at], m1 = s_key[2u * at + 1u];
+    uint32_t hits = 0;                                              /* bit t: an alternative of term t lies at the lane's start */
+    for (uint32_t j = 0; j < aa.n_alts; j++) {
+        const uint32_t hl = uni32(s_hl[j]), hi = hl & 63u, term = (hl >> 6) & 3u;
+        if (m.lane < m.ne && ((hits >> term) & 1u) == 0u && ((((hi >> 5) ? m1 : m0) >> (hi & 31u)) & 1u) != 0u)
+            hits |= (uint32_t)find_seam_candidate<true>(pa, s_key, m, hl >> 8, hi) << term;
+    }
+    for (uint32_t t = 0; t < ta.t.n_terms; t++) {
+        FindArgs f = pa.f;
+        f.bitmap = ta.t.mbits + t * ta.t.nwords;
+        f.tcnt = ta.t.mcnt + t * pa.f.ntiles;
+        find_seam_end(f, m, ((hits >> t) & 1u) != 0u);
+    }
+}
 
 /* The anchored calls with HUFGPU_ANCHOR_BOL or HUFGPU_ANCHOR_WORD, behind the seam kernel and in front of everything that
  * reads the match mask: a wave = one tile, a lane = one word.  `bound` is a mask of the walk's, a bit a byte: may this byte
@@ -959,6 +1086,148 @@ __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_mark_kernel(FindRe
     }
     const uint32_t cnt = wave_total_u32(fresh);
     if (lane == 0 && cnt != 0u) atomicAdd(&ra.rcnt[i], cnt);
+}
+
+/* ---- hufgpu_find_records_terms: the records that hold ALL of several terms, or all of them in order ---------------------- */
+
+/* Behind find_rec_mark_kernel, which has run once a term into that term's record mask: a wave = one tile, a lane = one word.
+ * A record holds every term when its start is set in every term's mask, and mark sets a record's bit in the tile of its
+ * START wherever the match lies, so the AND is local to the tile.  Plain stores into r.rbits / r.rcnt, which nobody has
+ * written before: afterwards they are what mark alone leaves for the older calls, for every word and count that a later
+ * kernel reads.  A tile of a block that is not served reports nothing. */
+struct FindAllArgs {
+    FindRecArgs r;
+    FindTerms t;
+};
+__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_all_kernel(FindAllArgs aa)
+{
+    const FindRecArgs &ra = aa.r;
+    const FindArgs &a = ra.p.f;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t i = find_tile_index<FIND_EMIT_THREADS>();
+    if (i >= a.ntiles) return;
+    const auto [b, t, blen] = find_tile(a, i);
+    if (t * HUF_SUB_TILE >= blen) return;
+    const uint64_t g = t * 64u + lane;
+    const bool inside = g * DSUB_SPL < blen;
+    bool some = a.errs[b] == HUFE_OK;                               /* does every term have a record that starts in this tile (the wave's) */
+    for (uint32_t k = 0; some && k < aa.t.n_terms; k++) some = aa.t.rcnt[k * a.ntiles + i] != 0u;
+    uint32_t r = some && inside ? 0xffffffffu : 0u;
+    for (uint32_t k = 0; some && k < aa.t.n_terms; k++) r &= inside ? aa.t.rbits[k * aa.t.nwords + b * a.wpb + g] : 0u;
+    if (inside) ra.rbits[b * a.wpb + g] = r;
+    const uint32_t cnt = wave_total_u32((uint32_t)__popc(r));
+    if (lane == 0) ra.rcnt[i] = cnt;
+}
+
+/* HUFGPU_TERMS_ORDERED, behind find_rec_all_kernel: of the records that hold every term, those that hold them one behind
+ * the other.  All alternatives of a term have one length, so a term's leftmost occurrence is the one that ends first, and
+ * the greedy walk is exact: x = the record's start, then for every term in turn p = the first match start of the term in
+ * [x, e) - none: the record's bit is cleared - and x = p + the term's length.  A match lies inside one record, so p < e says
+ * that all of it does.  tscan[t] is find_scan_kernel's scan of term t's gated tile counts, with totals of its own. */
+struct FindSeqArgs {
+    FindRecArgs r;
+    FindTerms t;
+    TwoLevel tscan[FIND_TERMS_MAX];
+};
+
+/* Called by a full wave, every lane with the same t, x and e, x < e, both in one record whose extent is known (so every block
+ * that [x, e) touches is served, and the term's mask is complete there): the first match start p of term t at or behind x.
+ * The 64 words of the tile that holds x; when they have none, ONE look-up in the scanned counts for the first tile behind it
+ * that has a match - O(log tiles) reads however far away it is - and a bit scan of that tile.  false: none below e. */
+__device__ __forceinline__ bool find_seq_first(const FindSeqArgs &sa, uint32_t t, uint64_t x, uint64_t e, uint32_t lane, uint64_t &p)
+{
+    const FindArgs &a = sa.r.p.f;
+    const uint32_t *mw = sa.t.mbits + t * sa.t.nwords;
+    uint64_t jb = x / a.s.bsize;
+    const uint64_t rel = x - jb * a.s.bsize;
+    uint64_t jt = rel / HUF_SUB_TILE;
+    const uint64_t g = jt * 64u + lane;
+    uint32_t w = g * DSUB_SPL < find_block_len(a, jb) ? mw[jb * a.wpb + g] : 0u;
+    const uint32_t xw = (uint32_t)(rel >> 5) & 63u;                 /* x's word in its tile: nothing below x counts */
+    if (lane < xw) w = 0u;
+    else if (lane == xw) w &= ~find_low_bits((uint32_t)rel & 31u);
+    uint64_t nz = __ballot(w != 0u);
+    if (nz == 0) {
+        const TwoLevel &sc = sa.tscan[t];
+        const uint64_t i = jb * a.tpb + jt;
+        const auto pre = [&](uint64_t k) { return k < a.ntiles ? two_level_prefix(sc, k) : *sc.total; };
+        const uint64_t c = pre(i + 1);
+        if (c == pre(a.ntiles)) return false;
+        uint64_t lo = i + 1, hi = a.ntiles - 1;                     /* the first j > i with pre(j + 1) > c */
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (pre(mid + 1) > c) hi = mid;
+            else lo = mid + 1;
+        }
+        const uint32_t j = uni32((uint32_t)lo);                     /* (a tile of a served block: the scan counts no other) */
+        jb = j / (uint32_t)a.tpb;
+        jt = j % (uint32_t)a.tpb;
+        const uint64_t gj = jt * 64u + lane;
+        w = gj * DSUB_SPL < find_block_len(a, jb) ? mw[jb * a.wpb + gj] : 0u;
+        nz = __ballot(w != 0u);
+        if (nz == 0) return false;                                  /* (cannot be: the tile's count is that of its words) */
+    }
+    const uint32_t first = uni32((uint32_t)__builtin_ctzll(nz));
+    p = jb * a.s.bsize + jt * HUF_SUB_TILE + 32u * first + (uint32_t)__builtin_ctz(wave_lane_u32(w, first));
+    return p < e;
+}
+
+/* A wave = one tile, a lane = one word of record starts.  A record that ends inside the tile - every one but the tile's last,
+ * when no delimiter lies behind that one's start - is its lane's own: the lane reads the terms' words of the tile, from x's
+ * word to e's at most.  The tile's last record is the wave's: its end comes from find_rec_emit_body's look-up, and every
+ * term costs find_seq_first, so the cost does not follow the record's length.  Plain stores over find_rec_all_kernel's words
+ * (a record's bit lies in the tile of its start: no other wave reads or writes them here), then the tile's count anew. */
+__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_rec_seq_kernel(FindSeqArgs sa)
+{
+    const FindRecArgs &ra = sa.r;
+    const FindArgs &a = ra.p.f;
+    const uint32_t lane = (uint32_t)lane_id(), nt = sa.t.n_terms;
+    const uint64_t i = find_tile_index<FIND_EMIT_THREADS>();
+    if (i >= a.ntiles) return;
+    const auto [b, t, blen] = find_tile(a, i);
+    if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK || ra.rcnt[i] == 0u) return;
+    const uint64_t g = t * 64u + lane, wbase = b * a.wpb + t * 64u;
+    const uint32_t r = g * DSUB_SPL < blen ? ra.rbits[b * a.wpb + g] : 0u;
+    const uint32_t d = find_rec_dword(ra, b, t, lane);
+    const FindRecLane k = find_rec_lane(d, lane);
+    /* two starts of a tile have a delimiter between them, so at most one start of the tile has none behind it */
+    const uint32_t tail = k.next < 0 ? r & k.tail : 0u;
+    uint32_t keep = r, rr = r & ~tail;
+    while (rr != 0u) {
+        const uint32_t bit = (uint32_t)__builtin_ctz(rr);
+        rr &= rr - 1u;
+        const uint32_t du = (d >> bit) << bit;
+        const uint32_t e = du != 0u ? 32u * lane + (uint32_t)__builtin_ctz(du) : (uint32_t)k.next;      /* in the tile; x < e: the record holds a match */
+        uint32_t x = 32u * lane + bit;
+        bool ok = true;
+        for (uint32_t q = 0; ok && q < nt; q++) {
+            const uint32_t *mw = sa.t.mbits + q * sa.t.nwords + wbase;
+            const uint32_t last = (e - 1u) >> 5;
+            uint32_t wi = x >> 5, w = mw[wi] & ~find_low_bits(x & 31u);
+            while (w == 0u && wi < last) w = mw[++wi];
+            const uint32_t p = 32u * wi + (w != 0u ? (uint32_t)__builtin_ctz(w) : 32u);
+            x = p + sa.t.len[q];
+            ok = p < e && (q + 1u == nt || x < e);
+        }
+        if (!ok) keep &= ~(1u << bit);
+    }
+    const uint64_t has_tail = __ballot(tail != 0u);
+    if (has_tail != 0) {
+        const uint32_t at = uni32((uint32_t)__builtin_ctzll(has_tail));
+        const uint32_t bit = (uint32_t)__builtin_ctz(wave_lane_u32(tail, at));
+        const uint64_t e = find_rec_end_behind(ra, i, lane);        /* (known: mark has dropped the records whose end is not) */
+        uint64_t x = b * a.s.bsize + t * HUF_SUB_TILE + 32u * at + bit;
+        bool ok = e != FIND_REC_OPEN;
+        for (uint32_t q = 0; ok && q < nt; q++) {
+            uint64_t p = 0;
+            ok = x < e && find_seq_first(sa, q, x, e, lane, p);
+            x = p + sa.t.len[q];
+        }
+        if (!ok && lane == at) keep &= ~(1u << bit);
+    }
+    if (keep != r) ra.rbits[b * a.wpb + g] = keep;
+    const uint32_t cnt = wave_total_u32((uint32_t)__popc(keep));
+    if (lane == 0) ra.rcnt[i] = cnt;
 }
 
 /* hufgpu_find_records_select: the records' route with two more answers.  r is the any-of call's; no is d_rec_no, or NULL;
