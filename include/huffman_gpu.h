@@ -706,7 +706,7 @@ int hufgpu_find_records_context(hufgpu_ctx_t *ctx, const void *d_stream, uint64_
  * which grows two workspaces more; every other form stays at one walk.  Measured in DESIGN.md 5.21.
  *
  * OUT OF SCOPE: anchors per alternative ('^foo|bar$': make two calls, or one without anchors and look), patterns of
- * variable length, and \b INSIDE a pattern.
+ * variable length (hufgpu_find_any_quant() has them, without anchors), and \b INSIDE a pattern.
  */
 #define HUFGPU_ANCHOR_BOL   1u   /* '^' : the match starts where a record starts */
 #define HUFGPU_ANCHOR_EOL   2u   /* '$' : the match ends where a record ends     */
@@ -794,6 +794,64 @@ int hufgpu_find_records_terms(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t 
                               const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
                               const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
                               const uint32_t *term_alts, uint32_t n_terms, uint32_t terms_mode,
+                              uint32_t select, uint32_t before, uint32_t after,
+                              uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no, uint8_t *d_rec_sel, uint64_t rec_cap, uint32_t max_len,
+                              uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                              uint32_t flags, void *stream);
+
+/*
+ * FIND, OPTIONAL AND REPEATED POSITIONS: grep -E 'colou?r', 'https?://', 'took [0-9]{1,5}ms',
+ * '[0-9]{1,3}\.[0-9]{1,3}\.[0-9]{1,3}\.[0-9]{1,3}'.  hufgpu_find_any_quant() is hufgpu_find_any() and
+ * hufgpu_find_records_quant() is hufgpu_find_records_context() - their contracts hold word for word: d_sub_index (the caller
+ * vouches for NOTHING), every output, cap and total, `select`, d_rec_no, before / after, d_rec_sel, the known-extent rule,
+ * one-symbol blocks served, flags, batch geometry, nblocks = 0, enqueue-only without a host write or a wait, every argument
+ * error (worded "find_any_quant: ..." / "find_records_quant: ...") in the older call's order - but for what a pattern is.
+ * There is no CPU path.
+ *
+ *   optional      : a HOST array of one byte a position, in the order of `classes` (alt_lens sums to its length), read
+ *                   before the call returns: 0 - the position is required -, or 1 - it may be left out.  NULL: all 0.
+ *   a form        : an alternative with some - none, all - of its optional positions dropped.  An alternative stands for
+ *                   ALL its forms: "colo" "u"? "r" for "color" and "colour".  x{m,n} is m required positions and n - m
+ *                   optional ones of one class.
+ *   a match       : a start p at which at least one form of at least one alternative lies as hufgpu_find_any() defines
+ *                   that for an alternative of the form's classes: p + len <= raw_size, data[p + k] in the form's class k,
+ *                   and every block that [p, p + len) touches is served.  Each form has its own span, hufgpu_find_any()'s
+ *                   "own seam rule" stated for forms: a longer form that reaches into a block which is not served does
+ *                   not take a shorter form's start away.  As a shorter span touches no more blocks, the SHORTEST form that
+ *                   lies at p decides.  A start is reported once, ascending, however many forms lie there.
+ *   alt_lens      : still sums to at most HUFGPU_FIND_PATTERN_MAX: a position takes one bit of the matcher's state
+ *                   whether it is optional or not.  So no match is longer than 64 bytes.
+ *   records       : no class may hold a delimiter, so every form lies inside one record; a record is selected when it
+ *                   holds a match, and from there on everything is hufgpu_find_records_context()'s.
+ *
+ * Found on the host, before anything is enqueued and before the context is looked at, behind the older call's checks of
+ * `select`, n_alts, the lengths and the classes and in front of its other checks, and HUF_ERROR_INVALID_ARGUMENT:
+ *
+ *   - an `optional` byte above 1 (the message names the alternative, the position and the value);
+ *   - an alternative whose positions are all optional: it would match everywhere (the message names the alternative).
+ *
+ * The identity: with optional == NULL or all zeros the calls enqueue exactly what hufgpu_find_any() /
+ * hufgpu_find_records_context() enqueue for the same arguments, and the twelve older calls launch what they always did.
+ * With an optional position the walk and the seam kernel are two of their own - the same Shift-And automaton with one 64-bit
+ * subtraction and four logic operations a byte more (Navarro and Raffinot's extended patterns) - and everything behind them
+ * runs as it is; the workspace is that of an any-of call whose longest alternative has as many positions.  DESIGN.md 5.23.
+ *
+ * OUT OF SCOPE: anchors together with optional positions; optional positions inside hufgpu_find_records_terms();
+ * unbounded repeats ('*', '+', '{m,}': they need state carried from tile to tile) and groups ('(ab)?'); and which form
+ * matched, so where a match ends.
+ */
+int hufgpu_find_any_quant(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                          const uint64_t *d_block_offsets, uint64_t nblocks,
+                          const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                          const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts, const uint8_t *optional,
+                          uint64_t *d_pos, uint64_t pos_cap,
+                          uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                          uint32_t flags, void *stream);
+int hufgpu_find_records_quant(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                              const uint64_t *d_block_offsets, uint64_t nblocks,
+                              const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                              const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                              const uint8_t *optional,
                               uint32_t select, uint32_t before, uint32_t after,
                               uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no, uint8_t *d_rec_sel, uint64_t rec_cap, uint32_t max_len,
                               uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,

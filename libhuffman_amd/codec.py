@@ -468,6 +468,29 @@ class GpuCodec:
         def __repr__(self):
             return "AnyOf(" + ", ".join(repr(a) for a in self.alternatives) + ")"
 
+    class Opt:
+        """An item of a `list` / `tuple` pattern or of an AnyOf alternative: a position that may be left out (grep -E 'x?').
+        `cls` is what a position of byte_classes is: an int, a `bytes` of the allowed values or an iterable of ints.
+        list(b"colo") + [GpuCodec.Opt(b"u"), ord("r")] is 'colou?r' (hufgpu_find_any_quant)."""
+        __slots__ = ("cls",)
+
+        def __init__(self, cls):
+            self.cls = cls
+
+        def __repr__(self):
+            return f"Opt({self.cls!r})"
+
+    class Rep:
+        """An item as Opt: `lo` to `hi` copies of one position (grep -E 'x{lo,hi}'), that is `lo` required positions and
+        `hi - lo` optional ones of the class `cls`.  Every copy takes one of the FIND_PATTERN_MAX positions."""
+        __slots__ = ("cls", "lo", "hi")
+
+        def __init__(self, cls, lo, hi):
+            self.cls, self.lo, self.hi = cls, int(lo), int(hi)
+
+        def __repr__(self):
+            return f"Rep({self.cls!r}, {self.lo}, {self.hi})"
+
     class _Terms:
         """What AllOf and Seq share: 1 to FIND_TERMS_MAX items, each a bytes-like literal, a list / tuple of classes or an
         AnyOf - one TERM of hufgpu_find_records_terms."""
@@ -514,6 +537,8 @@ class GpuCodec:
             if isinstance(item, GpuCodec._Terms):
                 raise TypeError(f"item {t} of {name} is {type(item).__name__}: AllOf and Seq do not nest")
             alts = list(item) if isinstance(item, GpuCodec.AnyOf) else [item]
+            if GpuCodec._is_quant(GpuCodec.AnyOf(*alts)):
+                raise ValueError(f"item {t} of {name} holds an Opt or a Rep: a pattern with optional positions has one term")
             if not alts:
                 raise ValueError(f"item {t} of {name} has no alternative: no record would hold it")
             if isinstance(pattern, GpuCodec.Seq) and len({len(a) for a in alts if not isinstance(a, str)}) > 1:
@@ -551,12 +576,209 @@ class GpuCodec:
             raise ValueError(f"the alternatives' lengths sum to {total}, above {_native.FIND_PATTERN_MAX}")
         return np.concatenate(rows), np.array([len(r) for r in rows], np.uint32)
 
+    @staticmethod
+    def _is_quant(pattern) -> bool:
+        """does a pattern - a list / tuple, or an AnyOf of such - hold an Opt or a Rep"""
+        alts = pattern if isinstance(pattern, GpuCodec.AnyOf) else (pattern,)
+        return any(isinstance(a, (list, tuple)) and any(isinstance(c, (GpuCodec.Opt, GpuCodec.Rep)) for c in a) for a in alts)
+
+    @staticmethod
+    def quant_classes(pattern, ignore_case: bool = False):
+        """The three host arrays of hufgpu_find_any_quant for a pattern with Opt / Rep items - a list / tuple, or an AnyOf
+        of alternatives -: (classes uint8 [total][32], alt_lens uint32 [n], optional uint8 [total]), a Rep written out as
+        its `lo` required and `hi - lo` optional positions.  `ignore_case` applies to every class.  Raises ValueError for what
+        alt_classes raises it for - the lengths count every copy of a Rep -, for a Rep with lo < 0, lo > hi or hi = 0 and
+        for an alternative whose positions are all optional; the message names the alternative and the item."""
+        if not isinstance(pattern, GpuCodec.AnyOf):
+            if isinstance(pattern, (str, GpuCodec._Terms)):
+                raise TypeError(f"a pattern is a bytes-like object, a list / tuple of classes or an AnyOf, not a {type(pattern).__name__}")
+            pattern = GpuCodec.AnyOf(pattern)
+        flat, flags = [], []
+        for j, alt in enumerate(pattern):
+            items, opt = [], []
+            for k, c in enumerate(alt if isinstance(alt, (list, tuple)) else ()):
+                if isinstance(c, GpuCodec.Rep):
+                    if c.lo < 0 or c.lo > c.hi:
+                        raise ValueError(f"alternative {j}, item {k}: Rep from {c.lo} to {c.hi} copies: 0 <= lo <= hi")
+                    if c.hi == 0:
+                        raise ValueError(f"alternative {j}, item {k}: Rep of at most 0 copies: leave the item out")
+                    items += [c.cls] * c.hi
+                    opt += [0] * c.lo + [1] * (c.hi - c.lo)
+                else:
+                    items.append(c.cls if isinstance(c, GpuCodec.Opt) else c)
+                    opt.append(int(isinstance(c, GpuCodec.Opt)))
+                if len(items) > _native.FIND_PATTERN_MAX:
+                    raise ValueError(f"alternative {j}, item {k}: the positions come to {len(items)}, above {_native.FIND_PATTERN_MAX}")
+            if not isinstance(alt, (list, tuple)):
+                items, opt = alt, [0] * len(alt)                    # (a literal; alt_classes words a str)
+            elif items and all(opt):
+                raise ValueError(f"alternative {j}: every position is optional: it would match everywhere")
+            flat.append(items)
+            flags += opt
+        classes, lens = GpuCodec.alt_classes(GpuCodec.AnyOf(*flat), ignore_case)
+        return classes, lens, np.array(flags, np.uint8)
+
+    _REGEX_SETS = {ord("d"): b"0123456789", ord("w"): b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789_",
+                   ord("s"): b" \t\n\r\f\v"}
+    _REGEX_CHARS = {ord("n"): 10, ord("t"): 9, ord("r"): 13, ord("f"): 12, ord("v"): 11}
+    _REGEX_META = b"\\.[]{}()*+?|^$-/"
+
+    @staticmethod
+    def regex(expr: bytes, delimiters=b"\n", ignore_case: bool = False):
+        """A subset of grep -E, compiled on the host to the pattern that find_pattern / find_records / grep take: an AnyOf of
+        lists with Opt / Rep items, one alternative a top-level '|'.  Taken: literal bytes; '\\' in front of a metacharacter;
+        \\n \\t \\r \\f \\v \\xHH; \\d \\w \\s and \\D \\W \\S; '.'; '[...]' with ranges, a leading '^' and the escapes above (a ']'
+        right behind the '[' or '[^' is a member); and behind a single position '?', '{m}', '{m,n}' and '{,n}'.  '.', a negated
+        set and \\D \\W \\S never hold one of `delimiters`, as a line of grep never holds a newline.  `ignore_case` adds the
+        other case of every ASCII letter of every class, in front of a set's negation.  Every position, a repeat's every copy, takes one of the
+        FIND_PATTERN_MAX positions that the alternatives share.
+        Raises ValueError, naming the offset in `expr`, for '*', '+' and '{m,}' (unbounded: not in this matcher), for '(' and
+        ')' (no groups), '^' and '$' (the `bol` / `eol` keywords anchor a pattern without repeats), a quantifier with nothing
+        to repeat, a bad '{...}', a bad range or escape, a set without its ']', an empty alternative or class, a repeat of at
+        most 0 copies, and a total above FIND_PATTERN_MAX positions."""
+        expr = bytes(expr)
+        delims = set(bytes(delimiters) if isinstance(delimiters, (bytes, bytearray)) else [int(v) for v in delimiters])
+        n = len(expr)
+
+        def bad(at, why):
+            return ValueError(f"regex: offset {at}: {why}")
+
+        def fold(values):
+            return set(values) | ({v ^ 0x20 for v in values if 0x41 <= (v & ~0x20) <= 0x5a and v < 128} if ignore_case else set())
+
+        def negated(values):
+            return set(range(256)) - fold(values) - delims
+
+        def escape(at, in_set):
+            """the class of the escape whose '\\' stands at `at`, and the offset behind it"""
+            if at + 1 >= n:
+                raise bad(at, "a '\\' at the end")
+            c = expr[at + 1]
+            if c in GpuCodec._REGEX_SETS:
+                return set(GpuCodec._REGEX_SETS[c]), at + 2
+            if c in b"DWS":
+                if in_set:
+                    raise bad(at, f"'\\{chr(c)}' inside a set")
+                return negated(GpuCodec._REGEX_SETS[c | 0x20]), at + 2
+            if c in GpuCodec._REGEX_CHARS:
+                return {GpuCodec._REGEX_CHARS[c]}, at + 2
+            if c == ord("x"):
+                digits = expr[at + 2:at + 4]
+                if len(digits) != 2 or any(d not in b"0123456789abcdefABCDEF" for d in digits):
+                    raise bad(at, "'\\x' needs two hex digits")
+                return {int(digits, 16)}, at + 4
+            if c in GpuCodec._REGEX_META:
+                return {c}, at + 2
+            raise bad(at, f"the escape '\\{chr(c)}' is not in this subset")
+
+        def bracket(at):
+            """the class of the set whose '[' stands at `at`, and the offset behind its ']'"""
+            i = at + 1
+            neg = i < n and expr[i] == ord("^")
+            i += neg
+            values, first = set(), True
+            while True:
+                if i >= n:
+                    raise bad(at, "a '[' without its ']'")
+                if expr[i] == ord("]") and not first:
+                    break
+                first = False
+                single = True
+                if expr[i] == ord("\\"):
+                    lo, j = escape(i, True)
+                    single = len(lo) == 1 and expr[i + 1] not in GpuCodec._REGEX_SETS
+                else:
+                    lo, j = {expr[i]}, i + 1
+                if j + 1 < n and expr[j] == ord("-") and expr[j + 1] != ord("]"):
+                    if expr[j + 1] == ord("\\"):
+                        hi, k = escape(j + 1, True)
+                        hi_single = len(hi) == 1 and expr[j + 2] not in GpuCodec._REGEX_SETS
+                    else:
+                        hi, k, hi_single = {expr[j + 1]}, j + 2, True
+                    a, b = min(lo), min(hi)
+                    if not single or not hi_single or a > b:
+                        raise bad(i, "a bad range")
+                    lo, j = set(range(a, b + 1)), k
+                values |= lo
+                i = j
+            return (negated(values) if neg else values), i + 1
+
+        def repeat(at):
+            """(lo, hi, the offset behind) of the quantifier at `at`, None when there is none"""
+            if at >= n or expr[at] not in b"?*+{":
+                return None
+            if expr[at] == ord("?"):
+                return 0, 1, at + 1
+            if expr[at] != ord("{"):
+                raise bad(at, f"'{chr(expr[at])}' is unbounded: not in this matcher")
+            end = expr.find(b"}", at)
+            body = expr[at + 1:end] if end >= 0 else b""
+            parts = body.split(b",")
+            if end < 0 or len(parts) > 2 or any(p and not p.isdigit() for p in parts) or not any(parts):
+                raise bad(at, "a bad '{...}': {m}, {m,n} or {,n}")
+            if len(parts) == 2 and not parts[1]:
+                raise bad(at, "'{m,}' is unbounded: not in this matcher")
+            lo = int(parts[0] or 0)
+            hi = int(parts[1]) if len(parts) == 2 else lo
+            if lo > hi:
+                raise bad(at, f"a repeat from {lo} to {hi}")
+            if hi == 0:
+                raise bad(at, "a repeat of at most 0 copies")
+            return lo, hi, end + 1
+
+        alts, items, total, i, alt_at = [], [], 0, 0, 0
+        while True:
+            if i >= n or expr[i] == ord("|"):
+                if not items:
+                    raise bad(alt_at, "an empty alternative: it would match everywhere")
+                if all(isinstance(c, GpuCodec.Opt) or (isinstance(c, GpuCodec.Rep) and c.lo == 0) for c in items):
+                    raise bad(alt_at, "every position of the alternative is optional: it would match everywhere")
+                alts.append(items)
+                if i >= n:
+                    break
+                items, i = [], i + 1
+                alt_at = i
+                continue
+            at, c = i, expr[i]
+            if c in b"?*+{":
+                raise bad(at, f"'{chr(c)}' has nothing to repeat")
+            if c in b"()":
+                raise bad(at, f"'{chr(c)}': groups are not in this matcher")
+            if c in b"^$":
+                raise bad(at, f"'{chr(c)}': anchors are keywords of the calls (bol, eol), not part of the expression")
+            if c == ord("\\"):
+                values, i = escape(at, False)
+            elif c == ord("["):
+                values, i = bracket(at)
+            elif c == ord("."):
+                values, i = negated(()), at + 1
+            else:
+                values, i = {c}, at + 1
+            values = fold(values)
+            if not values:
+                raise bad(at, "an empty class: it matches nothing")
+            cls = bytes(sorted(values))
+            rep = repeat(i)
+            copies = 1
+            if rep is None:
+                items.append(cls)
+            else:
+                lo, copies, i = rep
+                if i < n and expr[i] in b"?*+{":
+                    raise bad(i, f"'{chr(expr[i])}' behind a quantifier has nothing to repeat")
+                items.append(GpuCodec.Opt(cls) if (lo, copies) == (0, 1) else GpuCodec.Rep(cls, lo, copies))
+            total += copies
+            if total > _native.FIND_PATTERN_MAX:
+                raise bad(at, f"the positions come to {total}, above {_native.FIND_PATTERN_MAX}")
+        return GpuCodec.AnyOf(*alts)
+
     _NO_RECORDS = object()          # _find_route's `delimiters` of the calls that have none
 
     # route -> the C call that gives positions, the one that gives records
     _FIND_CALLS = {"literal": ("hufgpu_find_pattern", "hufgpu_find_records"),
                    "classes": ("hufgpu_find_classes", "hufgpu_find_records_classes"),
-                   "any": ("hufgpu_find_any", "hufgpu_find_records_any")}
+                   "any": ("hufgpu_find_any", "hufgpu_find_records_any"),
+                   "quant": ("hufgpu_find_any_quant", "hufgpu_find_records_quant")}
 
     WORD_BYTES = b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789_"     # grep -w's: [A-Za-z0-9_]
 
@@ -578,6 +800,8 @@ class GpuCodec:
             bits = ((_native.ANCHOR_BOL if bol or whole_line else 0) | (_native.ANCHOR_EOL if eol or whole_line else 0) |
                     (_native.ANCHOR_WORD if word else 0))
             ws = GpuCodec.byte_set(GpuCodec.WORD_BYTES if word_bytes is None else word_bytes) if word else None
+            if bits and GpuCodec._is_quant(pattern):
+                raise ValueError("`bol`, `eol`, `whole_line` and `word` do not go with Opt / Rep: an anchored search has no optional positions")
             route, key, st = GpuCodec._find_route(pattern, ignore_case, delimiters, select or bits != 0)
             if bits & (_native.ANCHOR_EOL | _native.ANCHOR_WORD):
                 total = int(np.frombuffer(key[1], np.uint32).sum()) + key[2]
@@ -590,8 +814,10 @@ class GpuCodec:
             if isinstance(pattern, str):
                 raise TypeError("a pattern is a bytes-like object or a list / tuple of classes, not a str")
             pattern = GpuCodec.AnyOf(pattern)
-        alts = classes = None
-        if isinstance(pattern, GpuCodec.AnyOf):
+        alts = classes = optional = None
+        if GpuCodec._is_quant(pattern):
+            *alts, optional = GpuCodec.quant_classes(pattern, ignore_case)
+        elif isinstance(pattern, GpuCodec.AnyOf):
             alts = GpuCodec.alt_classes(pattern, ignore_case)
         elif isinstance(pattern, (list, tuple)) or ignore_case:
             classes = GpuCodec.byte_classes(pattern, ignore_case)      # (raises for a wrong length)
@@ -617,6 +843,8 @@ class GpuCodec:
             raise ValueError(f"{where} holds a delimiter (value {v}): a match lies inside one record")
         if alts is None:
             return "classes", (classes.tobytes(), len(classes)), st
+        if optional is not None:
+            return "quant", (alts[0].tobytes(), alts[1].tobytes(), len(alts[1]), optional.tobytes()), st
         return "any", (alts[0].tobytes(), alts[1].tobytes(), len(alts[1])), st
 
     @staticmethod
@@ -649,6 +877,10 @@ class GpuCodec:
         class k for every k.  A bytes-like pattern without `ignore_case` makes the literal call.
         A GpuCodec.AnyOf pattern looks for SEVERAL alternatives in the one walk (hufgpu_find_any): a start at which at least
         one of them lies is reported once; which one is not reported.  `ignore_case` applies to every alternative.
+        GpuCodec.Opt and GpuCodec.Rep items in a `list` / `tuple` pattern or in an alternative are positions that may be left
+        out or repeated - 'colou?r', '[0-9]{1,3}', GpuCodec.regex() writes them - (hufgpu_find_any_quant): a start is reported
+        once when any way of leaving optional positions out lies there.  They are a ValueError next to `bol`, `eol`,
+        `whole_line` or `word`.
         `bol`, `eol` ('^', '$'), `whole_line` (grep -x: both) and `word` (grep -w) keep the occurrences whose neighbours allow
         it (hufgpu_find_any_anchored): the byte in front is absent or one of `delimiters`, the byte behind is, neither is one
         of `word_bytes` ([A-Za-z0-9_] when not given).  The reported position is still the pattern's own start.  `delimiters`
@@ -703,6 +935,9 @@ class GpuCodec:
         subtract the delimiters from a wide class.
         A GpuCodec.AnyOf pattern reports the records that hold at least one of its alternatives, each record once
         (hufgpu_find_records_any): grep -e A -e B.  No class of any alternative may hold a delimiter.
+        A pattern with GpuCodec.Opt / GpuCodec.Rep items - as find_pattern takes it, as GpuCodec.regex() writes it - makes the
+        call hufgpu_find_records_quant, whatever else is asked for: `invert`, `line_numbers` and the distances apply unchanged;
+        `bol`, `eol`, `whole_line`, `word` next to it and such an item inside an AllOf / Seq are a ValueError.
         `invert` reports the NON-EMPTY records that hold NO match (grep -v, but for the empty lines): a record whose extent
         is known lies in exactly one of the two answers.  `line_numbers` appends one tensor to the returned tuple,
         numbers[max_records] int64: the delimiters in front of each written record, 0-based (grep -n prints it plus 1), -1
@@ -763,6 +998,11 @@ class GpuCodec:
                                                         after, *ptrs, numbers.data_ptr() if line_numbers and max_records else None,
                                                         selected.data_ptr() if widens and max_records else None, max_records, max_len,
                                                         *tail)
+        elif route == "quant":
+            err = self.lib.hufgpu_find_records_quant(*head, st, *key, _native.SELECT_INVERT if invert else 0, before, after, *ptrs,
+                                                     numbers.data_ptr() if line_numbers and max_records else None,
+                                                     selected.data_ptr() if widens and max_records else None, max_records, max_len,
+                                                     *tail)
         elif widens:
             err = self.lib.hufgpu_find_records_context(*head, st, *key, _native.SELECT_INVERT if invert else 0, before, after, *ptrs,
                                                        numbers.data_ptr() if line_numbers and max_records else None,

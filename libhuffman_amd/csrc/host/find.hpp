@@ -3,7 +3,8 @@
    patterns; hufgpu_find_records, hufgpu_find_records_classes, hufgpu_find_records_any and hufgpu_find_records_select give
    the records - the pieces between delimiters - that hold one (or do not), and their numbers; hufgpu_find_records_context
    gives the records around them as well; hufgpu_find_any_anchored and hufgpu_find_records_anchored are hufgpu_find_any and
-   the context call for the matches that begin or end at a record's or a word's edge; hufgpu_find_records_terms is the
+   the context call for the matches that begin or end at a record's or a word's edge; hufgpu_find_any_quant and
+   hufgpu_find_records_quant are those two for patterns with optional positions; hufgpu_find_records_terms is the
    context call for the records that hold all of several terms, or all of them in order.  All enqueue-only.  A
    wrapper describes its call in three structs; find_call checks them (find_check, no HIP call), fills the kernels'
    arguments and grows the workspace (find_fill) and enqueues the chain of kernels/find.hpp (find_enqueue).
@@ -84,7 +85,9 @@ struct FindTermCall {
  * anc is NULL but for the anchored calls with an anchor: then alt's table holds one position more an alternative when
  * the byte behind a match is tested, and find_anchor_kernel runs when the byte in front is.
  * term is NULL but for the terms' call with two terms or more: the walk and the seam kernel then keep a mask a term, and
- * find_rec_mark_kernel runs once a term in front of find_rec_all_kernel (and find_rec_seq_kernel). */
+ * find_rec_mark_kernel runs once a term in front of find_rec_all_kernel (and find_rec_seq_kernel).
+ * opt is NULL but for the quant calls with an optional position: then alt is opt's table, plen the longest alternative's
+ * position count, and the walk and the seam kernel close the state over the optional positions (find_opt_masks). */
 struct FindKey {
     const char *who, *key_name;
     const uint8_t *key;
@@ -96,6 +99,7 @@ struct FindKey {
     const FindCtxCall *cx;
     const FindAncCall *anc;
     FindTermCall *term;
+    FindOptArgs *opt;
 };
 
 /* does the context call widen the answer: with both distances 0 it is the select call, maybe with flags */
@@ -230,6 +234,11 @@ static void find_enqueue_walk(hufgpu_ctx_t *ctx, const FindKey &k, const FindRec
         else if (ta.t.n_terms == 3) find_rec_term_sub_kernel<3><<<walk, wt, 0, s>>>(ta);
         else find_rec_term_sub_kernel<FIND_TERMS_MAX><<<walk, wt, 0, s>>>(ta);
         if (seam) find_term_seam_kernel<<<seams, st, 0, s>>>(ta);
+    } else if (k.opt) {
+        k.opt->a.r = ra;
+        if (rec) find_rec_opt_sub_kernel<<<walk, wt, 0, s>>>(*k.opt);
+        else find_opt_sub_kernel<<<walk, wt, 0, s>>>(*k.opt);
+        if (seam) find_opt_seam_kernel<<<seams, st, 0, s>>>(*k.opt);
     } else if (k.alt) {
         k.alt->r = ra;
         const bool front = find_anc_front(k), third = find_anc_third(k);
@@ -546,19 +555,68 @@ static void find_term_split(FindAltArgs *t, const uint32_t *alt_lens, const uint
     }
 }
 
-/* the seven any-of wrappers' call: the table, when both arrays are there (find_check words a missing one), then find_call */
+/* The quant calls' own checks, behind find_alt_table's: an `optional` byte that is neither 0 nor 1, an alternative whose
+ * positions are all optional.  Then, next to the table that find_alt_table has made in q->a, the three masks of
+ * kernels/find.hpp's FindOpt and the wider `first`; *any: is there an optional position at all - without one the call is
+ * the any-of call.  `optional` has one byte a position, in the order of `classes`. */
+static int find_opt_masks(hufgpu_ctx_t *ctx, const char *who, const uint32_t *alt_lens, uint32_t n_alts, const uint8_t *optional,
+                          FindOptArgs *q, bool *any)
+{
+    const uint8_t *op = optional;
+    for (uint32_t j = 0; j < n_alts; op += alt_lens[j++]) {
+        uint32_t required = 0;
+        for (uint32_t k = 0; k < alt_lens[j]; k++) {
+            if (op[k] > 1)
+                return find_bad(ctx, "%s: optional is %u at position %u of alternative %u: 0 (required) or 1 (may be left out)", who, op[k], k, j);
+            required += op[k] == 0;
+            *any |= op[k] != 0;
+        }
+        if (required == 0)
+            return find_bad(ctx, "%s: every position of alternative %u is optional: it would match everywhere", who, j);
+    }
+    uint64_t first = 0, O = 0, I = 0, F = 0;
+    op = optional;
+    for (uint32_t j = 0; j < n_alts; op += alt_lens[j++]) {
+        const uint32_t hi = q->a.hl[j] & 63u, len = alt_lens[j];
+        uint32_t k = len - 1u;                                      /* the positions that may hold a form's last byte */
+        first |= 1ull << (hi - k);
+        while (op[k]) first |= 1ull << (hi - --k);                  /* (a required position stops it) */
+        for (k = 0; k < len; k++) {
+            if (!op[k]) continue;
+            const uint32_t top = k;
+            while (k + 1u < len && op[k + 1u]) k++;
+            uint32_t low = k;                                       /* the maximal run top ... low */
+            if (low == len - 1u) {                                  /* it ends the alternative: its lowest bit is its i, set by `first` */
+                if (top == low) continue;
+                low--;
+            }
+            for (uint32_t b = top; b <= low; b++) O |= 1ull << (hi - b);
+            I |= 1ull << (hi - low - 1u);
+            F |= 1ull << (hi - top);
+        }
+    }
+    q->a.t.first[0] = (uint32_t)first;
+    q->a.t.first[1] = (uint32_t)(first >> 32);
+    q->q = {{(uint32_t)O, (uint32_t)(O >> 32)}, {(uint32_t)I, (uint32_t)(I >> 32)}, {(uint32_t)F, (uint32_t)(F >> 32)}};
+    return HUFE_OK;
+}
+
+/* the nine any-of wrappers' call: the table, when both arrays are there (find_check words a missing one), then find_call */
 static int find_alt_call(hufgpu_ctx_t *ctx, const char *who, const FindStream &in, const FindOut &out, const uint8_t *classes,
                          const uint32_t *alt_lens, uint32_t n_alts, const FindRecCall *rec, const FindSelCall *sel, const FindCtxCall *cx,
                          uint32_t flags, void *stream, const FindAncCall *anc = NULL, FindTermCall *term = NULL,
-                         const uint32_t *term_alts = NULL)
+                         const uint32_t *term_alts = NULL, const uint8_t *optional = NULL)
 {
-    FindAltArgs t;
+    FindOptArgs q;
+    FindAltArgs &t = q.a;
     uint32_t maxlen = 0;
+    bool quant = false;
     const bool both = classes && alt_lens;
     const uint8_t *behind = anc && (anc->anchors & (HUFGPU_ANCHOR_EOL | HUFGPU_ANCHOR_WORD)) ? anc->behind : NULL;
     if (both && find_alt_table(ctx, who, classes, alt_lens, n_alts, rec ? rec->delim_set : NULL, &t, &maxlen, behind)) return HUFE_ARGUMENT;
     if (both && term) find_term_split(&t, alt_lens, term_alts, term);
-    const FindKey k = {who, "classes, alt_lens", both ? classes : NULL, maxlen, rec, &t.t, &t, sel, cx, anc, term};
+    if (both && optional && find_opt_masks(ctx, who, alt_lens, n_alts, optional, &q, &quant)) return HUFE_ARGUMENT;
+    const FindKey k = {who, "classes, alt_lens", both ? classes : NULL, maxlen, rec, &t.t, &t, sel, cx, anc, term, quant ? &q : NULL};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -616,6 +674,36 @@ extern "C" int hufgpu_find_records_context(hufgpu_ctx_t *ctx, const void *d_stre
     const FindCtxCall cx = {before, after, d_rec_sel};
     const bool plain = (before | after) == 0u && !d_rec_sel;        /* the select call, by its launches */
     return find_alt_call(ctx, "find_records_context", in, out, classes, alt_lens, n_alts, &rec, &sel, plain ? NULL : &cx, flags, stream);
+}
+
+extern "C" int hufgpu_find_any_quant(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                     uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                     const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts, const uint8_t *optional,
+                                     uint64_t *d_pos, uint64_t pos_cap, uint64_t *d_block_counts, uint64_t *d_totals,
+                                     int32_t *d_block_errs, uint32_t flags, void *stream)
+{
+    const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
+    const FindOut out = {d_pos, pos_cap, d_block_counts, d_totals, d_block_errs};
+    return find_alt_call(ctx, "find_any_quant", in, out, classes, alt_lens, n_alts, NULL, NULL, NULL, flags, stream, NULL, NULL, NULL, optional);
+}
+
+extern "C" int hufgpu_find_records_quant(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                         uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                         const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                                         const uint8_t *optional, uint32_t select, uint32_t before, uint32_t after, uint64_t *d_rec_pos,
+                                         uint32_t *d_rec_len, uint64_t *d_rec_no, uint8_t *d_rec_sel, uint64_t rec_cap, uint32_t max_len,
+                                         uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs, uint32_t flags, void *stream)
+{
+    if (select & ~HUFGPU_SELECT_INVERT)
+        return find_bad(ctx, "find_records_quant: select 0x%x has a bit other than HUFGPU_SELECT_INVERT", select);
+    const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
+    const FindOut out = {d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs};
+    const FindRecCall rec = {delim_set, d_rec_len, max_len};
+    const FindSelCall sel = {select, d_rec_no};
+    const FindCtxCall cx = {before, after, d_rec_sel};
+    const bool plain = (before | after) == 0u && !d_rec_sel;        /* the select call, by its launches */
+    return find_alt_call(ctx, "find_records_quant", in, out, classes, alt_lens, n_alts, &rec, &sel, plain ? NULL : &cx, flags, stream, NULL,
+                         NULL, NULL, optional);
 }
 
 /* The anchored calls' own checks, behind the `select` check and in front of the older calls': a bit that is no anchor, BOL or

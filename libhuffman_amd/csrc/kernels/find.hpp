@@ -33,9 +33,14 @@
                                    find_rec_all (the AND of the record masks, into the mask that mark leaves for the other
                                    calls) [-> find_scan once a term (of the terms' match counts, into scans of their own) ->
                                    find_rec_seq: ORDERED only], then the context call's chain from [find_rec_invert] on
+   hufgpu_find_any_quant           no optional position: hufgpu_find_any's chain.  Else find_opt_sub -> find_opt_seam in the
+                                   place of find_alt_sub -> find_alt_seam: the any-of automaton closed over the optional
+                                   positions a byte (find_opt_step); the seam kernel runs it on a window of the edge bytes in LDS
+   hufgpu_find_records_quant       no optional position: the context call's chain.  Else find_rec_opt_sub -> find_opt_seam in
+                                   the place of find_rec_alt_sub -> find_alt_seam, then that chain as it is
    RECORDS = find_rec_dscan -> find_rec_mark -> find_scan -> find_finish [-> find_rec_emit]; no seam kernel for 1 byte
 
-   The walk: find_sub_body, the seven *_sub kernels and find_rec_term_sub_kernel
+   The walk: find_sub_body, the nine *_sub kernels and find_rec_term_sub_kernel
      Workgroup = one (block, chunk of 65 536 symbols), decode_sub_kernel's geometry with eight waves; a wave takes the
      chunk's tiles wave, wave + 8, ...  The header is parsed and its length must be the layout's, the tables come from
      dsub_fast_tables (the claimed code lengths checked against the stream's tree), and EVERY tile of EVERY chunk is the
@@ -328,6 +333,47 @@ __device__ __forceinline__ void find_cls_step(uint32_t &lo, uint32_t &hi, const 
     lo = ((lo << 1) | first_lo) & mv.x;
 }
 
+/* hufgpu_find_any_quant / hufgpu_find_records_quant: some positions of the any-of table are OPTIONAL, so an alternative
+ * stands for all its forms - every way of leaving optional positions out.  The table, `starts` and hl are the any-of call's
+ * (r.p.plen: the longest alternative's POSITION count, the length of its longest form); t.first is wider: the bits of all
+ * positions that may hold a form's LAST byte - an alternative's last position and, while that one is optional, the one in
+ * front of it, up to the first required one.  Three masks describe the maximal runs of optional positions top ... low (top
+ * the higher bit): o has the run's bits, i the bit just below the run (position low + 1), f the bit of top.  A run that
+ * ends its alternative has no position below it: its lowest bit comes in through t.first, is that run's i and is left out
+ * of o.  So no borrow of find_opt_step's subtraction leaves an alternative, and no bits are needed between two of them. */
+struct FindOpt {
+    uint32_t o[2], i[2], f[2];              /* ([0] the low half) */
+};
+struct FindOptArgs {
+    FindAltArgs a;
+    FindOpt q;
+};
+static_assert(sizeof(FindOptArgs) == sizeof(FindAltArgs) + 24 && sizeof(FindOptArgs) <= 4096, "a kernel's arguments end at 4 KiB");
+
+/* find_cls_step and the closure over the optional positions (Navarro and Raffinot's extended patterns): a set bit just
+ * below or inside a run of optional positions sets every bit of the run above it - "those positions are left out".
+ * Df - I clears the lowest set bit of every block i ... f and sets the bits below it, so ~(Df - I) ^ Df has exactly the bits
+ * above that lowest one; f bounds the borrow.  One subtraction with borrow out, one with borrow in, four logic operations a
+ * half; o, i and f are the kernel's arguments, the same for every lane. */
+__device__ __forceinline__ void find_opt_step(uint32_t &lo, uint32_t &hi, const uint32_t *s_m, uint32_t first_lo, uint32_t first_hi, uint32_t x,
+                                              const FindOpt &q)
+{
+    find_cls_step(lo, hi, s_m, first_lo, first_hi, x);
+    const uint32_t dl = lo | q.f[0], dh = hi | q.f[1];
+    const uint64_t d = (((uint64_t)dh << 32) | dl) - (((uint64_t)q.i[1] << 32) | q.i[0]);
+    lo |= q.o[0] & (~(uint32_t)d ^ dl);
+    hi |= q.o[1] & (~(uint32_t)(d >> 32) ^ dh);
+}
+
+/* the automaton's step of a walk: OPT, the one with the closure */
+template <bool OPT>
+__device__ __forceinline__ void find_step(uint32_t &lo, uint32_t &hi, const uint32_t *s_m, uint32_t first_lo, uint32_t first_hi, uint32_t x,
+                                          [[maybe_unused]] const FindOpt *q)
+{
+    if constexpr (OPT) find_opt_step(lo, hi, s_m, first_lo, first_hi, x, *q);
+    else find_cls_step(lo, hi, s_m, first_lo, first_hi, x);
+}
+
 /* find_pat_lane for classes: the starts among the lane's 32 at which every byte is in its position's class, all of it
  * inside the tile's tsym symbols.  The lane warms the automaton up on the (plen - 1 rounded up to words) bytes behind
  * its 32 - its neighbours' bytes of the wave's slice, read from the far end - and then takes its own 32 from the last to
@@ -338,24 +384,29 @@ __device__ __forceinline__ void find_cls_step(uint32_t &lo, uint32_t &hi, const 
  * ALT (hufgpu_find_any): the state holds several alternatives, plen is the longest one's length, and a start is a byte at
  * which ANY bit of `starts` is set.  Alternative j's start bit depends on the len_j <= plen bytes from the start on and on
  * nothing else, so the same mask of the starts serves: the walk sets the starts with start + plen <= tsym, whichever
- * alternative lies there, and find_alt_seam_kernel has the tile's last plen - 1 starts for every alternative. */
-template <bool ALT = false>
+ * alternative lies there, and find_alt_seam_kernel has the tile's last plen - 1 starts for every alternative.
+ * OPT (hufgpu_find_any_quant): the step is find_opt_step with q's masks, and plen is the longest alternative's position
+ * count.  A start bit behind byte i depends on the bytes i ... i + plen - 1 and on nothing else - no form is longer -, so
+ * warm-up, find_fit and the mask of the starts are the any-of walk's; find_opt_seam_kernel has the tile's last plen - 1 starts. */
+template <bool ALT = false, bool OPT = false>
 __device__ __forceinline__ uint32_t find_cls_lane(const uint32_t *tile_words, const uint32_t (&w)[8], const uint32_t *s_m, uint32_t first_lo,
                                                   uint32_t first_hi, uint32_t plen, uint32_t tsym, uint32_t lane,
-                                                  [[maybe_unused]] uint32_t starts_lo = 0, [[maybe_unused]] uint32_t starts_hi = 0)
+                                                  [[maybe_unused]] uint32_t starts_lo = 0, [[maybe_unused]] uint32_t starts_hi = 0,
+                                                  [[maybe_unused]] const FindOpt *q = nullptr)
 {
+    static_assert(ALT || !OPT, "optional positions: the any-of route's");
     uint32_t lo = 0, hi = 0;
     for (uint32_t k = (plen + 2u) >> 2; k-- > 0u;) {                /* the words that hold the plen - 1 bytes behind the lane's */
         const uint32_t x = tile_words[dmin<uint32_t>(8u * lane + 8u + k, HUF_SUB_TILE / 4 - 1u)];
 #pragma unroll
-        for (int i = 3; i >= 0; i--) find_cls_step(lo, hi, s_m, first_lo, first_hi, (x >> (8 * i)) & 0xffu);
+        for (int i = 3; i >= 0; i--) find_step<OPT>(lo, hi, s_m, first_lo, first_hi, (x >> (8 * i)) & 0xffu, q);
     }
     uint32_t m = 0;
 #pragma unroll
     for (int j = 7; j >= 0; j--) {
 #pragma unroll
         for (int i = 3; i >= 0; i--) {
-            find_cls_step(lo, hi, s_m, first_lo, first_hi, (w[j] >> (8 * i)) & 0xffu);
+            find_step<OPT>(lo, hi, s_m, first_lo, first_hi, (w[j] >> (8 * i)) & 0xffu, q);
             /* (the bytes come last first: the mask is shifted up under each new bit - a bit set by its own constant would
              * keep 25 constants and 32 partial masks in registers, 34 VGPRs more) */
             if constexpr (ALT) m = (m << 1) | dmin<uint32_t>((hi & starts_hi) | (lo & starts_lo), 1u);
@@ -401,11 +452,14 @@ __device__ __forceinline__ void find_term_lane(const uint32_t *tile_words, const
  * ct in the place of the pattern's bytes.  ALT: ct holds several alternatives, alt says where they start, and p->plen is
  * the longest one's length.  NT != 0 (find_rec_term_sub_kernel): the alternatives stand in NT terms, and what leaves the
  * workgroup is a match mask word a group and a count a tile for every TERM, into tm's term-major arrays, in the place of the one
- * mask and count: the delimiter mask, the edges, the checks and the status are as they are. */
-template <bool PAT, bool REC = false, bool CLS = false, bool ALT = false, uint32_t NT = 0>
+ * mask and count: the delimiter mask, the edges, the checks and the status are as they are.  OPT (find_opt_sub_kernel,
+ * find_rec_opt_sub_kernel): the any-of walk with find_opt_step and q's masks in the place of find_cls_step. */
+template <bool PAT, bool REC = false, bool CLS = false, bool ALT = false, uint32_t NT = 0, bool OPT = false>
 __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatArgs *p, const FindRecArgs *r = nullptr, const FindClsTable *ct = nullptr,
-                                              [[maybe_unused]] const FindAltArgs *alt = nullptr, [[maybe_unused]] const FindTerms *tm = nullptr)
+                                              [[maybe_unused]] const FindAltArgs *alt = nullptr, [[maybe_unused]] const FindTerms *tm = nullptr,
+                                              [[maybe_unused]] const FindOpt *q = nullptr)
 {
+    static_assert(!OPT || (ALT && NT == 0), "optional positions: the any-of route's, one term");
     static_assert(PAT || !REC, "the records' route is the pattern's");
     static_assert(NT == 0 || (ALT && REC && NT <= FIND_TERMS_MAX), "the terms' route is the any-of records'");
     static_assert(PAT || !CLS, "the classes' route is the pattern's");
@@ -459,9 +513,11 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
                  * which is what the automaton's start bits say after plen copies of the leaf (after len_j of them
                  * alternative j's start bit is set iff the leaf is in all its classes, and it stays as it is from then on).
                  * The starts of a tile at which the LONGEST alternative fits are set here, as in other blocks;
-                 * find_alt_seam_kernel has the rest, alternative by alternative. */
+                 * find_alt_seam_kernel has the rest, alternative by alternative.  OPT: the same question to the automaton
+                 * with the closure - the state only grows under copies of one byte, and after plen of them every form has
+                 * had its length; find_opt_seam_kernel has the rest. */
                 uint32_t lo = 0, hi = 0;
-                for (uint32_t k = 0; k < plen; k++) find_cls_step(lo, hi, s_set, ct->first[0], ct->first[1], (uint32_t)leaf);
+                for (uint32_t k = 0; k < plen; k++) find_step<OPT>(lo, hi, s_set, ct->first[0], ct->first[1], (uint32_t)leaf, q);
                 match = ((hi & alt->starts[1]) | (lo & alt->starts[0])) != 0u;
                 if constexpr (NT != 0) {
 #pragma unroll
@@ -545,6 +601,7 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
         if constexpr (PAT) {
             const uint32_t tsym = find_tile_syms(blen, t), plen = p->plen;
             if constexpr (NT != 0) find_term_lane<NT>(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane, *tm, mt);
+            else if constexpr (OPT) m = find_cls_lane<true, true>(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane, alt->starts[0], alt->starts[1], q);
             else if constexpr (ALT) m = find_cls_lane<true>(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane, alt->starts[0], alt->starts[1]);
             else if constexpr (CLS) m = find_cls_lane(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane);
             else m = find_pat_lane(tile_words, w, s_set, plen, tsym, lane);         /* (0 for a lane without symbols) */
@@ -607,6 +664,15 @@ __global__ __launch_bounds__(FIND_THREADS) void find_cls_sub_kernel(FindClsArgs 
 __global__ __launch_bounds__(FIND_THREADS) void find_rec_cls_sub_kernel(FindClsArgs a) { find_sub_body<true, true, true>(a.r.p.f, &a.r.p, &a.r, &a.t); }
 __global__ __launch_bounds__(FIND_THREADS) void find_alt_sub_kernel(FindAltArgs a) { find_sub_body<true, false, true, true>(a.r.p.f, &a.r.p, nullptr, &a.t, &a); }
 __global__ __launch_bounds__(FIND_THREADS) void find_rec_alt_sub_kernel(FindAltArgs a) { find_sub_body<true, true, true, true>(a.r.p.f, &a.r.p, &a.r, &a.t, &a); }
+/* hufgpu_find_any_quant / hufgpu_find_records_quant with an optional position */
+__global__ __launch_bounds__(FIND_THREADS) void find_opt_sub_kernel(FindOptArgs a)
+{
+    find_sub_body<true, false, true, true, 0, true>(a.a.r.p.f, &a.a.r.p, nullptr, &a.a.t, &a.a, nullptr, &a.q);
+}
+__global__ __launch_bounds__(FIND_THREADS) void find_rec_opt_sub_kernel(FindOptArgs a)
+{
+    find_sub_body<true, true, true, true, 0, true>(a.a.r.p.f, &a.a.r.p, &a.a.r, &a.a.t, &a.a, nullptr, &a.q);
+}
 /* hufgpu_find_records_terms with two terms or more: NT is the call's n_terms, a kernel each */
 template <uint32_t NT>
 __global__ __launch_bounds__(FIND_THREADS) void find_rec_term_sub_kernel(FindTermArgs ta)
@@ -786,6 +852,57 @@ __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_term_seam_kernel(FindT
         f.tcnt = ta.t.mcnt + t * pa.f.ntiles;
         find_seam_end(f, m, ((hits >> t) & 1u) != 0u);
     }
+}
+
+/* hufgpu_find_any_quant: the tile's last plen - 1 starts (plen: the longest alternative's position count) for every form of
+ * every alternative.  A form's length is not known in advance, so "byte k against bit hi - k" does not carry over.  What
+ * does: let e be the end of the bytes within [p, p + plen) that exist and lie in served blocks; the automaton of the walk, run
+ * with an empty state from byte e - 1 down to byte p, has a start bit set behind byte p iff a form lies at p that ends at or
+ * in front of e - the shortest form that lies there decides, as its span is the one that touches the fewest blocks.
+ * The wave copies its window once - the tile's tail slot, then the heads of the tiles behind it over the layout's tile
+ * lengths, up to raw_size or the first block that is not served: at most 63 + 63 bytes, `filled` of them - into LDS, and
+ * every lane runs its at most plen steps on LDS bytes.  One bit and one count a start through find_seam_end. */
+__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_opt_seam_kernel(FindOptArgs qa)
+{
+    __shared__ uint32_t s_key[FIND_CLS_WORDS];
+    __shared__ uint8_t s_win[FIND_SEAM_THREADS / 64][FIND_EDGE_SLOT];
+    const FindAltArgs &aa = qa.a;
+    const FindPatArgs &pa = aa.r.p;
+    const FindArgs &a = pa.f;
+    find_seam_key<true>(pa, &aa.t, s_key);
+    const uint64_t i = find_tile_index<FIND_SEAM_THREADS>();
+    if (i >= a.ntiles) return;
+    const FindTile tl = find_tile(a, i);
+    if (tl.t * HUF_SUB_TILE >= tl.blen || a.errs[tl.b] != HUFE_OK) return;
+    const FindSeam m = find_seam_lane(pa, i, tl);
+    uint8_t *win = s_win[uni32(threadIdx.x >> 6)];
+    if (m.lane < m.ne) win[m.lane] = pa.edges[i * FIND_EDGE_SLOT + 64u + m.lane];
+    const uint32_t want = m.ne + pa.plen - 1u;                      /* the last start's bytes end here: at most 126 */
+    uint32_t filled = m.ne;
+    uint64_t cb = tl.b, ct = tl.t, cblen = tl.blen;
+    while (filled < want) {                                         /* (the wave's: a tile of the layout a round, a byte at least) */
+        if ((ct + 1) * HUF_SUB_TILE < cblen) {
+            ct++;
+        } else {
+            cb++;
+            ct = 0;
+            if (cb >= a.s.nblocks || a.errs[cb] != HUFE_OK) break;  /* the data ends, or a block is not served: e */
+            cblen = find_block_len(a, cb);
+        }
+        const uint32_t n = dmin<uint32_t>(find_tile_syms(cblen, ct), want - filled);    /* (<= plen - 1: the head slot holds them) */
+        if (m.lane < n) win[filled + m.lane] = pa.edges[(cb * a.tpb + ct) * FIND_EDGE_SLOT + m.lane];
+        filled += n;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");           /* the window is in LDS before other lanes read it */
+    __builtin_amdgcn_wave_barrier();
+    bool hit = false;
+    if (m.lane < m.ne) {
+        uint32_t lo = 0, hi = 0;
+        for (uint32_t k = dmin<uint32_t>(m.lane + pa.plen, filled); k-- > m.lane;)
+            find_opt_step(lo, hi, s_key, aa.t.first[0], aa.t.first[1], win[k], qa.q);
+        hit = ((hi & aa.starts[1]) | (lo & aa.starts[0])) != 0u;
+    }
+    find_seam_end(a, m, hit);
 }
 
 /* The anchored calls with HUFGPU_ANCHOR_BOL or HUFGPU_ANCHOR_WORD, behind the seam kernel and in front of everything that
