@@ -858,6 +858,92 @@ int hufgpu_find_records_quant(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t 
                               uint32_t flags, void *stream);
 
 /*
+ * FIND, ONE grep -E LINE: anchors, terms and optional positions TOGETHER.  '^[0-9]{1,3}\.[0-9]{1,3}', grep -w 'colou?r',
+ * 'refused [0-9]{1,5} times$', '^2026-10-19.*ERROR', 'ERROR.*took [0-9]{1,5}ms'.  hufgpu_find_any_expr() is
+ * hufgpu_find_any_anchored() with `optional` behind n_alts; hufgpu_find_records_expr() is hufgpu_find_records_context()
+ * with `optional`, the three term arguments of hufgpu_find_records_terms() and the two anchor arguments of
+ * hufgpu_find_records_anchored().  Their contracts hold word for word: d_sub_index (the caller vouches for NOTHING), every
+ * output, cap and total, `select`, d_rec_no, before / after, d_rec_sel, the known-extent rule, one-symbol blocks served,
+ * flags, batch geometry, nblocks = 0, enqueue-only without a host write or a wait, every argument error (worded
+ * "find_any_expr: ..." / "find_records_expr: ...") - but for what a pattern is and which occurrences count.  There is no CPU
+ * path.
+ *
+ *   an occurrence : a start p, an alternative j and a FORM of j (hufgpu_find_any_quant(): some of its optional positions
+ *                   dropped) of length len that lies at p.  Its left neighbour is L = data[p - 1], ABSENT when p = 0; its
+ *                   right neighbour is R = data[p + len], absent when p + len = raw_size: R depends on the form.  It
+ *                   QUALIFIES by hufgpu_find_any_anchored()'s rule, form by form:
+ *                     HUFGPU_ANCHOR_BOL   L is absent or L is in D
+ *                     HUFGPU_ANCHOR_EOL   R is absent or R is in D
+ *                     HUFGPU_ANCHOR_WORD  (L is absent or L is not in W) and (R is absent or R is not in W)
+ *   positions call: p is reported once, ascending, when some form of some alternative lies there, qualifies, and has its
+ *                   tested span in served blocks only: [p, p + len), widened by one byte on each side where a neighbour
+ *                   exists and an anchor tests it.  Each form has its own span; as a shorter span touches no more blocks,
+ *                   the SHORTEST QUALIFYING form decides the right side ('ab?$' on "ab\n": "a" lies at p and does not
+ *                   qualify, "ab" does).  A start is left out on doubt, never reported wrongly.
+ *   records call  : n_terms = 1: a record is selected when it holds a qualifying occurrence.
+ *                   HUFGPU_TERMS_ALL, more terms: every term may hold optional positions; anchors must be 0.
+ *                   HUFGPU_TERMS_ORDERED, more terms: p_t + len_t <= p_{t+1} as in hufgpu_find_records_terms(), and the
+ *                   anchors bind the OUTER edges - grep '^A.*B$', grep -w 'A.*B' -: BOL and the left half of WORD test L of
+ *                   term 0's occurrence, EOL and the right half of WORD test R of the last term's.  Optional positions -
+ *                   and alternatives of several lengths - are allowed in the LAST term only: the walk over a record takes
+ *                   each term's first occurrence behind the end of the one before, which needs the end of every term but
+ *                   the last.  That is exact: term 0's starts are filtered to those whose L qualifies, the last term's to
+ *                   those with a form whose R qualifies, and as the lengths in front of the last term are fixed, taking the
+ *                   first of each finds a witness if and only if there is one.
+ *                   From the selected records on everything is hufgpu_find_records_context()'s.
+ *   the budget    : with EOL or WORD every alternative whose right neighbour is tested takes one more bit of the matcher's
+ *                   state: all alternatives of the positions call and of a one-term call, the last term's otherwise.  The
+ *                   lengths plus one for each of those sum to at most HUFGPU_FIND_PATTERN_MAX.
+ *   one-symbol blocks: served; an alternative lies inside one only if the one value is in the classes of one of its forms
+ *                   AND may stand behind it.
+ *
+ * Found on the host, before anything is enqueued and before the context is looked at, HUF_ERROR_INVALID_ARGUMENT, in this
+ * order (the older calls', each group where its call has it):
+ *
+ *   1. `select` with a bit other than HUFGPU_SELECT_INVERT (records call);
+ *   2. the anchored calls': an unknown `anchors` bit; BOL or EOL without delim_set (positions call); WORD without word_set;
+ *   3. the terms call's: terms_mode, a NULL term_alts, n_terms, a term without alternatives, counts that do not sum to n_alts;
+ *      then HUFGPU_TERMS_ORDERED with unequal lengths in a term OTHER than the last;
+ *   4. HUFGPU_TERMS_ALL with n_terms > 1 and anchors != 0;
+ *   5. the any-of calls': n_alts, a length of 0, the sum of the lengths; then the budget above; then the classes;
+ *   6. the quant calls': an `optional` byte above 1, an alternative whose positions are all optional;
+ *   7. HUFGPU_TERMS_ORDERED with an optional position in a term other than the last (the message names the term, the
+ *      alternative and the position);
+ *   8. the older calls' remaining checks (required pointers, caps, geometry, the context).
+ *
+ * The identities.  With optional NULL or all zeros and one term the calls enqueue exactly what hufgpu_find_any_anchored() /
+ * hufgpu_find_records_anchored() enqueue; with anchors = 0 and one term what hufgpu_find_any_quant() /
+ * hufgpu_find_records_quant() enqueue; with anchors = 0 and no optional position what hufgpu_find_records_terms() enqueues
+ * (which, unlike that call, also serves an ordered last term of several lengths).  The fourteen older calls launch what
+ * they always did.  Where the dimensions cross, the walk is the quant calls' (several terms: the terms' walk with the
+ * closure), the seam kernel is the quant calls' window with the end of the data as a boundary, and the kernel for the byte
+ * in front runs over the one mask, or term 0's.  DESIGN.md 5.24.
+ *
+ * OUT OF SCOPE: anchors with HUFGPU_TERMS_ALL of several terms (which term would they bind?); optional positions in a term
+ * in front of another in an ordered call (its earliest end is not to be had from a mask of starts); anchors per alternative;
+ * \b INSIDE a pattern; unbounded repeats; groups; and which form matched.
+ */
+int hufgpu_find_any_expr(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                         const uint64_t *d_block_offsets, uint64_t nblocks,
+                         const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                         const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts, const uint8_t *optional,
+                         const uint8_t delim_set[32], const uint8_t word_set[32], uint32_t anchors,
+                         uint64_t *d_pos, uint64_t pos_cap,
+                         uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                         uint32_t flags, void *stream);
+int hufgpu_find_records_expr(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                             const uint64_t *d_block_offsets, uint64_t nblocks,
+                             const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                             const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                             const uint8_t *optional,
+                             const uint32_t *term_alts, uint32_t n_terms, uint32_t terms_mode,
+                             const uint8_t word_set[32], uint32_t anchors,
+                             uint32_t select, uint32_t before, uint32_t after,
+                             uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no, uint8_t *d_rec_sel, uint64_t rec_cap, uint32_t max_len,
+                             uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                             uint32_t flags, void *stream);
+
+/*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from
  * another rank, or encoded here by a caller that did not keep the 7 % of side data.  hufgpu_encode_sub() writes the
  * sub-index as a by-product of packing; these three rebuild exactly that - the same entries, entry for entry

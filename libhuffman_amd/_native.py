@@ -82,7 +82,8 @@ hufgpu_sub_index_from_raw hufgpu_decode_build_sub hufgpu_build_sub_index hufgpu_
 hufgpu_append hufgpu_truncate hufgpu_ranges_counters hufgpu_gather hufgpu_find_bytes hufgpu_find_pattern hufgpu_find_records
 hufgpu_find_classes hufgpu_find_records_classes hufgpu_find_any hufgpu_find_records_any
 hufgpu_find_records_select hufgpu_find_records_context hufgpu_find_any_anchored hufgpu_find_records_anchored
-hufgpu_find_records_terms hufgpu_find_any_quant hufgpu_find_records_quant""".split()
+hufgpu_find_records_terms hufgpu_find_any_quant hufgpu_find_records_quant
+hufgpu_find_any_expr hufgpu_find_records_expr""".split()
 
 
 def so_path() -> str:
@@ -226,6 +227,11 @@ def load() -> C.CDLL:
     L.hufgpu_find_records_quant.restype = C.c_int         # hufgpu_find_records_context's with `optional` behind n_alts
     L.hufgpu_find_records_quant.argtypes = (L.hufgpu_find_records_context.argtypes[:12] + [vp] +
                                             L.hufgpu_find_records_context.argtypes[12:])
+    L.hufgpu_find_any_expr.restype = C.c_int              # hufgpu_find_any_anchored's with `optional` behind n_alts
+    L.hufgpu_find_any_expr.argtypes = L.hufgpu_find_any.argtypes[:11] + [vp, vp, vp, C.c_uint32] + L.hufgpu_find_any.argtypes[11:]
+    L.hufgpu_find_records_expr.restype = C.c_int          # hufgpu_find_records_context's with `optional`, the terms' three and the anchors' two
+    L.hufgpu_find_records_expr.argtypes = (L.hufgpu_find_records_context.argtypes[:12] + [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32] +
+                                           L.hufgpu_find_records_context.argtypes[12:])
     _LIB = L
     return L
 

@@ -519,6 +519,126 @@ class GpuCodec:
         AnyOf item must have one length."""
         __slots__ = ()
 
+    class Expr:
+        """A whole grep -E line of this matcher's subset as the `pattern` of find_records / count_records / grep, and with one
+        term of find_pattern / count_pattern (hufgpu_find_any_expr / hufgpu_find_records_expr): anchors, terms and optional
+        positions TOGETHER.  Each term is a bytes-like literal, a list / tuple of classes with Opt / Rep items, or an AnyOf
+        of those.  `ordered`: the terms one behind the other without overlap (grep 'A.*B'), else all of them anywhere
+        (grep A | grep B).  `bol`, `eol`, `whole_line`, `word`, `word_bytes` are the keywords of find_records, carried by the
+        Expr: with ordered terms they bind the OUTER edges ('^A.*B$'), and they do not go with `ordered=False` and several
+        terms.  Of ordered terms only the LAST may hold Opt / Rep items or alternatives of several lengths.  GpuCodec.egrep()
+        writes an Expr from a grep -E expression.  `ignore_case` and `delimiters` stay keywords of the methods."""
+        __slots__ = ("terms", "ordered", "bol", "eol", "word", "word_bytes")
+
+        def __init__(self, *terms, ordered=True, bol=False, eol=False, whole_line=False, word=False, word_bytes=None):
+            self.terms, self.ordered = tuple(terms), bool(ordered)
+            self.bol, self.eol = bool(bol or whole_line), bool(eol or whole_line)
+            self.word, self.word_bytes = bool(word), word_bytes
+
+        def __len__(self):
+            return len(self.terms)
+
+        def __iter__(self):
+            return iter(self.terms)
+
+        def __repr__(self):
+            flags = [f"{k}={getattr(self, k)!r}" for k in ("bol", "eol", "word") if getattr(self, k)]
+            flags += [] if self.ordered else ["ordered=False"]
+            flags += [] if self.word_bytes is None else [f"word_bytes={self.word_bytes!r}"]
+            return "Expr(" + ", ".join([repr(t) for t in self.terms] + flags) + ")"
+
+    @staticmethod
+    def expr_arrays(expr, ignore_case: bool = False, delimiters=b"\n"):
+        """The host arrays of hufgpu_find_records_expr for an Expr, checked as the C call checks them: a dict of `classes`
+        uint8 [total][32], `alt_lens` uint32 [n_alts], `optional` uint8 [total], `term_alts` uint32 [n_terms], `ordered`,
+        `anchors` (the HUFGPU_ANCHOR bits), `delim_set` and `word_set` (byte_sets; the latter None without `word`).
+        `delimiters` None: a search for positions, no class is looked at for delimiters.  Raises ValueError for no term or
+        more than FIND_TERMS_MAX, `word_bytes` without `word`, anchors next to several terms with `ordered=False`, what
+        quant_classes raises for a term (the message names the term), and for ordered terms an Opt / Rep item or alternatives
+        of several lengths in a term other than the last (the message names the term, the alternative and the item), a class
+        that holds a delimiter, and positions - plus one for every alternative whose byte behind is tested: with `eol` or
+        `word` all of one term, the last term's otherwise - above FIND_PATTERN_MAX; TypeError for a term that is a str, an
+        AllOf, a Seq or an Expr."""
+        if not isinstance(expr, GpuCodec.Expr):
+            raise TypeError("expr_arrays takes a GpuCodec.Expr")
+        n_terms = len(expr)
+        if not 1 <= n_terms <= _native.FIND_TERMS_MAX:
+            raise ValueError(f"Expr has 1 to {_native.FIND_TERMS_MAX} terms, not {n_terms}")
+        if expr.word_bytes is not None and not expr.word:
+            raise ValueError("`word_bytes` says what `word` looks at: give `word=True` with it")
+        bits = ((_native.ANCHOR_BOL if expr.bol else 0) | (_native.ANCHOR_EOL if expr.eol else 0) |
+                (_native.ANCHOR_WORD if expr.word else 0))
+        if bits and n_terms > 1 and not expr.ordered:
+            raise ValueError(f"anchors do not go with `ordered=False` and {n_terms} terms: which term would they bind?")
+        rows, lens, opts, counts = [], [], [], []
+        for t, term in enumerate(expr):
+            if isinstance(term, (str, GpuCodec._Terms, GpuCodec.Expr)):
+                raise TypeError(f"term {t} is a {type(term).__name__}: a term is a bytes-like literal, a list / tuple of classes "
+                                "or an AnyOf")
+            alts = term if isinstance(term, GpuCodec.AnyOf) else GpuCodec.AnyOf(term)
+            if len(alts) == 0:
+                raise ValueError(f"term {t} has no alternative: no record would hold it")
+            inner = expr.ordered and t + 1 < n_terms                   # a term in front of another: one length, no optional position
+            for j, alt in enumerate(alts if inner else ()):
+                for k, c in enumerate(alt if isinstance(alt, (list, tuple)) else ()):
+                    if isinstance(c, (GpuCodec.Opt, GpuCodec.Rep)):
+                        raise ValueError(f"term {t}, alternative {j}, item {k} is {c!r}: of ordered terms only the last may hold "
+                                         "optional positions")
+            try:
+                c, l, o = GpuCodec.quant_classes(alts, ignore_case)
+            except ValueError as e:
+                raise ValueError(f"term {t}: {e}") from None
+            if inner and len(set(l.tolist())) > 1:
+                raise ValueError(f"term {t} has alternatives of the lengths {sorted(set(l.tolist()))}: of ordered terms only the "
+                                 "last may have several")
+            rows.append(c), lens.append(l), opts.append(o), counts.append(len(l))
+        classes, alt_lens, optional = np.concatenate(rows), np.concatenate(lens), np.concatenate(opts)
+        behind = bits & (_native.ANCHOR_EOL | _native.ANCHOR_WORD)
+        total = int(alt_lens.sum()) + (counts[-1] if behind else 0)
+        if len(alt_lens) > _native.FIND_PATTERN_MAX or total > _native.FIND_PATTERN_MAX:
+            raise ValueError(f"the {len(alt_lens)} alternatives' positions" + (f" and one position behind each of the {counts[-1]} "
+                             "whose byte behind is tested" if behind else "") + f" sum to {total}, above {_native.FIND_PATTERN_MAX}")
+        st = None if delimiters is None else GpuCodec.byte_set(delimiters)
+        both = classes & np.frombuffer(st, np.uint8) if st is not None else None
+        if both is not None and both.any():
+            row = int(np.flatnonzero(both.any(axis=1))[0])
+            v = int(np.flatnonzero(np.unpackbits(both[row], bitorder="little"))[0])
+            j = int(np.searchsorted(np.cumsum(alt_lens), row, side="right"))
+            t = int(np.searchsorted(np.cumsum(counts), j, side="right"))
+            raise ValueError(f"term {t}: class {row - int(alt_lens[:j].sum())} of alternative {j - int(sum(counts[:t]))} holds a "
+                             f"delimiter (value {v}): a match lies inside one record")
+        ws = GpuCodec.byte_set(GpuCodec.WORD_BYTES if expr.word_bytes is None else expr.word_bytes) if expr.word else None
+        return {"classes": classes, "alt_lens": alt_lens, "optional": optional, "term_alts": np.array(counts, np.uint32),
+                "ordered": expr.ordered, "anchors": bits, "delim_set": st, "word_set": ws}
+
+    @staticmethod
+    def _expr_alone(pattern, bol, eol, whole_line, word, word_bytes):
+        """an Expr carries its anchors: the methods' anchor keywords next to one are a ValueError"""
+        if bol or eol or whole_line or word or word_bytes is not None:
+            raise ValueError("`bol`, `eol`, `whole_line`, `word` and `word_bytes` next to an Expr: the Expr carries its anchors")
+
+    @staticmethod
+    def egrep(expr: bytes, delimiters=b"\n", ignore_case: bool = False):
+        """A grep -E line of this matcher's subset, compiled on the host to a GpuCodec.Expr.  regex()'s grammar - its parser -
+        and besides: '^' at the start and '$' at the end of an alternative; '\\<' at its start with '\\>' at its end, or '\\b'
+        at both, for `word`; and, in an expression without a top-level '|', a top-level '.*' that splits it into ordered terms,
+        FIND_TERMS_MAX at most.  A leading '.*' is dropped together with a '^' in front of it, a trailing one together with a
+        '$' behind it.  Raises ValueError ("egrep: offset N: ...") for what regex() raises it for - 'x*', 'x+', '.+', '{m,}' and
+        groups among it - and for an anchor anywhere else, '\\b' inside a term or at one end only, alternatives that do not all
+        carry the same anchors (anchors per alternative are out of scope), a quantified term in front of a '.*', '.*' next to
+        '|', and more than FIND_TERMS_MAX terms."""
+        alts = GpuCodec._regex_parse(expr, delimiters, ignore_case, "egrep", True)
+        for alt in alts:
+            if alt["wl"] != alt["wr"]:
+                raise ValueError(f"egrep: offset {alt['at']}: a word's edge at one end of the alternative only: '\\<' and '\\>' "
+                                 "(or '\\b' and '\\b') stand at both")
+            if any(alt[k] != alts[0][k] for k in ("bol", "eol", "wl")):
+                raise ValueError(f"egrep: offset {alt['at']}: the alternatives do not carry the same anchors: anchors per "
+                                 "alternative are not in this matcher")
+        first = alts[0]
+        terms = first["terms"] if len(alts) == 1 else [GpuCodec.AnyOf(*(alt["terms"][0] for alt in alts))]
+        return GpuCodec.Expr(*terms, ordered=True, bol=first["bol"], eol=first["eol"], word=first["wl"])
+
     @staticmethod
     def _find_terms(pattern, ignore_case, delimiters, anchors):
         """(key, st, term_alts, n_terms, mode) of hufgpu_find_records_terms for an AllOf / Seq of two items or more: the
@@ -636,12 +756,20 @@ class GpuCodec:
         ')' (no groups), '^' and '$' (the `bol` / `eol` keywords anchor a pattern without repeats), a quantifier with nothing
         to repeat, a bad '{...}', a bad range or escape, a set without its ']', an empty alternative or class, a repeat of at
         most 0 copies, and a total above FIND_PATTERN_MAX positions."""
+        return GpuCodec.AnyOf(*(alt["terms"][0] for alt in GpuCodec._regex_parse(expr, delimiters, ignore_case, "regex", False)))
+
+    @staticmethod
+    def _regex_parse(expr, delimiters, ignore_case, who, extended):
+        """The parser that regex() and egrep() share: a list of one dict an alternative, {"terms": the lists of items that a
+        top-level '.*' separates - regex(): always one -, "bol", "eol", "wl", "wr": the anchors at its two ends, "at": its
+        offset}.  `extended` (egrep): '^', '\\<' and '\\b' at the start of an alternative, '$', '\\>' and '\\b' at its end, and
+        a top-level '.*' are taken; without it they are the errors that regex() documents."""
         expr = bytes(expr)
         delims = set(bytes(delimiters) if isinstance(delimiters, (bytes, bytearray)) else [int(v) for v in delimiters])
         n = len(expr)
 
         def bad(at, why):
-            return ValueError(f"regex: offset {at}: {why}")
+            return ValueError(f"{who}: offset {at}: {why}")
 
         def fold(values):
             return set(values) | ({v ^ 0x20 for v in values if 0x41 <= (v & ~0x20) <= 0x5a and v < 128} if ignore_case else set())
@@ -726,26 +854,93 @@ class GpuCodec:
                 raise bad(at, "a repeat of at most 0 copies")
             return lo, hi, end + 1
 
-        alts, items, total, i, alt_at = [], [], 0, 0, 0
+        def quantified(term):
+            return any(isinstance(c, (GpuCodec.Opt, GpuCodec.Rep)) for c in term)
+
+        def alt_ends(at):
+            """does the alternative end at `at`, but for a '$'"""
+            at += at < n and expr[at] == ord("$")
+            return at >= n or expr[at] == ord("|")
+
+        def new_alt(at):
+            return {"terms": [], "bol": False, "eol": False, "wl": False, "wr": False, "at": at, "star": None}
+
+        # (egrep) split_at: the offset of a '.*' behind which no item has come yet; lead: it stood in front of the first item
+        alts, alt, items, total, i, alt_at, split_at, lead = [], new_alt(0), [], 0, 0, 0, None, False
         while True:
             if i >= n or expr[i] == ord("|"):
-                if not items:
+                if alt["star"] is not None and (alts or i < n):
+                    raise bad(alt["star"], "'.*' next to '|': an expression has alternatives or terms, not both")
+                if split_at is not None and not lead:                 # a trailing '.*', and a '$' behind it: nothing to test
+                    if alt["wr"]:
+                        raise bad(split_at, "'.*' in front of a word's end: '\\b' would stand inside a term")
+                    alt["eol"] = False
+                elif not items:
                     raise bad(alt_at, "an empty alternative: it would match everywhere")
-                if all(isinstance(c, GpuCodec.Opt) or (isinstance(c, GpuCodec.Rep) and c.lo == 0) for c in items):
-                    raise bad(alt_at, "every position of the alternative is optional: it would match everywhere")
-                alts.append(items)
+                else:
+                    alt["terms"].append(items)
+                for term in alt["terms"]:
+                    if all(isinstance(c, GpuCodec.Opt) or (isinstance(c, GpuCodec.Rep) and c.lo == 0) for c in term):
+                        raise bad(alt_at, "every position of the alternative is optional: it would match everywhere"
+                                  if len(alt["terms"]) == 1 else "every position of a term is optional: it would match everywhere")
+                if not alt["terms"]:
+                    raise bad(alt_at, "an empty alternative: it would match everywhere")
+                alts.append(alt)
                 if i >= n:
                     break
-                items, i = [], i + 1
-                alt_at = i
+                items, i, split_at, lead = [], i + 1, None, False
+                alt_at, alt = i, new_alt(i)
                 continue
             at, c = i, expr[i]
             if c in b"?*+{":
                 raise bad(at, f"'{chr(c)}' has nothing to repeat")
             if c in b"()":
                 raise bad(at, f"'{chr(c)}': groups are not in this matcher")
-            if c in b"^$":
+            if c in b"^$" and not extended:
                 raise bad(at, f"'{chr(c)}': anchors are keywords of the calls (bol, eol), not part of the expression")
+            fresh = not items and not alt["terms"] and split_at is None   # nothing of the alternative but anchors has come
+            if c == ord("^"):
+                if not fresh or alt["bol"] or alt["wl"]:
+                    raise bad(at, "'^' stands at the start of an alternative")
+                alt["bol"], i = True, at + 1
+                continue
+            if c == ord("$"):
+                if not (at + 1 >= n or expr[at + 1] == ord("|")) or fresh:
+                    raise bad(at, "'$' stands at the end of an alternative")
+                alt["eol"], i = True, at + 1
+                continue
+            if extended and c == ord("\\") and at + 1 < n and expr[at + 1] in b"<>b":
+                k = expr[at + 1]
+                if k != ord(">") and fresh and not alt["wl"]:
+                    alt["wl"] = True
+                elif k != ord("<") and not fresh and not alt["wr"] and alt_ends(at + 2):
+                    alt["wr"] = True
+                else:
+                    raise bad(at, f"'\\{chr(k)}' inside a term: a word's edges stand at the two ends of an alternative")
+                i = at + 2
+                continue
+            if extended and c == ord(".") and at + 1 < n and expr[at + 1] == ord("*"):
+                if at + 2 < n and expr[at + 2] in b"?*+{":
+                    raise bad(at + 2, f"'{chr(expr[at + 2])}' behind a quantifier has nothing to repeat")
+                if fresh:                                               # a leading '.*', and a '^' in front of it: nothing to test
+                    if alt["wl"]:
+                        raise bad(at, "'.*' behind a word's start: '\\b' would stand inside a term")
+                    alt["bol"], lead = False, True
+                elif items:
+                    alt["terms"].append(items)
+                    items, lead = [], False
+                if split_at is None:
+                    split_at = at
+                if alt["star"] is None:
+                    alt["star"] = at
+                i = at + 2
+                continue
+            if split_at is not None and not lead:                       # an item behind a '.*': the term in front must have one length
+                if quantified(alt["terms"][-1]):
+                    raise bad(split_at, "a quantified term in front of a '.*': only the last term may hold '?' or '{m,n}'")
+                if len(alt["terms"]) >= _native.FIND_TERMS_MAX:
+                    raise bad(split_at, f"more than {_native.FIND_TERMS_MAX} terms")
+            split_at, lead = None, False
             if c == ord("\\"):
                 values, i = escape(at, False)
             elif c == ord("["):
@@ -770,7 +965,7 @@ class GpuCodec:
             total += copies
             if total > _native.FIND_PATTERN_MAX:
                 raise bad(at, f"the positions come to {total}, above {_native.FIND_PATTERN_MAX}")
-        return GpuCodec.AnyOf(*alts)
+        return alts
 
     _NO_RECORDS = object()          # _find_route's `delimiters` of the calls that have none
 
@@ -778,7 +973,8 @@ class GpuCodec:
     _FIND_CALLS = {"literal": ("hufgpu_find_pattern", "hufgpu_find_records"),
                    "classes": ("hufgpu_find_classes", "hufgpu_find_records_classes"),
                    "any": ("hufgpu_find_any", "hufgpu_find_records_any"),
-                   "quant": ("hufgpu_find_any_quant", "hufgpu_find_records_quant")}
+                   "quant": ("hufgpu_find_any_quant", "hufgpu_find_records_quant"),
+                   "expr": ("hufgpu_find_any_expr", "hufgpu_find_records_expr")}
 
     WORD_BYTES = b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789_"     # grep -w's: [A-Za-z0-9_]
 
@@ -887,10 +1083,17 @@ class GpuCodec:
         matters with `bol`, `eol` or `whole_line` only; with none of the five set the call is the one it always was.  Raises
         ValueError for `word_bytes` without `word`, and with `eol`, `whole_line` or `word` for alternatives whose lengths plus
         one each exceed FIND_PATTERN_MAX.  An AllOf or a Seq is a TypeError: a conjunction has no position of its own."""
-        if isinstance(pattern, GpuCodec._Terms):
+        if isinstance(pattern, GpuCodec._Terms) or (isinstance(pattern, GpuCodec.Expr) and len(pattern) > 1):
             raise TypeError(f"{type(pattern).__name__} selects records: find_records, count_records and grep take it, a search for "
                             "positions does not")
-        route, key, st, (anchors, ws) = self._find_route(pattern, ignore_case, anchors=(bol, eol, whole_line, word, word_bytes))
+        if isinstance(pattern, GpuCodec.Expr):
+            self._expr_alone(pattern, bol, eol, whole_line, word, word_bytes)
+            x = self.expr_arrays(pattern, ignore_case, None)
+            route, anchors = "expr", 0
+            key = (x["classes"].tobytes(), x["alt_lens"].tobytes(), len(x["alt_lens"]), x["optional"].tobytes(),
+                   self.byte_set(delimiters), x["word_set"], x["anchors"])
+        else:
+            route, key, st, (anchors, ws) = self._find_route(pattern, ignore_case, anchors=(bol, eol, whole_line, word, word_bytes))
         max_positions = int(max_positions)
         pos = self._find_buffer(out, max_positions, torch.int64)
         head, tail, totals, errs, counts = self._find_args(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
@@ -963,19 +1166,26 @@ class GpuCodec:
         alternatives together share the FIND_PATTERN_MAX positions.  `ignore_case`, `invert`, `line_numbers` and the distances
         apply to that selection unchanged; one item makes the call that the item alone makes.  ValueError: any of `bol`, `eol`,
         `whole_line`, `word` next to them, more than FIND_TERMS_MAX items, and a Seq item whose alternatives differ in
-        length; TypeError: an AllOf or a Seq inside another one or inside an AnyOf."""
+        length; TypeError: an AllOf or a Seq inside another one or inside an AnyOf.
+        A GpuCodec.Expr pattern - GpuCodec.egrep() writes one - has anchors, terms and optional positions together
+        (hufgpu_find_records_expr); it carries its anchors, so an anchor keyword next to it is a ValueError, and `ignore_case`,
+        `invert`, `line_numbers` and the distances apply to its selection unchanged."""
         before, after = self._find_context(before, after, context)
         widens = bool(before or after)
         select = bool(invert) or bool(line_numbers) or widens
-        terms = None
-        if isinstance(pattern, GpuCodec._Terms):
+        terms = expr = None
+        if isinstance(pattern, GpuCodec.Expr):
+            self._expr_alone(pattern, bol, eol, whole_line, word, word_bytes)
+            expr = self.expr_arrays(pattern, ignore_case, delimiters)
+            route, st, anchors, ws = "expr", expr["delim_set"], 0, None
+        elif isinstance(pattern, GpuCodec._Terms):
             terms = self._find_terms(pattern, ignore_case, delimiters, (bol, eol, whole_line, word, word_bytes))
             if terms[3] == 1:                                           # one item: the call that it makes today
                 (pattern,), terms = pattern, None
         if terms is not None:
             key, st, term_alts, n_terms, mode = terms
             anchors, ws = 0, None
-        else:
+        elif expr is None:
             route, key, st, (anchors, ws) = self._find_route(pattern, ignore_case, delimiters, select,
                                                              (bol, eol, whole_line, word, word_bytes))
         max_records, max_len = int(max_records), int(max_len)
@@ -988,7 +1198,15 @@ class GpuCodec:
         head, tail, totals, errs, counts = self._find_args(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
                                                            block_counts, relaxed)
         ptrs = (pos.data_ptr() if max_records else None, lens.data_ptr() if max_records else None)
-        if terms is not None:
+        if expr is not None:
+            x = expr
+            err = getattr(self.lib, self._FIND_CALLS[route][1])(
+                *head, st, x["classes"].tobytes(), x["alt_lens"].tobytes(), len(x["alt_lens"]), x["optional"].tobytes(),
+                x["term_alts"].tobytes(), len(x["term_alts"]), _native.TERMS_ORDERED if x["ordered"] else _native.TERMS_ALL,
+                x["word_set"], x["anchors"], _native.SELECT_INVERT if invert else 0, before, after, *ptrs,
+                numbers.data_ptr() if line_numbers and max_records else None,
+                selected.data_ptr() if widens and max_records else None, max_records, max_len, *tail)
+        elif terms is not None:
             err = self.lib.hufgpu_find_records_terms(*head, st, *key, term_alts, n_terms, mode, _native.SELECT_INVERT if invert else 0,
                                                      before, after, *ptrs, numbers.data_ptr() if line_numbers and max_records else None,
                                                      selected.data_ptr() if widens and max_records else None, max_records, max_len,

@@ -5,7 +5,8 @@
    gives the records around them as well; hufgpu_find_any_anchored and hufgpu_find_records_anchored are hufgpu_find_any and
    the context call for the matches that begin or end at a record's or a word's edge; hufgpu_find_any_quant and
    hufgpu_find_records_quant are those two for patterns with optional positions; hufgpu_find_records_terms is the
-   context call for the records that hold all of several terms, or all of them in order.  All enqueue-only.  A
+   context call for the records that hold all of several terms, or all of them in order; hufgpu_find_any_expr and
+   hufgpu_find_records_expr take anchors, terms and optional positions together.  All enqueue-only.  A
    wrapper describes its call in three structs; find_call checks them (find_check, no HIP call), fills the kernels'
    arguments and grows the workspace (find_fill) and enqueues the chain of kernels/find.hpp (find_enqueue).
    Part of hufgpu_api.hip (one translation unit). */
@@ -87,7 +88,10 @@ struct FindTermCall {
  * term is NULL but for the terms' call with two terms or more: the walk and the seam kernel then keep a mask a term, and
  * find_rec_mark_kernel runs once a term in front of find_rec_all_kernel (and find_rec_seq_kernel).
  * opt is NULL but for the quant calls with an optional position: then alt is opt's table, plen the longest alternative's
- * position count, and the walk and the seam kernel close the state over the optional positions (find_opt_masks). */
+ * position count, and the walk and the seam kernel close the state over the optional positions (find_opt_masks).
+ * expr is NULL but for the expr calls where they cross those three: optional positions with a tested byte behind a match,
+ * and two terms or more with an optional position or an anchor.  Then opt is expr's (its masks 0 without an optional
+ * position), and the walk and the seam kernel are the ones with the closure, the seam kernel's with the data's end. */
 struct FindKey {
     const char *who, *key_name;
     const uint8_t *key;
@@ -100,6 +104,7 @@ struct FindKey {
     const FindAncCall *anc;
     FindTermCall *term;
     FindOptArgs *opt;
+    FindExprArgs *expr;
 };
 
 /* does the context call widen the answer: with both distances 0 it is the select call, maybe with flags */
@@ -226,7 +231,40 @@ static void find_enqueue_walk(hufgpu_ctx_t *ctx, const FindKey &k, const FindRec
 {
     const dim3 wt(FIND_THREADS), st(FIND_SEAM_THREADS);
     const bool rec = k.rec != NULL, seam = k.plen > 1;
-    if (k.term) {
+    const bool front = find_anc_front(k), third = find_anc_third(k);
+    /* the bytes' walk with the boundary set, into a mask and tile counts of its own: the same checks, so the same
+     * statuses a second time, and no word of the first walk is touched */
+    const auto third_walk = [&]() {
+        FindArgs ba = ra.p.f;
+        memset(ba.set, 0, sizeof(ba.set));
+        for (int i = 0; i < 32; i++) ba.set[i >> 2] |= (uint32_t)k.anc->front[i] << (8 * (i & 3));
+        ba.bitmap = ctx->d_fabits;
+        ba.tcnt = ctx->d_fatcnt;
+        find_sub_kernel<<<walk, wt, 0, s>>>(ba);
+    };
+    /* the byte in front of a match, over the mask and counts of `f` */
+    const auto anchor = [&](const FindArgs &f) {
+        const FindAnchorArgs fa = {f, third ? ctx->d_fabits : ra.dbits};
+        find_anchor_kernel<<<tiles, dim3(FIND_EMIT_THREADS), 0, s>>>(fa);
+    };
+    if (k.term && k.expr) {
+        /* the terms' walk with the closure; the anchors bind the outer edges: the byte behind a match is a position of the
+         * LAST term's alternatives, the byte in front is looked at for term 0's mask and counts */
+        FindExprArgs &x = *k.expr;
+        x.qa.a.r = ra;
+        x.t = k.term->t;
+        if (x.t.n_terms == 2) find_rec_term_opt_sub_kernel<2><<<walk, wt, 0, s>>>(x);
+        else if (x.t.n_terms == 3) find_rec_term_opt_sub_kernel<3><<<walk, wt, 0, s>>>(x);
+        else find_rec_term_opt_sub_kernel<FIND_TERMS_MAX><<<walk, wt, 0, s>>>(x);
+        if (third) third_walk();
+        if (seam) find_term_opt_seam_kernel<<<seams, st, 0, s>>>(x);
+        if (front) {
+            FindArgs f0 = ra.p.f;
+            f0.bitmap = x.t.mbits;
+            f0.tcnt = x.t.mcnt;
+            anchor(f0);
+        }
+    } else if (k.term) {
         /* a mask a term, and a kernel for each number of terms: a mask that is not needed still costs registers */
         k.alt->r = ra;
         const FindTermArgs ta = {*k.alt, k.term->t};
@@ -236,30 +274,21 @@ static void find_enqueue_walk(hufgpu_ctx_t *ctx, const FindKey &k, const FindRec
         if (seam) find_term_seam_kernel<<<seams, st, 0, s>>>(ta);
     } else if (k.opt) {
         k.opt->a.r = ra;
-        if (rec) find_rec_opt_sub_kernel<<<walk, wt, 0, s>>>(*k.opt);
+        /* (the expr calls, with an anchor: the records' form whenever the byte in front is tested, as below) */
+        if (rec || front) find_rec_opt_sub_kernel<<<walk, wt, 0, s>>>(*k.opt);
         else find_opt_sub_kernel<<<walk, wt, 0, s>>>(*k.opt);
-        if (seam) find_opt_seam_kernel<<<seams, st, 0, s>>>(*k.opt);
+        if (third) third_walk();
+        if (seam && k.expr) find_opt_anc_seam_kernel<<<seams, st, 0, s>>>(*k.expr);
+        else if (seam) find_opt_seam_kernel<<<seams, st, 0, s>>>(*k.opt);
+        if (front) anchor(ra.p.f);
     } else if (k.alt) {
         k.alt->r = ra;
-        const bool front = find_anc_front(k), third = find_anc_third(k);
         if (rec || front) find_rec_alt_sub_kernel<<<walk, wt, 0, s>>>(*k.alt);
         else find_alt_sub_kernel<<<walk, wt, 0, s>>>(*k.alt);
-        if (third) {
-            /* the bytes' walk with the boundary set, into a mask and tile counts of its own: the same checks, so the same
-             * statuses a second time, and no word of the first walk is touched */
-            FindArgs ba = ra.p.f;
-            memset(ba.set, 0, sizeof(ba.set));
-            for (int i = 0; i < 32; i++) ba.set[i >> 2] |= (uint32_t)k.anc->front[i] << (8 * (i & 3));
-            ba.bitmap = ctx->d_fabits;
-            ba.tcnt = ctx->d_fatcnt;
-            find_sub_kernel<<<walk, wt, 0, s>>>(ba);
-        }
+        if (third) third_walk();
         if (seam && find_anc_behind(k)) find_anc_seam_kernel<<<seams, st, 0, s>>>(*k.alt);
         else if (seam) find_alt_seam_kernel<<<seams, st, 0, s>>>(*k.alt);
-        if (front) {
-            const FindAnchorArgs fa = {ra.p.f, third ? ctx->d_fabits : ra.dbits};
-            find_anchor_kernel<<<tiles, dim3(FIND_EMIT_THREADS), 0, s>>>(fa);
-        }
+        if (front) anchor(ra.p.f);
     } else if (k.cls) {
         const FindClsArgs ca = {ra, *k.cls};
         if (rec) find_rec_cls_sub_kernel<<<walk, wt, 0, s>>>(ca);
@@ -503,9 +532,10 @@ extern "C" int hufgpu_find_records_classes(hufgpu_ctx_t *ctx, const void *d_stre
  * find_table_add's - and their table (kernels/find.hpp, FindAltArgs: alternative 0 at the bits 63 ... 64 - len_0,
  * alternative 1 below it).  `classes` and `alt_lens` are not NULL; the total is looked at before `classes` is read.
  * *maxlen: the longest alternative's length.  `behind` (the anchored calls): every alternative gets one position more, that
- * class, which takes a bit of the state and counts into *maxlen. */
+ * class, which takes a bit of the state and counts into *maxlen.  `bfrom` (the expr call's ordered terms): the alternatives
+ * from that one on only - the last term's. */
 static int find_alt_table(hufgpu_ctx_t *ctx, const char *who, const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
-                          const uint8_t *delim_set, FindAltArgs *t, uint32_t *maxlen, const uint8_t *behind = NULL)
+                          const uint8_t *delim_set, FindAltArgs *t, uint32_t *maxlen, const uint8_t *behind = NULL, uint32_t bfrom = 0)
 {
     if (n_alts == 0 || n_alts > HUFGPU_FIND_PATTERN_MAX)
         return find_bad(ctx, "%s: n_alts %u is not 1 to %d", who, n_alts, HUFGPU_FIND_PATTERN_MAX);
@@ -517,18 +547,22 @@ static int find_alt_table(hufgpu_ctx_t *ctx, const char *who, const uint8_t *cla
     if (total > HUFGPU_FIND_PATTERN_MAX)
         return find_bad(ctx, "%s: the lengths of the %u alternatives sum to %llu, above %d", who, n_alts, (unsigned long long)total,
                         HUFGPU_FIND_PATTERN_MAX);
-    if (behind && total + n_alts > HUFGPU_FIND_PATTERN_MAX)
+    if (behind && bfrom == 0 && total + n_alts > HUFGPU_FIND_PATTERN_MAX)
         return find_bad(ctx, "%s: the lengths of the %u alternatives and one boundary position each sum to %llu, above %d", who, n_alts,
                         (unsigned long long)(total + n_alts), HUFGPU_FIND_PATTERN_MAX);
+    if (behind && bfrom != 0 && total + (n_alts - bfrom) > HUFGPU_FIND_PATTERN_MAX)
+        return find_bad(ctx, "%s: the lengths of the %u alternatives and one boundary position for each of the last term's %u sum to %llu, above %d",
+                        who, n_alts, n_alts - bfrom, (unsigned long long)(total + (n_alts - bfrom)), HUFGPU_FIND_PATTERN_MAX);
     memset(t, 0, sizeof(*t));
     t->n_alts = n_alts;
     *maxlen = 0;
     uint32_t hi = 63;
     for (uint32_t j = 0; j < n_alts; j++) {
-        const uint32_t len = alt_lens[j], bits = len + (behind ? 1u : 0u);
+        const uint8_t *bj = j >= bfrom ? behind : NULL;
+        const uint32_t len = alt_lens[j], bits = len + (bj ? 1u : 0u);
         char of[32];
         snprintf(of, sizeof(of), "alternative %u", j);
-        if (find_table_add(ctx, who, of, classes, len, hi, delim_set, &t->t, behind)) return HUFE_ARGUMENT;
+        if (find_table_add(ctx, who, of, classes, len, hi, delim_set, &t->t, bj)) return HUFE_ARGUMENT;
         t->starts[hi >> 5] |= 1u << (hi & 31u);
         t->hl[j] = (uint16_t)(hi | (bits << 8));
         if (bits > *maxlen) *maxlen = bits;
@@ -558,9 +592,11 @@ static void find_term_split(FindAltArgs *t, const uint32_t *alt_lens, const uint
 /* The quant calls' own checks, behind find_alt_table's: an `optional` byte that is neither 0 nor 1, an alternative whose
  * positions are all optional.  Then, next to the table that find_alt_table has made in q->a, the three masks of
  * kernels/find.hpp's FindOpt and the wider `first`; *any: is there an optional position at all - without one the call is
- * the any-of call.  `optional` has one byte a position, in the order of `classes`. */
+ * the any-of call.  `optional` has one byte a position, in the order of `classes`.  `bfrom` (the expr calls): the alternatives
+ * from that one on have a boundary position behind their own, a required one that `optional` has no byte for - so no run of
+ * optional positions ends such an alternative, and its bit in `first` is the boundary's alone. */
 static int find_opt_masks(hufgpu_ctx_t *ctx, const char *who, const uint32_t *alt_lens, uint32_t n_alts, const uint8_t *optional,
-                          FindOptArgs *q, bool *any)
+                          FindOptArgs *q, bool *any, uint32_t bfrom = ~0u)
 {
     const uint8_t *op = optional;
     for (uint32_t j = 0; j < n_alts; op += alt_lens[j++]) {
@@ -577,14 +613,15 @@ static int find_opt_masks(hufgpu_ctx_t *ctx, const char *who, const uint32_t *al
     uint64_t first = 0, O = 0, I = 0, F = 0;
     op = optional;
     for (uint32_t j = 0; j < n_alts; op += alt_lens[j++]) {
-        const uint32_t hi = q->a.hl[j] & 63u, len = alt_lens[j];
+        const uint32_t hi = q->a.hl[j] & 63u, own = alt_lens[j], len = own + (j >= bfrom ? 1u : 0u);
+        const auto opt = [&](uint32_t at) { return at < own && op[at] != 0; };
         uint32_t k = len - 1u;                                      /* the positions that may hold a form's last byte */
         first |= 1ull << (hi - k);
-        while (op[k]) first |= 1ull << (hi - --k);                  /* (a required position stops it) */
+        while (opt(k)) first |= 1ull << (hi - --k);                 /* (a required position stops it) */
         for (k = 0; k < len; k++) {
-            if (!op[k]) continue;
+            if (!opt(k)) continue;
             const uint32_t top = k;
-            while (k + 1u < len && op[k + 1u]) k++;
+            while (opt(k + 1u)) k++;
             uint32_t low = k;                                       /* the maximal run top ... low */
             if (low == len - 1u) {                                  /* it ends the alternative: its lowest bit is its i, set by `first` */
                 if (top == low) continue;
@@ -607,16 +644,40 @@ static int find_alt_call(hufgpu_ctx_t *ctx, const char *who, const FindStream &i
                          uint32_t flags, void *stream, const FindAncCall *anc = NULL, FindTermCall *term = NULL,
                          const uint32_t *term_alts = NULL, const uint8_t *optional = NULL)
 {
-    FindOptArgs q;
+    FindExprArgs x;                         /* (the older calls use its FindOptArgs, or that one's FindAltArgs, and nothing else) */
+    FindOptArgs &q = x.qa;
     FindAltArgs &t = q.a;
     uint32_t maxlen = 0;
     bool quant = false;
     const bool both = classes && alt_lens;
     const uint8_t *behind = anc && (anc->anchors & (HUFGPU_ANCHOR_EOL | HUFGPU_ANCHOR_WORD)) ? anc->behind : NULL;
-    if (both && find_alt_table(ctx, who, classes, alt_lens, n_alts, rec ? rec->delim_set : NULL, &t, &maxlen, behind)) return HUFE_ARGUMENT;
+    /* anchors bind the outer edges of ordered terms: the byte behind a match is the last term's */
+    const uint32_t bfrom = behind && term && term_alts ? n_alts - term_alts[term->t.n_terms - 1u] : 0u;
+    if (both && find_alt_table(ctx, who, classes, alt_lens, n_alts, rec ? rec->delim_set : NULL, &t, &maxlen, behind, bfrom)) return HUFE_ARGUMENT;
     if (both && term) find_term_split(&t, alt_lens, term_alts, term);
-    if (both && optional && find_opt_masks(ctx, who, alt_lens, n_alts, optional, &q, &quant)) return HUFE_ARGUMENT;
-    const FindKey k = {who, "classes, alt_lens", both ? classes : NULL, maxlen, rec, &t.t, &t, sel, cx, anc, term, quant ? &q : NULL};
+    q.q = {};
+    if (both && optional && find_opt_masks(ctx, who, alt_lens, n_alts, optional, &q, &quant, behind ? bfrom : ~0u)) return HUFE_ARGUMENT;
+    if (both && optional && term && term->ordered) {               /* find_rec_seq_kernel needs every term's end but the last one's */
+        const uint8_t *op = optional;
+        for (uint32_t tq = 0, j = 0; tq + 1u < term->t.n_terms; tq++) {
+            for (const uint32_t end = j + term_alts[tq]; j < end; op += alt_lens[j++]) {
+                for (uint32_t i = 0; i < alt_lens[j]; i++) {
+                    if (op[i])
+                        return find_bad(ctx, "%s: position %u of alternative %u, in term %u, is optional: an ordered call allows optional positions in its last term only",
+                                        who, i, j, tq);
+                }
+            }
+        }
+    }
+    /* where the call crosses what the older ones keep apart: the kernels with the closure and the data's end */
+    const bool cross = both && (term ? (quant || anc) : (quant && behind));
+    x.bnd[0] = x.bnd[1] = 0;
+    for (uint32_t j = bfrom; cross && behind && j < n_alts; j++) {
+        const uint32_t bit = (t.hl[j] & 63u) - alt_lens[j];
+        x.bnd[bit >> 5] |= 1u << (bit & 31u);
+    }
+    const FindKey k = {who, "classes, alt_lens", both ? classes : NULL, maxlen, rec, &t.t, &t, sel, cx, anc, term,
+                       quant || cross ? &q : NULL, cross ? &x : NULL};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -766,10 +827,10 @@ extern "C" int hufgpu_find_records_anchored(hufgpu_ctx_t *ctx, const void *d_str
 
 /* hufgpu_find_records_terms' own checks, behind the `select` check and in front of the older calls': the mode, the array,
  * the number of terms, a term without alternatives, counts that do not sum to n_alts and - ordered - a term whose
- * alternatives differ in length.  The lengths are looked at only where the older checks would read them too: both arrays
+ * alternatives differ in length (last_free, the expr call: but for the last term, whose end no kernel needs).  The lengths are looked at only where the older checks would read them too: both arrays
  * there and n_alts within its bounds; whatever else is wrong with them is the older checks' to word. */
 static int find_term_check(hufgpu_ctx_t *ctx, const char *who, const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
-                           const uint32_t *term_alts, uint32_t n_terms, uint32_t terms_mode)
+                           const uint32_t *term_alts, uint32_t n_terms, uint32_t terms_mode, bool last_free = false)
 {
     if (terms_mode > HUFGPU_TERMS_ORDERED)
         return find_bad(ctx, "%s: terms_mode %u is neither HUFGPU_TERMS_ALL (0) nor HUFGPU_TERMS_ORDERED (1)", who, terms_mode);
@@ -784,7 +845,7 @@ static int find_term_check(hufgpu_ctx_t *ctx, const char *who, const uint8_t *cl
     if (total != n_alts)
         return find_bad(ctx, "%s: the %u terms have %llu alternatives, and n_alts is %u", who, n_terms, (unsigned long long)total, n_alts);
     if (terms_mode != HUFGPU_TERMS_ORDERED || !classes || !alt_lens || n_alts > HUFGPU_FIND_PATTERN_MAX) return HUFE_OK;
-    for (uint32_t t = 0, j = 0; t < n_terms; j += term_alts[t++]) {
+    for (uint32_t t = 0, j = 0; t + (last_free ? 1u : 0u) < n_terms; j += term_alts[t++]) {
         for (uint32_t i = 1; i < term_alts[t]; i++) {
             if (alt_lens[j + i] != alt_lens[j])
                 return find_bad(ctx, "%s: the alternatives of term %u have the lengths %u and %u: an ordered call needs one length a term",
@@ -817,4 +878,51 @@ extern "C" int hufgpu_find_records_terms(hufgpu_ctx_t *ctx, const void *d_stream
     term.ordered = terms_mode == HUFGPU_TERMS_ORDERED;
     return find_alt_call(ctx, "find_records_terms", in, out, classes, alt_lens, n_alts, &rec, &sel, plain ? NULL : &cx, flags, stream, NULL,
                          n_terms > 1 ? &term : NULL, term_alts);              /* (one term: the context call, by its launches) */
+}
+
+extern "C" int hufgpu_find_any_expr(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                    uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                    const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts, const uint8_t *optional,
+                                    const uint8_t delim_set[32], const uint8_t word_set[32], uint32_t anchors, uint64_t *d_pos,
+                                    uint64_t pos_cap, uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                                    uint32_t flags, void *stream)
+{
+    FindAncCall anc;
+    if (anchors && find_anc_sets(ctx, "find_any_expr", anchors, delim_set, word_set, false, &anc)) return HUFE_ARGUMENT;
+    const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
+    const FindOut out = {d_pos, pos_cap, d_block_counts, d_totals, d_block_errs};
+    return find_alt_call(ctx, "find_any_expr", in, out, classes, alt_lens, n_alts, NULL, NULL, NULL, flags, stream, anchors ? &anc : NULL, NULL,
+                         NULL, optional);
+}
+
+/* hufgpu_find_records_expr: the `select` check, the anchored calls' checks, the terms call's - an ordered call's last term
+ * may have alternatives of several lengths -, then anchors with ALL of several terms; find_alt_call has the rest. */
+extern "C" int hufgpu_find_records_expr(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                        uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                        const uint8_t delim_set[32], const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts,
+                                        const uint8_t *optional, const uint32_t *term_alts, uint32_t n_terms, uint32_t terms_mode,
+                                        const uint8_t word_set[32], uint32_t anchors, uint32_t select, uint32_t before, uint32_t after,
+                                        uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no, uint8_t *d_rec_sel, uint64_t rec_cap,
+                                        uint32_t max_len, uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                                        uint32_t flags, void *stream)
+{
+    const char *who = "find_records_expr";
+    if (select & ~HUFGPU_SELECT_INVERT) return find_bad(ctx, "%s: select 0x%x has a bit other than HUFGPU_SELECT_INVERT", who, select);
+    FindAncCall anc;
+    if (anchors && find_anc_sets(ctx, who, anchors, delim_set, word_set, true, &anc)) return HUFE_ARGUMENT;
+    if (find_term_check(ctx, who, classes, alt_lens, n_alts, term_alts, n_terms, terms_mode, true)) return HUFE_ARGUMENT;
+    if (terms_mode == HUFGPU_TERMS_ALL && n_terms > 1 && anchors)
+        return find_bad(ctx, "%s: anchors 0x%x with HUFGPU_TERMS_ALL of %u terms: anchors need one term or HUFGPU_TERMS_ORDERED", who, anchors, n_terms);
+    const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
+    const FindOut out = {d_rec_pos, rec_cap, d_block_counts, d_totals, d_block_errs};
+    const FindRecCall rec = {delim_set, d_rec_len, max_len};
+    const FindSelCall sel = {select, d_rec_no};
+    const FindCtxCall cx = {before, after, d_rec_sel};
+    const bool plain = (before | after) == 0u && !d_rec_sel;        /* the select call, by its launches */
+    FindTermCall term;
+    memset(&term, 0, sizeof(term));
+    term.t.n_terms = n_terms;
+    term.ordered = terms_mode == HUFGPU_TERMS_ORDERED;
+    return find_alt_call(ctx, who, in, out, classes, alt_lens, n_alts, &rec, &sel, plain ? NULL : &cx, flags, stream, anchors ? &anc : NULL,
+                         n_terms > 1 ? &term : NULL, term_alts, optional);
 }

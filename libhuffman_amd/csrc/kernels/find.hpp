@@ -38,9 +38,17 @@
                                    positions a byte (find_opt_step); the seam kernel runs it on a window of the edge bytes in LDS
    hufgpu_find_records_quant       no optional position: the context call's chain.  Else find_rec_opt_sub -> find_opt_seam in
                                    the place of find_rec_alt_sub -> find_alt_seam, then that chain as it is
+   hufgpu_find_any_expr            one of anchors and optional positions alone: the anchored call's, the quant call's chain.
+                                   Both: find_opt_sub - find_rec_opt_sub when the byte in front is tested - and, with EOL / WORD,
+                                   find_opt_anc_seam in the place of find_opt_seam: the window with the end of the data as a
+                                   boundary; BOL / WORD: find_anchor behind the seam kernel
+   hufgpu_find_records_expr        one term: as the positions call, on the context call's chain (WORD: find_sub a second time).
+                                   2 to 4 terms without an optional position or an anchor: the terms call's chain.  Else
+                                   find_rec_term_opt_sub -> find_term_opt_seam in the place of find_rec_term_sub -> find_term_seam,
+                                   and - ORDERED with BOL / WORD - find_anchor over term 0's mask in front of dscan / mark
    RECORDS = find_rec_dscan -> find_rec_mark -> find_scan -> find_finish [-> find_rec_emit]; no seam kernel for 1 byte
 
-   The walk: find_sub_body, the nine *_sub kernels and find_rec_term_sub_kernel
+   The walk: find_sub_body, the nine *_sub kernels, find_rec_term_sub_kernel and find_rec_term_opt_sub_kernel
      Workgroup = one (block, chunk of 65 536 symbols), decode_sub_kernel's geometry with eight waves; a wave takes the
      chunk's tiles wave, wave + 8, ...  The header is parsed and its length must be the layout's, the tables come from
      dsub_fast_tables (the claimed code lengths checked against the stream's tree), and EVERY tile of EVERY chunk is the
@@ -350,19 +358,35 @@ struct FindOptArgs {
 };
 static_assert(sizeof(FindOptArgs) == sizeof(FindAltArgs) + 24 && sizeof(FindOptArgs) <= 4096, "a kernel's arguments end at 4 KiB");
 
+/* hufgpu_find_any_expr / hufgpu_find_records_expr, where they cross what the older calls keep apart: optional positions
+ * in a table with boundary positions (anchors), in several terms, or anchors around ordered terms.  qa is the quant calls'
+ * - with no optional position its three masks are 0 and find_opt_step is find_cls_step -, t the terms' (n_terms = 0: one
+ * term, and the one mask and count of qa.a.r.p.f), and bnd has the bits of the BOUNDARY positions: those of every alternative
+ * whose byte behind a match is tested, which the seam kernel takes as met where the data ends. */
+struct FindExprArgs {
+    FindOptArgs qa;
+    uint32_t bnd[2];                        /* ([0] the low half) */
+    FindTerms t;
+};
+static_assert(sizeof(FindTermArgs) + sizeof(FindOpt) <= 4096 && sizeof(FindExprArgs) <= 4096, "a kernel's arguments end at 4 KiB");
+
 /* find_cls_step and the closure over the optional positions (Navarro and Raffinot's extended patterns): a set bit just
  * below or inside a run of optional positions sets every bit of the run above it - "those positions are left out".
  * Df - I clears the lowest set bit of every block i ... f and sets the bits below it, so ~(Df - I) ^ Df has exactly the bits
  * above that lowest one; f bounds the borrow.  One subtraction with borrow out, one with borrow in, four logic operations a
  * half; o, i and f are the kernel's arguments, the same for every lane. */
-__device__ __forceinline__ void find_opt_step(uint32_t &lo, uint32_t &hi, const uint32_t *s_m, uint32_t first_lo, uint32_t first_hi, uint32_t x,
-                                              const FindOpt &q)
+__device__ __forceinline__ void find_opt_close(uint32_t &lo, uint32_t &hi, const FindOpt &q)
 {
-    find_cls_step(lo, hi, s_m, first_lo, first_hi, x);
     const uint32_t dl = lo | q.f[0], dh = hi | q.f[1];
     const uint64_t d = (((uint64_t)dh << 32) | dl) - (((uint64_t)q.i[1] << 32) | q.i[0]);
     lo |= q.o[0] & (~(uint32_t)d ^ dl);
     hi |= q.o[1] & (~(uint32_t)(d >> 32) ^ dh);
+}
+__device__ __forceinline__ void find_opt_step(uint32_t &lo, uint32_t &hi, const uint32_t *s_m, uint32_t first_lo, uint32_t first_hi, uint32_t x,
+                                              const FindOpt &q)
+{
+    find_cls_step(lo, hi, s_m, first_lo, first_hi, x);
+    find_opt_close(lo, hi, q);
 }
 
 /* the automaton's step of a walk: OPT, the one with the closure */
@@ -418,17 +442,18 @@ __device__ __forceinline__ uint32_t find_cls_lane(const uint32_t *tile_words, co
 }
 
 /* find_cls_lane<true> with a mask word a TERM: the automaton is the same one, and in the place of "any start bit" the lane
- * asks NT times "a start bit of term t".  NT, the number of terms, is the kernel's at compile time: the masks stay in registers. */
-template <uint32_t NT>
+ * asks NT times "a start bit of term t".  NT, the number of terms, is the kernel's at compile time: the masks stay in registers.
+ * OPT (the expr call): the step is find_opt_step, as in find_cls_lane<true, true>. */
+template <uint32_t NT, bool OPT = false>
 __device__ __forceinline__ void find_term_lane(const uint32_t *tile_words, const uint32_t (&w)[8], const uint32_t *s_m, uint32_t first_lo,
                                                uint32_t first_hi, uint32_t plen, uint32_t tsym, uint32_t lane, const FindTerms &tm,
-                                               uint32_t (&m)[NT])
+                                               uint32_t (&m)[NT], [[maybe_unused]] const FindOpt *q = nullptr)
 {
     uint32_t lo = 0, hi = 0;
     for (uint32_t k = (plen + 2u) >> 2; k-- > 0u;) {                /* the words that hold the plen - 1 bytes behind the lane's */
         const uint32_t x = tile_words[dmin<uint32_t>(8u * lane + 8u + k, HUF_SUB_TILE / 4 - 1u)];
 #pragma unroll
-        for (int i = 3; i >= 0; i--) find_cls_step(lo, hi, s_m, first_lo, first_hi, (x >> (8 * i)) & 0xffu);
+        for (int i = 3; i >= 0; i--) find_step<OPT>(lo, hi, s_m, first_lo, first_hi, (x >> (8 * i)) & 0xffu, q);
     }
 #pragma unroll
     for (uint32_t t = 0; t < NT; t++) m[t] = 0;
@@ -436,7 +461,7 @@ __device__ __forceinline__ void find_term_lane(const uint32_t *tile_words, const
     for (int j = 7; j >= 0; j--) {
 #pragma unroll
         for (int i = 3; i >= 0; i--) {
-            find_cls_step(lo, hi, s_m, first_lo, first_hi, (w[j] >> (8 * i)) & 0xffu);
+            find_step<OPT>(lo, hi, s_m, first_lo, first_hi, (w[j] >> (8 * i)) & 0xffu, q);
 #pragma unroll
             for (uint32_t t = 0; t < NT; t++) m[t] = (m[t] << 1) | dmin<uint32_t>((hi & tm.starts[t][1]) | (lo & tm.starts[t][0]), 1u);
         }
@@ -453,13 +478,14 @@ __device__ __forceinline__ void find_term_lane(const uint32_t *tile_words, const
  * the longest one's length.  NT != 0 (find_rec_term_sub_kernel): the alternatives stand in NT terms, and what leaves the
  * workgroup is a match mask word a group and a count a tile for every TERM, into tm's term-major arrays, in the place of the one
  * mask and count: the delimiter mask, the edges, the checks and the status are as they are.  OPT (find_opt_sub_kernel,
- * find_rec_opt_sub_kernel): the any-of walk with find_opt_step and q's masks in the place of find_cls_step. */
+ * find_rec_opt_sub_kernel): the any-of walk with find_opt_step and q's masks in the place of find_cls_step; with NT
+ * (find_rec_term_opt_sub_kernel) the terms' walk with it. */
 template <bool PAT, bool REC = false, bool CLS = false, bool ALT = false, uint32_t NT = 0, bool OPT = false>
 __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatArgs *p, const FindRecArgs *r = nullptr, const FindClsTable *ct = nullptr,
                                               [[maybe_unused]] const FindAltArgs *alt = nullptr, [[maybe_unused]] const FindTerms *tm = nullptr,
                                               [[maybe_unused]] const FindOpt *q = nullptr)
 {
-    static_assert(!OPT || (ALT && NT == 0), "optional positions: the any-of route's, one term");
+    static_assert(!OPT || ALT, "optional positions: the any-of route's");
     static_assert(PAT || !REC, "the records' route is the pattern's");
     static_assert(NT == 0 || (ALT && REC && NT <= FIND_TERMS_MAX), "the terms' route is the any-of records'");
     static_assert(PAT || !CLS, "the classes' route is the pattern's");
@@ -600,7 +626,7 @@ __device__ __forceinline__ void find_sub_body(const FindArgs &a, const FindPatAr
         [[maybe_unused]] uint32_t mt[NT ? NT : 1];
         if constexpr (PAT) {
             const uint32_t tsym = find_tile_syms(blen, t), plen = p->plen;
-            if constexpr (NT != 0) find_term_lane<NT>(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane, *tm, mt);
+            if constexpr (NT != 0) find_term_lane<NT, OPT>(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane, *tm, mt, q);
             else if constexpr (OPT) m = find_cls_lane<true, true>(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane, alt->starts[0], alt->starts[1], q);
             else if constexpr (ALT) m = find_cls_lane<true>(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane, alt->starts[0], alt->starts[1]);
             else if constexpr (CLS) m = find_cls_lane(tile_words, w, s_set, ct->first[0], ct->first[1], plen, tsym, lane);
@@ -678,6 +704,13 @@ template <uint32_t NT>
 __global__ __launch_bounds__(FIND_THREADS) void find_rec_term_sub_kernel(FindTermArgs ta)
 {
     find_sub_body<true, true, true, true, NT>(ta.a.r.p.f, &ta.a.r.p, &ta.a.r, &ta.a.t, &ta.a, &ta.t);
+}
+
+/* hufgpu_find_records_expr with two terms or more and an optional position or an anchor: the terms' walk with the closure */
+template <uint32_t NT>
+__global__ __launch_bounds__(FIND_THREADS) void find_rec_term_opt_sub_kernel(FindExprArgs xa)
+{
+    find_sub_body<true, true, true, true, NT, true>(xa.qa.a.r.p.f, &xa.qa.a.r.p, &xa.qa.a.r, &xa.qa.a.t, &xa.qa.a, &xa.t, &xa.qa.q);
 }
 
 /* ---- the seams: the matches that leave their tile (launched for plen >= 2 only) ---------------------------------------- */
@@ -862,7 +895,9 @@ __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_term_seam_kernel(FindT
  * The wave copies its window once - the tile's tail slot, then the heads of the tiles behind it over the layout's tile
  * lengths, up to raw_size or the first block that is not served: at most 63 + 63 bytes, `filled` of them - into LDS, and
  * every lane runs its at most plen steps on LDS bytes.  One bit and one count a start through find_seam_end. */
-__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_opt_seam_kernel(FindOptArgs qa)
+template <bool SEED, bool TERMS>
+__device__ __forceinline__ void find_win_seam_body(const FindOptArgs &qa, [[maybe_unused]] const uint32_t *bnd = nullptr,
+                                                   [[maybe_unused]] const FindTerms *tm = nullptr)
 {
     __shared__ uint32_t s_key[FIND_CLS_WORDS];
     __shared__ uint8_t s_win[FIND_SEAM_THREADS / 64][FIND_EDGE_SLOT];
@@ -895,15 +930,45 @@ __global__ __launch_bounds__(FIND_SEAM_THREADS) void find_opt_seam_kernel(FindOp
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");           /* the window is in LDS before other lanes read it */
     __builtin_amdgcn_wave_barrier();
-    bool hit = false;
+    uint32_t lo = 0, hi = 0;
     if (m.lane < m.ne) {
-        uint32_t lo = 0, hi = 0;
+        if constexpr (SEED) {
+            /* The window ends where the DATA ends - not at a block that is not served, which lies in front of raw_size, and
+             * not at `want` short of it - and the lane's scan begins there: a form that ends at raw_size has nothing behind
+             * it, which meets its boundary position.  So the scan starts from "the boundary positions are met", closed over
+             * the optional positions in front of them (a form may leave those out), in the place of the empty state.  A seed
+             * bit stands for a boundary position and for optional positions that a form drops: for no byte.  Every position
+             * above them is reached by find_opt_step alone, one byte of the window each, and the window holds no byte from
+             * raw_size on - so no form that needs a byte behind the data gets its start bit. */
+            const uint64_t wend = m.pos - m.lane + filled;          /* (m.pos - m.lane: the window's first byte) */
+            if (wend == a.s.raw_size && m.lane + pa.plen > filled) {
+                lo = bnd[0];
+                hi = bnd[1];
+                find_opt_close(lo, hi, qa.q);
+            }
+        }
         for (uint32_t k = dmin<uint32_t>(m.lane + pa.plen, filled); k-- > m.lane;)
             find_opt_step(lo, hi, s_key, aa.t.first[0], aa.t.first[1], win[k], qa.q);
-        hit = ((hi & aa.starts[1]) | (lo & aa.starts[0])) != 0u;
     }
-    find_seam_end(a, m, hit);
+    if constexpr (TERMS) {                                          /* a hit a term, read off the term's start bits */
+        for (uint32_t t = 0; t < tm->n_terms; t++) {
+            FindArgs f = a;
+            f.bitmap = tm->mbits + t * tm->nwords;
+            f.tcnt = tm->mcnt + t * a.ntiles;
+            find_seam_end(f, m, ((hi & tm->starts[t][1]) | (lo & tm->starts[t][0])) != 0u);
+        }
+    } else {
+        find_seam_end(a, m, ((hi & aa.starts[1]) | (lo & aa.starts[0])) != 0u);
+    }
 }
+__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_opt_seam_kernel(FindOptArgs qa) { find_win_seam_body<false, false>(qa); }
+
+/* The expr calls' seam kernels: find_opt_seam_kernel's window, with the end of the data as a boundary (SEED, above) - a
+ * form that ends exactly at raw_size has its start among its tile's last plen - 1, as plen counts the boundary position -
+ * and, for two terms or more, find_term_seam_kernel in window form: the automaton runs ONCE a lane whatever the number of
+ * alternatives, and find_seam_end runs once a term. */
+__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_opt_anc_seam_kernel(FindExprArgs xa) { find_win_seam_body<true, false>(xa.qa, xa.bnd); }
+__global__ __launch_bounds__(FIND_SEAM_THREADS) void find_term_opt_seam_kernel(FindExprArgs xa) { find_win_seam_body<true, true>(xa.qa, xa.bnd, &xa.t); }
 
 /* The anchored calls with HUFGPU_ANCHOR_BOL or HUFGPU_ANCHOR_WORD, behind the seam kernel and in front of everything that
  * reads the match mask: a wave = one tile, a lane = one word.  `bound` is a mask of the walk's, a bit a byte: may this byte
