@@ -345,7 +345,12 @@ int hufgpu_gather(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
  * 2 048 bytes) - return HUF_ERROR_INVALID_ARGUMENT before anything is enqueued.  nblocks = 0 (with raw_size = 0) is
  * success: d_totals is zeroed and nothing else is enqueued.  The workspaces are the context's, sized by the layout and
  * doubled when they grow (only then does the call wait); two calls back to back on one stream are safe, calls on different
- * streams of one context are not.
+ * streams of one context are not.  The enqueue-only calls - this one and the rest of the search family, hufgpu_gather(),
+ * hufgpu_histogram(), and hufgpu_encode() / hufgpu_encode_sub() / hufgpu_decode() / hufgpu_decode_sub() without their host
+ * result pointer - may be captured into a graph on a non-default stream once a call of the same sizes has made the
+ * workspaces: the graph carries the whole call and may be replayed on other contents of the same buffers.  "Never waits"
+ * is the call's own promise: the first launch of one of its kernels on a stream that has not run it may wait inside the
+ * runtime (seen: 1.5 ms, once more than 20 ms, for the decoders that use scratch memory).
  */
 int hufgpu_find_bytes(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
                       const uint64_t *d_block_offsets, uint64_t nblocks,

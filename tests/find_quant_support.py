@@ -87,7 +87,7 @@ def call(lib, name, **kw):
 
 # ---- guarded device buffers --------------------------------------------------------------------------------------------------
 def quant_call(torch, codec, enc, name, alternatives, cap, delims=b"\n", max_len=0, invert=False, before=0, after=0, numbers=True,
-               flags=True, counts=True, sub=None, optional="as the pattern says"):
+               flags=True, counts=True, sub=None, optional="as the pattern says", fetch=True):
     """one call as tests/find_support.py's find_call makes the older ones: guarded buffers - LEAD guard words in front, `cap`
     slots, TAIL behind - for every output the call has, the 7-tuple of host arrays back.  `optional`: None or bytes in the
     place of the pattern's own flags"""
@@ -117,7 +117,7 @@ def quant_call(torch, codec, enc, name, alternatives, cap, delims=b"\n", max_len
                   totals=totals.data_ptr(), errs=errs.data_ptr(), flags=0, hip_stream=codec._stream())
     codec._check(invoke(codec.lib, name, values), "Failed to enqueue the search")
 
-    def host(t):
-        return None if t is None else t.cpu().numpy()
-
-    return (host(pbuf), host(lbuf), host(totals), host(errs), host(cnt), host(nbuf), host(sbuf))
+    bufs = (pbuf, lbuf, totals, errs, cnt, nbuf, sbuf)
+    if not fetch:                       # the device tensors, without a wait: find_support's find_fetch brings them to the host
+        return bufs
+    return tuple(None if t is None else t.cpu().numpy() for t in bufs)

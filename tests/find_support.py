@@ -209,20 +209,23 @@ def payload_start(enc, b):
 METHODS = ("find_bytes", "find_pattern", "find_records")
 
 
-def find_call(torch, codec, enc, name, key, cap, delims=b"\n", words=W, anchors=0, max_len=0, invert=False, before=0, after=0,
-              numbers=None, flags=None, counts=True, sub=None, raw_size=None, blocksize=None, **kw):
+def find_enqueue(torch, codec, enc, name, key, cap, delims=b"\n", words=W, anchors=0, max_len=0, invert=False, before=0, after=0,
+                 numbers=None, flags=None, counts=True, sub=None, raw_size=None, blocksize=None, **kw):
     """One call with guarded output buffers - LEAD guard words in front, `cap` slots, TAIL behind, all filled with the guard -
-    for exactly the outputs the call has; returns the 7-tuple of host arrays.
+    for exactly the outputs the call has; returns the 7-tuple of device tensors without a wait (find_fetch brings it to the
+    host), so that the call can stand behind a gate or in a captured graph (tests/test_gpu_streams.py).
 
     `name` is a GpuCodec method - find_bytes, find_pattern, find_records - which picks the C call by the type of `key` (values,
     a literal, classes, an AnyOf) and by `kw` (ignore_case, relaxed, ...); `numbers` there is line_numbers=True with a third
     buffer.  Or it is one of the C calls of tests/find_calls.py that take the any-of table: `key` is the list of alternatives
     and the call is made as the table spells it; `numbers` and `flags` (default: given wherever the call has them) are live
-    buffers at cap 0 as well, where d_rec_pos and d_rec_len are NULL."""
+    buffers at cap 0 as well, where d_rec_pos and d_rec_len are NULL.  With `direct=True` a name that both have means the C
+    call, and `key` is what that call looks for: byte values, a literal, a list of classes or the list of alternatives."""
+    direct = kw.pop("direct", False)
     sub = enc.sub if sub is None else sub
     raw_size = enc.raw_size if raw_size is None else raw_size
     blocksize = enc.row_bs if blocksize is None else blocksize
-    by_method = name in METHODS
+    by_method = name in METHODS and not direct
     slots = () if by_method else CALLS[name]
     has_lengths = name == "find_records" or "rlens" in slots
     if by_method:
@@ -250,7 +253,15 @@ def find_call(torch, codec, enc, name, key, cap, delims=b"\n", words=W, anchors=
                                                         out=pbuf[LEAD:LEAD + cap] if cap else None, **kw)
     else:
         assert not kw, kw
-        classes, lens = GpuCodec.alt_classes(AnyOf(*key))
+        if "lens" in slots:
+            classes, lens = GpuCodec.alt_classes(AnyOf(*key))
+            looked_for = dict(cls=classes.tobytes(), lens=lens.tobytes(), n=len(lens))
+        elif "cls" in slots:
+            looked_for = dict(cls=GpuCodec.byte_classes(key).tobytes(), plen=len(key))
+        elif "pattern" in slots:
+            looked_for = dict(pattern=bytes(key), plen=len(key))
+        else:
+            looked_for = dict(st=GpuCodec.byte_set(key))
         totals = torch.empty(4, dtype=torch.int64, device="cuda")
         errs = torch.empty(enc.nb, dtype=torch.int32, device="cuda")
         cnt = torch.empty(enc.nb, dtype=torch.int64, device="cuda") if counts else None
@@ -259,7 +270,7 @@ def find_call(torch, codec, enc, name, key, cap, delims=b"\n", words=W, anchors=
             return None if buf is None else buf[LEAD:].data_ptr()
 
         values = dict(ctx=codec._ctx, stream=enc.stream.data_ptr(), stream_len=enc.length, index=enc.offsets.data_ptr(), nblocks=enc.nb,
-                      sub=sub.data_ptr(), raw_size=raw_size, blocksize=blocksize, cls=classes.tobytes(), lens=lens.tobytes(), n=len(lens),
+                      sub=sub.data_ptr(), raw_size=raw_size, blocksize=blocksize, **looked_for,
                       delims=None if delims is None else GpuCodec.byte_set(delims),
                       words=None if words is None else GpuCodec.byte_set(words), anchors=anchors, select=1 if invert else 0,
                       before=before, after=after, pos=ptr(pbuf), rlens=ptr(lbuf), no=ptr(nbuf), sel=ptr(sbuf), cap=cap, max_len=max_len,
@@ -267,10 +278,17 @@ def find_call(torch, codec, enc, name, key, cap, delims=b"\n", words=W, anchors=
                       hip_stream=codec._stream())
         codec._check(invoke(codec.lib, name, values), "Failed to enqueue the search")
 
-    def host(t):
-        return None if t is None else t.cpu().numpy()
+    return (pbuf, lbuf, totals, errs, cnt if counts else None, nbuf, sbuf)
 
-    return (host(pbuf), host(lbuf), host(totals), host(errs), host(cnt) if counts else None, host(nbuf), host(sbuf))
+
+def find_fetch(bufs):
+    """find_enqueue's device tensors as the 7-tuple of host arrays (waits for the stream they are fetched on)"""
+    return tuple(None if t is None else t.cpu().numpy() for t in bufs)
+
+
+def find_call(torch, codec, enc, name, key, cap, **kw):
+    """find_enqueue and find_fetch in one: the call and its 7-tuple of host arrays"""
+    return find_fetch(find_enqueue(torch, codec, enc, name, key, cap, **kw))
 
 
 def positions_of(res):

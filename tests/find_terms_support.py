@@ -55,7 +55,7 @@ def call(lib, **kw):
 
 # ---- guarded device buffers --------------------------------------------------------------------------------------------------
 def terms_call(torch, codec, enc, terms, mode, cap, delims=b"\n", max_len=0, invert=False, before=0, after=0, numbers=True, flags=True,
-               counts=True, sub=None):
+               counts=True, sub=None, fetch=True):
     """one hufgpu_find_records_terms call as tests/find_support.py's find_call makes the older ones: guarded buffers - LEAD
     guard words in front, `cap` slots, TAIL behind - for every output, the 7-tuple of host arrays back"""
     from find_support import GUARD8, GUARD32, GUARD64, LEAD, TAIL as BEHIND
@@ -83,7 +83,7 @@ def terms_call(torch, codec, enc, terms, mode, cap, delims=b"\n", max_len=0, inv
                   hip_stream=codec._stream())
     codec._check(invoke(codec.lib, values), "Failed to enqueue the search")
 
-    def host(t):
-        return None if t is None else t.cpu().numpy()
-
-    return (host(pbuf), host(lbuf), host(totals), host(errs), host(cnt), host(nbuf), host(sbuf))
+    bufs = (pbuf, lbuf, totals, errs, cnt, nbuf, sbuf)
+    if not fetch:                       # the device tensors, without a wait: find_support's find_fetch brings them to the host
+        return bufs
+    return tuple(None if t is None else t.cpu().numpy() for t in bufs)

@@ -39,6 +39,42 @@ class Enc:
         return {} if self.sub is None else dict(sub_index=self.sub, raw_size=self.n, blocksize=self.bs)
 
 
+# ---- ranges ----------------------------------------------------------------------------------------------------------------
+TILE = 2048
+
+
+def touched(enc, lo, hi):
+    """first and last block of the cut range, None when it is empty"""
+    lo_c, hi_c = min(lo, enc.n), min(hi, enc.n)
+    if lo_c >= hi_c:
+        return None
+    fb = int(np.searchsorted(enc.P, lo_c, side="right")) - 1
+    lb = int(np.searchsorted(enc.P, hi_c, side="left")) - 1
+    return fb, lb
+
+
+def ranges_route_model(enc, ranges, oo):
+    """(direct, staged, tiles, items) the rule of include/huffman_gpu.h gives"""
+    cover, pairs, whole = np.zeros(enc.nb, int), np.zeros(enc.nb, int), np.zeros(enc.nb, int)
+    for i, (lo, hi) in enumerate(ranges):
+        t = touched(enc, lo, hi)
+        lo_c, hi_c = min(lo, enc.n), min(hi, enc.n)
+        if t is None or oo[i + 1] - oo[i] < hi_c - lo_c:
+            continue
+        for b in range(t[0], t[1] + 1):
+            p0, p1 = int(enc.P[b]), int(enc.P[b + 1])
+            c0, c1 = max(lo_c, p0) - p0, min(hi_c, p1) - p0
+            if c0 >= c1:
+                continue
+            cover[b] += 1
+            pairs[b] += (c1 - 1) // TILE - c0 // TILE + 1
+            whole[b] += c0 == 0 and c1 == p1 - p0
+    direct = (cover == 1) & (whole == 1)
+    rest = (cover > 0) & ~direct
+    tiles = rest & enc.elig & (pairs <= (enc.block_lens + TILE - 1) // TILE)
+    return int(direct.sum()), int((rest & ~tiles).sum()), int(tiles.sum()), int(pairs[tiles].sum())
+
+
 # ---- inputs ------------------------------------------------------------------------------------------------------------
 def by_counts(n, bs, counts, seed):
     """every block a permutation of the same multiset: value v counts[v] times (cut for a short last block)"""

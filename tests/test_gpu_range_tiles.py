@@ -10,8 +10,9 @@ import numpy as np
 import pytest
 
 from libhuffman_amd import datagen
-from stream_support import GUARD, Enc, dev, make, max_code_len
-from test_gpu_ranges import check_all_good, slots_for, touched
+from stream_support import GUARD, Enc, dev, make, max_code_len, touched
+from stream_support import ranges_route_model as model
+from test_gpu_ranges import check_all_good, slots_for
 
 pytestmark = pytest.mark.gpu
 
@@ -42,29 +43,6 @@ def encode(torch, codec, kind, n, bs):
     enc.block_lens = np.diff(enc.P)
     enc.elig = np.full(enc.nb, kind != "const41")      # (the header length is the layout's in all of these)
     return enc
-
-
-# ---- the routing rule, restated ----------------------------------------------------------------------------------------
-def model(enc, ranges, oo):
-    """(direct, staged, tiles, items) the rule of include/huffman_gpu.h gives"""
-    cover, pairs, whole = np.zeros(enc.nb, int), np.zeros(enc.nb, int), np.zeros(enc.nb, int)
-    for i, (lo, hi) in enumerate(ranges):
-        t = touched(enc, lo, hi)
-        lo_c, hi_c = min(lo, enc.n), min(hi, enc.n)
-        if t is None or oo[i + 1] - oo[i] < hi_c - lo_c:
-            continue
-        for b in range(t[0], t[1] + 1):
-            p0, p1 = int(enc.P[b]), int(enc.P[b + 1])
-            c0, c1 = max(lo_c, p0) - p0, min(hi_c, p1) - p0
-            if c0 >= c1:
-                continue
-            cover[b] += 1
-            pairs[b] += (c1 - 1) // TILE - c0 // TILE + 1
-            whole[b] += c0 == 0 and c1 == p1 - p0
-    direct = (cover == 1) & (whole == 1)
-    rest = (cover > 0) & ~direct
-    tiles = rest & enc.elig & (pairs <= (enc.block_lens + TILE - 1) // TILE)
-    return int(direct.sum()), int((rest & ~tiles).sum()), int(tiles.sum()), int(pairs[tiles].sum())
 
 
 def call(torch, codec, enc, ranges, oo, tiles, relaxed=False, sub_index="own"):

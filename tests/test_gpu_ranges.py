@@ -13,7 +13,7 @@ import pytest
 
 import sub_index_ref as sref
 from libhuffman_amd import datagen
-from stream_support import GUARD, Enc, dev
+from stream_support import GUARD, Enc, dev, touched
 
 pytestmark = pytest.mark.gpu
 
@@ -74,16 +74,6 @@ def check_all_good(enc, ranges, got, errs, raws, oo, only=None):
         diff = np.flatnonzero(got != want)
         assert diff.size == 0, f"bytes differ at {diff[:8]} (slots start at {oo[:8]})"
     assert np.all(got[:oo[0]] == GUARD) and np.all(got[oo[-1]:] == GUARD)
-
-
-def touched(enc, lo, hi):
-    """first and last block of the cut range, None when it is empty"""
-    lo_c, hi_c = min(lo, enc.n), min(hi, enc.n)
-    if lo_c >= hi_c:
-        return None
-    fb = int(np.searchsorted(enc.P, lo_c, side="right")) - 1
-    lb = int(np.searchsorted(enc.P, hi_c, side="left")) - 1
-    return fb, lb
 
 
 def witnesses(torch, codec, oracle, enc, fb, lb, relaxed=False):
