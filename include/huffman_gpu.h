@@ -1243,6 +1243,18 @@ int hufgpu_block_index(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t avail, 
  * block - what a caller that feeds a stream piecewise keeps for its next piece). */
 int hufgpu_decode_stream_complete(hufgpu_ctx_t *ctx, uint64_t *raw_len, uint64_t *consumed);
 
+/* What the block discovery (kernels/discover.hpp) of the last hufgpu_decode_stream() or hufgpu_block_index() on the
+ * context did: counters[0] = 1 if the call went through the discovery at all (0: a stream below the path's threshold, a
+ * misaligned one, HUFGPU_SEQUENTIAL, a stream of leading big blocks alone - [1..7] are then 0), [1] = candidate headers
+ * found, [2] = candidates the arrays held (= [1] when the call returned without an error), [3] = candidates the lean
+ * probe handed to the exact one, [4] = links of the chain that are not "the next candidate" (0: the plain chain, which
+ * the walk takes as it stands), [5] = blocks the walk validated, [6] = output bytes the probes left in place for them
+ * (~0: none - hufgpu_block_index, an output without room for every candidate, a chain that skips a candidate, no block
+ * validated),
+ * [7] = passes of the discovery (2: the stream held more candidates than the arrays, and everything ran again with room).
+ * Results never depend on these.  HUF_ERROR_INVALID_ARGUMENT for a NULL context or array; touches no GPU. */
+int hufgpu_stream_counters(hufgpu_ctx_t *ctx, uint64_t counters[8]);
+
 /* Deterministic synthetic inputs of SURVEY §8d, generated in HBM (kind: 0 const41,
  * 1 uniform256, 2 uniform255, 3 zipf255). `first` = index of the first byte of this shard in
  * the global sequence, so shards of one logical input can be produced on different GPUs. */

@@ -79,7 +79,7 @@ hufgpu_ctx_device hufgpu_shard_unique_id hufgpu_shard_create hufgpu_shard_destro
 hufgpu_shard_range hufgpu_shard_plan_decode hufgpu_encode_sharded hufgpu_decode_sharded hufgpu_shard_set_timeout
 hufgpu_batch_geometry hufgpu_encode_batch hufgpu_decode_batch hufgpu_decode_ranges
 hufgpu_sub_index_from_raw hufgpu_decode_build_sub hufgpu_build_sub_index hufgpu_update_ranges
-hufgpu_append hufgpu_truncate hufgpu_ranges_counters hufgpu_gather hufgpu_find_bytes hufgpu_find_pattern hufgpu_find_records
+hufgpu_append hufgpu_truncate hufgpu_ranges_counters hufgpu_stream_counters hufgpu_gather hufgpu_find_bytes hufgpu_find_pattern hufgpu_find_records
 hufgpu_find_classes hufgpu_find_records_classes hufgpu_find_any hufgpu_find_records_any
 hufgpu_find_records_select hufgpu_find_records_context hufgpu_find_any_anchored hufgpu_find_records_anchored
 hufgpu_find_records_terms hufgpu_find_any_quant hufgpu_find_records_quant
@@ -180,6 +180,8 @@ def load() -> C.CDLL:
                                        C.POINTER(C.c_int32), P64, vp]
     L.hufgpu_ranges_counters.restype = C.c_int
     L.hufgpu_ranges_counters.argtypes = [vp, P64]
+    L.hufgpu_stream_counters.restype = C.c_int
+    L.hufgpu_stream_counters.argtypes = [vp, P64]
     L.hufgpu_sub_index_from_raw.argtypes = [vp, vp, u64, vp, vp, u64, u64, vp, C.c_uint32, P64, vp]
     L.hufgpu_decode_build_sub.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, vp, C.c_uint32, P64, P64, vp]
     L.hufgpu_build_sub_index.argtypes = [vp, vp, u64, vp, u64, u64, vp, C.c_uint32, P64, vp]

@@ -1467,6 +1467,14 @@ class GpuCodec:
                                             C.byref(raw), C.byref(used), self._stream())
         return int(err), int(raw.value), int(used.value)
 
+    def stream_counters(self):
+        """What the block discovery of the last decode_stream / hufgpu_block_index did (hufgpu_stream_counters): (ran,
+        candidates found, candidates held, sent to the exact probe, links that are not "the next candidate", blocks
+        validated, output bytes the probes left in place or 2**64 - 1, passes)."""
+        c = (C.c_uint64 * 8)()
+        self._check(self.lib.hufgpu_stream_counters(self._ctx, c), "counter readout failed")
+        return tuple(int(x) for x in c)
+
     def fill(self, out: torch.Tensor, kind: str, first: int = 0, seed: int | None = None):
         seed = FILL_SEEDS[kind] if seed is None else seed
         self._check(self.lib.hufgpu_fill(self._ctx, out.data_ptr(), out.numel(), FILL_KINDS[kind],

@@ -43,6 +43,7 @@ struct hufgpu_ctx {
     uint32_t *d_nxt;
     uint64_t *d_walk;             /* 5 result words of walk_kernel (fixed) */
     uint64_t *d_spec_off;         /* speculative output offsets of the candidates (disc_cands + 1) */
+    uint64_t scounters[8];        /* hufgpu_stream_counters(): of the last hufgpu_decode_stream / hufgpu_block_index */
 
     /* blocks of many MiB in a raw stream: the sub-index built for them (kernels/spec_index.hpp) */
     uint64_t big_lanes, big_sub_bytes;

@@ -13,6 +13,8 @@ static int discover_chain(hufgpu_ctx_t *ctx, const uint8_t *st, uint64_t avail, 
                           bool *complete_out, uint64_t *in_place_out)
 {
     *m_out = 0; *resume_out = 0; *complete_out = false; *in_place_out = ~0ull;
+    ctx->scounters[0] = 1;                                               /* (hufgpu_stream_counters; the rest is 0 from the entry point) */
+    ctx->scounters[6] = ~0ull;                                           /* nothing in place, also when no candidate is found */
     const uint64_t nwg = (scan_len + DISC_CHUNK - 1) / DISC_CHUNK;
     const uint64_t ngroups = (nwg + DISC_SCAN_GROUP - 1) / DISC_SCAN_GROUP;
     int rc = grow_ws(ctx, G_DISC_WGS, nwg);
@@ -25,6 +27,7 @@ static int discover_chain(hufgpu_ctx_t *ctx, const uint8_t *st, uint64_t avail, 
      * stream turns out to hold more candidates than they take (the walk's result says so), does the host wait for the
      * count, make room and go again - what every call did until round 5. */
     for (int attempt = 0; attempt < 2; attempt++) {
+        ctx->scounters[7] = (uint64_t)attempt + 1;
         HIP_OK(ctx, hipMemsetAsync(ctx->d_walk, 0, DISC_WORDS * sizeof(uint64_t), s));
         discover_kernel<<<dim3((unsigned)nwg), dim3(DISC_THREADS), 0, s>>>(st, avail, scan_len, max_tree, ctx->d_wg_counts, (DiscSlot *)ctx->d_disc_slots, ctx->d_disc_masks);
         scan_counts_kernel<SCAN_THREADS><<<dim3((unsigned)ngroups), dim3(SCAN_THREADS), 0, s>>>(ctx->d_wg_counts, nwg, ctx->d_wg_base, group_base, group_total, ctx->d_walk, ctx->disc_cands);
@@ -33,6 +36,7 @@ static int discover_chain(hufgpu_ctx_t *ctx, const uint8_t *st, uint64_t avail, 
             HIP_OK(ctx, hipMemcpyAsync(ctx->h_result, ctx->d_walk + DISC_FOUND, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
             HIP_OK(ctx, hipStreamSynchronize(s));
             const uint64_t found = ctx->h_result[0];
+            ctx->scounters[1] = found;
             if (found == 0 || found >= 0x7fffffffull) return HUFE_OK;
             rc = grow_ws(ctx, G_DISC_CANDS, found);
             if (rc) return rc;
@@ -54,8 +58,15 @@ static int discover_chain(hufgpu_ctx_t *ctx, const uint8_t *st, uint64_t avail, 
         link_kernel<<<dim3((unsigned)((width + 255) / 256)), dim3(256), 0, s>>>(ctx->d_cand, ctx->d_cand_end, ctx->d_cand_status, ctx->d_walk, length, ctx->d_nxt);
         walk_kernel<<<dim3(1), dim3(WALK_THREADS), 0, s>>>(ctx->d_cand, ctx->d_cand_end, ctx->d_nxt, ctx->d_chain, ctx->d_walk, ctx->d_spec_off, out_cap);
         HIP_OK(ctx, hipGetLastError());
-        HIP_OK(ctx, hipMemcpyAsync(ctx->h_result, ctx->d_walk, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        static_assert(DISC_NCAND < 10 && DISC_ODD_LINKS < 10 && DISC_REDO < 10, "the copy below brings the read-out's words");
+        HIP_OK(ctx, hipMemcpyAsync(ctx->h_result, ctx->d_walk, 10 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_OK(ctx, hipStreamSynchronize(s));
+        ctx->scounters[1] = ctx->h_result[DISC_FOUND];
+        ctx->scounters[2] = ctx->h_result[DISC_NCAND];
+        ctx->scounters[3] = ctx->h_result[DISC_REDO];
+        ctx->scounters[4] = ctx->h_result[DISC_ODD_LINKS];
+        ctx->scounters[5] = ctx->h_result[0];
+        ctx->scounters[6] = ctx->h_result[0] ? ctx->h_result[4] : ~0ull;     /* (no block validated: nothing counts as in place) */
         if (ctx->h_result[DISC_FOUND] > width) continue;                 /* more candidates than the arrays took: once more, with room */
         *m_out = ctx->h_result[0];
         *in_place_out = ctx->h_result[4];   /* bytes the probe already decoded into `out` for these m blocks */
@@ -196,6 +207,7 @@ extern "C" int hufgpu_block_index(hufgpu_ctx_t *ctx, const void *d_stream, uint6
 {
     if (!ctx || !d_index || !nblocks || !consumed) return HUFE_ARGUMENT;
     *d_index = NULL; *nblocks = 0; *consumed = 0;
+    memset(ctx->scounters, 0, sizeof(ctx->scounters));
     if (length == 0) return HUFE_OK;
     if (!d_stream || ((uintptr_t)d_stream & 15u)) return HUFE_ARGUMENT;
     HIP_OK(ctx, hipSetDevice(ctx->device));
@@ -295,6 +307,7 @@ extern "C" int hufgpu_decode_stream(hufgpu_ctx_t *ctx, const void *d_stream, uin
     if (!ctx) return HUFE_ARGUMENT;
     if (raw_len) *raw_len = 0;
     if (consumed) *consumed = 0;
+    memset(ctx->scounters, 0, sizeof(ctx->scounters));
     if (length == 0) return HUFE_OK;                  /* src/decoder.c:218 */
     if ((!d_stream && avail) || (!d_out && out_cap)) return HUFE_ARGUMENT;
     HIP_OK(ctx, hipSetDevice(ctx->device));
@@ -321,6 +334,15 @@ extern "C" int hufgpu_decode_stream(hufgpu_ctx_t *ctx, const void *d_stream, uin
     if (raw_len) *raw_len = rawpos + raw2;
     if (consumed) *consumed = pos + used2;
     return err;
+}
+
+/* What the discovery of the last hufgpu_decode_stream / hufgpu_block_index did (include/huffman_gpu.h): host values that
+ * discover_chain took from its last copy of d_walk, no GPU is touched. */
+extern "C" int hufgpu_stream_counters(hufgpu_ctx_t *ctx, uint64_t counters[8])
+{
+    if (!ctx || !counters) return HUFE_ARGUMENT;
+    memcpy(counters, ctx->scounters, sizeof(ctx->scounters));
+    return HUFE_OK;
 }
 
 extern "C" int hufgpu_decode_stream_complete(hufgpu_ctx_t *ctx, uint64_t *raw_len, uint64_t *consumed)

@@ -82,6 +82,15 @@ def header(nsym: int, ent: list) -> bytes:
     return struct.pack("<Qh", nsym, len(ent)) + np.asarray(ent, dtype="<i2").tobytes()
 
 
+def _handmade_block(payload: bytes, leaves: int) -> bytes:
+    """A block whose tree is complete with 2 or 4 leaves ('A' = 0, 'B' = 1 / 'A'..'D' = 00..11): its payload is ANY byte
+    string, one symbol a bit or two (src/decoder.c:34-96 walks whatever tree the stream brings)."""
+    tree = [0x0101, 0x41, -1, -1, 0x42, -1, -1] if leaves == 2 else \
+           [0x0103, 0x0101, 0x41, -1, -1, 0x42, -1, -1, 0x0102, 0x43, -1, -1, 0x44, -1, -1]
+    per_byte = 8 if leaves == 2 else 4
+    return struct.pack("<Qh", per_byte * len(payload), len(tree)) + b"".join(struct.pack("<h", v) for v in tree) + payload
+
+
 def pack_payload(leaf_bits: list, pick: np.ndarray, pad_ones: bool = False, chunk: int = 1 << 20):
     """(payload bytes, bit count before padding): the codewords leaf_bits[pick[0]], leaf_bits[pick[1]] ... back to back,
     most significant bit first, the last byte filled with zeros or ones.  Codes of any length; numpy, a chunk of symbols at

@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from handmade_streams import _handmade_block
 from libhuffman_amd import datagen
 
 pytestmark = pytest.mark.gpu
@@ -351,16 +352,6 @@ def test_decode_stream_parallel_discovery(torch_mod, codec, oracle, kind, n, bs)
         err, raw, used = codec.decode_stream(s, stream.size, stream.size, out, relaxed=True, sequential=sequential)
         assert (err, raw, used) == (0, n, stream.size), (kind, sequential)
         assert np.array_equal(out[:raw].cpu().numpy(), data)
-
-
-def _handmade_block(payload: bytes, leaves: int) -> bytes:
-    """A block whose tree is complete with 2 or 4 leaves ('A' = 0, 'B' = 1 / 'A'..'D' = 00..11): its payload is ANY byte
-    string, one symbol a bit or two (src/decoder.c:34-96 walks whatever tree the stream brings)."""
-    import struct
-    tree = [0x0101, 0x41, -1, -1, 0x42, -1, -1] if leaves == 2 else \
-           [0x0103, 0x0101, 0x41, -1, -1, 0x42, -1, -1, 0x0102, 0x43, -1, -1, 0x44, -1, -1]
-    per_byte = 8 if leaves == 2 else 4
-    return struct.pack("<Qh", per_byte * len(payload), len(tree)) + b"".join(struct.pack("<h", v) for v in tree) + payload
 
 
 @pytest.mark.parametrize("leaves,pay_bytes,at,fake_len,small_blocks",
