@@ -1053,6 +1053,88 @@ int hufgpu_update_ranges(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t strea
                          uint32_t flags, uint64_t *out_len, uint64_t *blocks_reencoded, void *stream);
 
 /*
+ * SCATTER: records overwritten at positions that are on the device - the write side of hufgpu_gather(), as
+ * hufgpu_update_ranges() is the write side of hufgpu_decode_ranges().  The starts and (start, length) records that the
+ * hufgpu_find_* calls leave in device memory go in as they are: find -> scatter blanks what grep found with no host wait in
+ * between, and both can sit in one captured graph.  Nothing about the records is read on the host, no host memory is
+ * written, and the call only enqueues on `stream` (NULL = the context's); it waits only when a workspace of the context
+ * grows.  Two calls back to back on one stream are safe, calls on different streams of one context are not.  It works on
+ * a non-default stream and inside a stream capture (a replay reads d_pos, d_len and d_src anew).  There is no CPU path.
+ *
+ *   record i      : bytes [d_pos[i], d_pos[i] + len_i) of the original data, exactly as hufgpu_gather() defines it: len_i =
+ *                   d_len[i] or, with d_len = NULL, max_len for every record.  Positions are the layout's: fixed blocksize,
+ *                   blocksize = 0 means one block.  A record that reaches past raw_size is cut there; one that starts at
+ *                   or behind raw_size, or has len_i = 0, writes nothing.  An overwrite changes no length.
+ *   new bytes     : without HUFGPU_SCATTER_FILL the first len_i bytes of slot d_src + i * src_stride (src_stride >= max_len,
+ *                   any alignment) - the layout hufgpu_gather() writes, so gather -> the caller's kernel -> scatter needs
+ *                   no repacking.  With the flag every covered byte becomes `fill` and d_src is not read.
+ *   overlap       : records may repeat, overlap and come in any order (the overlapping starts of hufgpu_find_pattern() are
+ *                   the normal input).  With FILL the result is defined.  Without, a byte that several records cover
+ *                   receives the byte that ONE of those records carries for it, which one is unspecified; every other byte
+ *                   is exact.
+ *   result        : hufgpu_update_ranges()' contract word for word.  With D' = D with the records applied, d_out receives
+ *                   the records of all blocks back to back: an untouched block's record is the old one, moved byte for
+ *                   byte, a touched block's record is what hufgpu_encode() writes for the block's bytes of D' alone.  For a
+ *                   stream of hufgpu_encode(D, blocksize) the output is hufgpu_encode(D', blocksize) byte for byte.
+ *                   d_out_block_offsets (nblocks + 1 entries) is REQUIRED here and receives the new index.
+ *                   d_out_sub_index is optional and follows hufgpu_update_ranges()' rules: the touched rows receive every
+ *                   entry hufgpu_encode_sub() writes; with d_sub_index given as well the untouched rows are copied from it.
+ *                   d_sub_index is optional, verified as ever - any content gives the same result - and only speeds up
+ *                   the decode of the touched blocks.
+ *   routing       : EVERY touched block is staged: decoded whole into the context's scratch area (the one
+ *                   hufgpu_decode_ranges() uses) by the indexed decoders, overlaid there, encoded from there.  There is no
+ *                   "direct" kind - whether a block lies wholly inside one record would need the records sorted.  So a
+ *                   touched block MUST DECODE, even when the records cover all of it (hufgpu_update_ranges() does not ask
+ *                   that of a block wholly inside one range).  Untouched blocks are not decoded: damage in them is carried
+ *                   over unseen.
+ *   touched_cap   : the largest number of distinct blocks the records may touch, 1 .. nblocks.  It sizes the scratch area
+ *                   (touched_cap x blocksize rounded up to 16; HUF_ERROR_MEMORY_ALLOCATION from the call itself when it
+ *                   cannot grow), the row workspaces and every row grid.  hufgpu_scatter_touched_bound() returns
+ *                   min(nblocks, nrecords * ((max_len + blocksize - 2) / blocksize + 1)), which always suffices (1 for
+ *                   blocksize = 0).  If more blocks are touched the call reports failure in d_result; it never writes
+ *                   outside its buffers.
+ *   d_result      : four words of device memory, required, zeroed by the call's first kernel, written by its last launch:
+ *                     [0] status: 0 or a huf_error_t value        [2] the number of touched blocks, even when above the cap
+ *                     [1] the length of the new stream, 0 when    [3] the record or block that caused the status, ~0 when
+ *                         the status is not 0                         none
+ *                   The status is the first condition that holds, in this order:
+ *                     1. HUF_ERROR_INVALID_ARGUMENT: some len_i > max_len; [3] is the lowest such i (such records write
+ *                        nothing and touch nothing).
+ *                     2. HUF_ERROR_MEMORY_ALLOCATION: touched > touched_cap.
+ *                     3. a touched block cannot be served: its header does not parse under `flags`, its block_len is not
+ *                        the layout's, or it does not decode.  The status is what hufgpu_decode() says of it, or
+ *                        HUF_ERROR_READ_WRITE for a block_len that is not the layout's; [3] is the first such block in
+ *                        stream order.
+ *                     4. HUF_ERROR_MEMORY_ALLOCATION: the new stream is longer than out_cap.  Old length + touched_cap x
+ *                        hufgpu_encode_bound(blocksize, 0) always suffices.
+ *                   With a non-zero status the contents of d_out and the two output indexes are unspecified; nothing else
+ *                   has been written.  The input stream is never written.
+ *   flags         : HUFGPU_RELAXED_TREE as for hufgpu_decode(), HUFGPU_SCATTER_FILL.
+ *
+ * Argument errors return HUF_ERROR_INVALID_ARGUMENT, worded "scatter: ...", before anything is enqueued and before the
+ * context is looked at, the first that holds in this order: a NULL d_stream / d_block_offsets / d_pos / d_out /
+ * d_out_block_offsets / d_result; a NULL d_src without FILL; src_stride < max_len without FILL; (raw_size, blocksize) that
+ * do not give nblocks; blocksize >= HUFGPU_BATCH_CHUNKED_FROM (the chunked encoder waits once per block, so this call does
+ * not serve it); touched_cap = 0 or above nblocks; more than 2^32 - 1 (record, block) parts by hufgpu_gather()'s bound;
+ * a d_out that is not 4-byte aligned, a sub-index that is not 8-byte aligned; a d_out_sub_index with a layout it cannot
+ * hold (more than 2^31 - 1 rows of chunks); hufgpu_update_ranges()' out-of-place overlap checks with the d_src extent
+ * nrecords * src_stride, and d_result against the three outputs; no context.  nrecords = 0 or max_len = 0 is
+ * hufgpu_update_ranges()' "no ranges" case, enqueued: a plain copy of the stream, its index and - when both are given -
+ * its sub-index, with d_result = {0, stream_len, 0, ~0} (or {HUF_ERROR_MEMORY_ALLOCATION, 0, 0, ~0} and nothing copied
+ * when stream_len > out_cap).  A pending hufgpu_decode() of the context is forgotten.
+ */
+#define HUFGPU_SCATTER_FILL 0x100u   /* flags: every record's new bytes are `fill`, d_src is not read */
+int hufgpu_scatter(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                   const uint64_t *d_block_offsets, uint64_t nblocks,
+                   const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                   uint64_t nrecords, const uint64_t *d_pos, const uint32_t *d_len, uint32_t max_len,
+                   const void *d_src, uint64_t src_stride, uint8_t fill,
+                   uint64_t touched_cap,
+                   void *d_out, uint64_t out_cap, uint64_t *d_out_block_offsets, void *d_out_sub_index,
+                   uint64_t *d_result, uint32_t flags, void *stream);
+uint64_t hufgpu_scatter_touched_bound(uint64_t nblocks, uint64_t blocksize, uint64_t nrecords, uint32_t max_len);
+
+/*
  * APPEND and TRUNCATE: an indexed stream made longer or shorter IN PLACE.  Every record in front of the last block
  * stays where it is, so the cost follows the appended bytes, not the stream.
  *

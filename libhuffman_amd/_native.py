@@ -43,6 +43,7 @@ ANCHOR_BOL, ANCHOR_EOL, ANCHOR_WORD = 1, 2, 4   # HUFGPU_ANCHOR_*: the anchored 
 FIND_PATTERN_MAX = 64           # HUFGPU_FIND_PATTERN_MAX: the bytes of a hufgpu_find_pattern pattern
 FIND_TERMS_MAX = 4              # HUFGPU_FIND_TERMS_MAX: the terms of a hufgpu_find_records_terms call
 TERMS_ALL, TERMS_ORDERED = 0, 1  # HUFGPU_TERMS_*: every term somewhere in the record, or one behind the other
+SCATTER_FILL = 0x100            # HUFGPU_SCATTER_FILL: hufgpu_scatter writes one byte value, d_src is not read
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t))
@@ -83,7 +84,7 @@ hufgpu_append hufgpu_truncate hufgpu_ranges_counters hufgpu_stream_counters hufg
 hufgpu_find_classes hufgpu_find_records_classes hufgpu_find_any hufgpu_find_records_any
 hufgpu_find_records_select hufgpu_find_records_context hufgpu_find_any_anchored hufgpu_find_records_anchored
 hufgpu_find_records_terms hufgpu_find_any_quant hufgpu_find_records_quant
-hufgpu_find_any_expr hufgpu_find_records_expr""".split()
+hufgpu_find_any_expr hufgpu_find_records_expr hufgpu_scatter hufgpu_scatter_touched_bound""".split()
 
 
 def so_path() -> str:
@@ -234,6 +235,11 @@ def load() -> C.CDLL:
     L.hufgpu_find_records_expr.restype = C.c_int          # hufgpu_find_records_context's with `optional`, the terms' three and the anchors' two
     L.hufgpu_find_records_expr.argtypes = (L.hufgpu_find_records_context.argtypes[:12] + [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32] +
                                            L.hufgpu_find_records_context.argtypes[12:])
+    L.hufgpu_scatter.restype = C.c_int                    # hufgpu_gather's up to max_len, then the new bytes, the cap, update_ranges' outputs
+    L.hufgpu_scatter.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, u64, vp, vp, C.c_uint32, vp, u64, C.c_uint8, u64,
+                                 vp, u64, vp, vp, vp, C.c_uint32, vp]
+    L.hufgpu_scatter_touched_bound.restype = u64
+    L.hufgpu_scatter_touched_bound.argtypes = [u64, u64, u64, C.c_uint32]
     _LIB = L
     return L
 

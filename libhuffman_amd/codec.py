@@ -1340,6 +1340,175 @@ class GpuCodec:
         """update_ranges for the one range [lo, lo + data.numel())."""
         return self.update_ranges(stream, stream_len, offsets, nblocks, [(lo, lo + data.numel())], data, **kwargs)
 
+    # -- scatter: records at device-resident positions overwritten, enqueue-only ---------------------
+    def scatter_touched_bound(self, nblocks: int, blocksize: int, nrecords: int, max_len: int) -> int:
+        """The blocks that `nrecords` records of up to `max_len` bytes can touch at most (hufgpu_scatter_touched_bound)."""
+        return int(self.lib.hufgpu_scatter_touched_bound(nblocks, blocksize, nrecords, max_len))
+
+    @staticmethod
+    def _scatter_source(data, fill, n: int, max_len):
+        """(data as [n, >= max_len] rows or None, fill byte or None, max_len, stride) of scatter's `data` / `fill`; raises
+        ValueError / TypeError for what scatter documents."""
+        if (data is None) == (fill is None):
+            raise ValueError("scatter takes exactly one of `data` (the records' new bytes) and `fill` (one byte value for all)")
+        if fill is not None:
+            if isinstance(fill, (bytes, bytearray)):
+                if len(fill) != 1:
+                    raise ValueError(f"`fill` is one byte, not {len(fill)}")
+                fill = fill[0]
+            fill = int(fill)
+            if not 0 <= fill <= 255:
+                raise ValueError(f"`fill` is a byte value, not {fill}")
+            return None, fill, max_len, 0
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8:
+            raise TypeError("`data` is a uint8 tensor: [nrecords, >= max_len] slots, or 1-D with `max_len`")
+        if data.dim() == 1:
+            if max_len is None:
+                raise ValueError("a 1-D `data` needs `max_len`, the bytes of a slot")
+            if data.numel() != n * int(max_len):
+                raise ValueError(f"a 1-D `data` holds nrecords x max_len = {n * int(max_len)} bytes, not {data.numel()}")
+            data = data.contiguous().view(n, int(max_len))
+        if data.dim() != 2 or data.size(0) != n:
+            raise ValueError(f"`data` has one slot a record: [{n}, >= max_len], not {list(data.shape)}")
+        if data.size(1) > 1 and data.stride(1) != 1:
+            raise ValueError("a slot of `data` is contiguous")
+        if max_len is not None and data.size(1) < int(max_len):
+            raise ValueError(f"a slot of `data` has {data.size(1)} bytes, fewer than max_len = {int(max_len)}")
+        stride = data.stride(0) if n > 1 else max(data.stride(0), data.size(1))
+        return data, None, (data.size(1) if max_len is None else max_len), stride
+
+    def scatter(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, positions: torch.Tensor,
+                lengths, *, data: torch.Tensor | None = None, fill=None, raw_size: int, blocksize: int,
+                sub_index: torch.Tensor | None = None, max_len: int | None = None, touched_cap: int | None = None,
+                out: torch.Tensor | None = None, want_sub_index: bool = False, relaxed: bool = False):
+        """Overwrite record i = bytes [positions[i], positions[i] + length_i) of the original data, out of place, on torch's
+        current stream and without a synchronisation (hufgpu_scatter): the write side of gather().  `positions` is a CUDA
+        int64 / uint64 tensor, `lengths` an int (every record that long), None (every record `max_len` long) or a CUDA
+        int32 tensor with `max_len` their host-known bound - what find_pattern / find_records leave on the device.
+        Exactly one of `data` and `fill`: `data` is a uint8 CUDA tensor of slots [nrecords, >= max_len] (its row stride is
+        the call's src_stride: what gather() returns goes in as it is) or 1-D with `max_len`; `fill` is one byte value
+        (an int or a `bytes` of one) that every covered byte becomes.  Records may overlap, repeat and come in any order;
+        with `data`, a byte that several records cover gets the byte of one of them.  `touched_cap` bounds the distinct
+        blocks the records touch and sizes the scratch area; it defaults to scatter_touched_bound().  `sub_index` is the
+        OLD stream's (optional), `want_sub_index` asks for the new stream's.  Without `out` the output is stream_len +
+        touched_cap x encode_bound(blocksize) bytes, which always suffices.
+        Returns (out, new_offsets int64 [nblocks + 1], result int64 [4], new sub-index or None), all CUDA tensors; nothing
+        has been waited for, so `out` is the whole buffer and result[1] the new length: scatter_result(result) reads it."""
+        assert positions.is_cuda and positions.dtype in (torch.int64, torch.uint64) and positions.dim() == 1
+        positions = positions.contiguous()
+        n = positions.numel()
+        len_ptr = None
+        if isinstance(lengths, torch.Tensor):
+            if max_len is None:
+                raise ValueError("lengths on the device need max_len, their bound")
+            assert lengths.is_cuda and lengths.dtype == torch.int32 and lengths.numel() == n
+            lengths = lengths.contiguous()
+            len_ptr = lengths.data_ptr() if n else None
+        elif lengths is not None:
+            if max_len is not None and int(max_len) != int(lengths):
+                raise ValueError("a fixed record size is max_len")
+            max_len = int(lengths)
+        data, fill, max_len, stride = self._scatter_source(data, fill, n, max_len)
+        if max_len is None:
+            raise ValueError("scatter needs the records' length: `lengths`, or `max_len`")
+        max_len = int(max_len)
+        if touched_cap is None:
+            touched_cap = max(1, self.scatter_touched_bound(nblocks, blocksize, n, max_len))
+        touched_cap = int(touched_cap)
+        if out is None:
+            per_block = self.encode_bound(min(blocksize, raw_size) if blocksize else raw_size, 0)
+            out = torch.empty(stream_len + min(touched_cap, nblocks) * per_block + 64, dtype=torch.uint8, device=self.tdev)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous()
+        new_offsets = torch.empty(nblocks + 1, dtype=torch.int64, device=self.tdev)
+        new_sub = self.new_sub_index(raw_size, blocksize) if want_sub_index else None
+        result = torch.empty(4, dtype=torch.int64, device=self.tdev)
+        flags = (_native.RELAXED_TREE if relaxed else _native.STRICT_TREE) | (_native.SCATTER_FILL if fill is not None else 0)
+        err = self.lib.hufgpu_scatter(self._ctx, stream.data_ptr() if stream.numel() else None, stream_len,
+                                      offsets.data_ptr(), nblocks, sub_index.data_ptr() if sub_index is not None else None,
+                                      raw_size, blocksize, n, positions.data_ptr() if n else result.data_ptr(),   # (no record: never read)
+                                      len_ptr, max_len,
+                                      None if data is None else (data.data_ptr() if data.numel() else result.data_ptr()), stride,
+                                      fill or 0, touched_cap, out.data_ptr(), out.numel(), new_offsets.data_ptr(),
+                                      new_sub.data_ptr() if new_sub is not None else None, result.data_ptr(), flags, self._stream())
+        self._pending_decode = None
+        self._check(err, "Failed to enqueue the scatter")
+        return out, new_offsets, result, new_sub
+
+    def scatter_result(self, result: torch.Tensor):
+        """Reads the four result words of a scatter() once (this waits for the call): returns (new length, touched blocks),
+        or raises HuffmanGpuError with the status; the exception's `.raw` is the record or block that caused it (None when
+        the status names none) and `.touched` the number of touched blocks."""
+        status, length, touched, who = (int(x) for x in result.cpu().tolist())
+        if status:
+            who = None if who == -1 else who
+            detail = {_native.HUF_ERROR_INVALID_ARGUMENT: f"record {who} is longer than max_len",
+                      _native.HUF_ERROR_MEMORY_ALLOCATION: f"{touched} blocks are touched, or the new stream does not fit the output"
+                      }.get(status, f"block {who} cannot be served")
+            e = HuffmanGpuError(status, "The scatter failed", detail)
+            e.raw, e.touched = who, touched
+            raise e
+        return length, touched
+
+    def redact(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, sub_index: torch.Tensor,
+               raw_size: int, blocksize: int, pattern, fill=b"*", *, max_matches: int, lines: bool = False, max_len: int = 0,
+               touched_cap: int | None = None, out: torch.Tensor | None = None, want_sub_index: bool = False,
+               relaxed: bool = False, **find):
+        """Blank what a search finds: find_pattern (or, with `lines=True`, find_records) followed by scatter(fill=...), on
+        torch's current stream with no host wait in between.  Every byte of every occurrence of `pattern` becomes `fill`;
+        with `lines=True` the first `max_len` bytes of every selected record do (the delimiter stays).  `max_matches` is
+        the search's cap (occurrences or records behind it are not blanked: the returned totals say how many there
+        were); `**find` are the search's keywords (`ignore_case`, `bol`, `word`, ... and with `lines` `delimiters`,
+        `invert`, ...).
+        A search for positions reports where a match STARTS; where it ends is known only for a pattern of one length - a
+        literal, a list / tuple of classes, an AnyOf whose alternatives all have that length.  Opt / Rep items, an Expr
+        and an AnyOf of unequal lengths raise ValueError without `lines=True`.
+        The scatter is given the search's cap as its number of records, not the found count, which is on the device.  The
+        entries behind the found count are made harmless on the device before it runs: positions from totals[1] on are
+        replaced by raw_size (and lengths by 0) - a record that starts at raw_size writes nothing.
+        What it costs in memory: the scatter cannot know how many blocks the matches touch, so with `touched_cap=None` it
+        takes scatter_touched_bound(nblocks, blocksize, max_matches, length), which is EVERY block as soon as max_matches
+        reaches nblocks / 2.  The context's scratch area then grows to touched_cap x blocksize - the whole raw size - and an
+        `out` made here is stream_len + touched_cap x encode_bound(blocksize) bytes, however few matches there are.  A
+        caller who knows that the matches are few passes `touched_cap=` (a status of HUF_ERROR_MEMORY_ALLOCATION in
+        `result`, and nothing written outside the buffers, if more blocks are touched) and may pass `out=`.
+        Returns (out, new_offsets, result, new sub-index or None, totals): scatter()'s, and the search's totals."""
+        max_matches = int(max_matches)
+        if lines:
+            if int(max_len) < 1:
+                raise ValueError("redact(lines=True) needs max_len, the bytes of a record that are blanked at most")
+            found = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
+                                      max_records=max_matches, max_len=int(max_len), relaxed=relaxed, **find)
+            pos, lens, totals = found[0], found[1], found[2]
+            written = torch.arange(max_matches, device=self.tdev) < totals[1]
+            pos = torch.where(written, pos, raw_size)
+            lens = torch.where(written, lens, 0).clamp_(max=int(max_len))
+            lengths, mlen = lens, int(max_len)
+        else:
+            if isinstance(pattern, GpuCodec.Expr):
+                raise ValueError("an Expr has no one match length (where a match ends is not reported): redact it with lines=True")
+            if not isinstance(pattern, GpuCodec._Terms):
+                if self._is_quant(pattern):
+                    raise ValueError("a pattern with Opt / Rep items has no one match length (where a match ends is not reported): "
+                                     "redact it with lines=True")
+                route, key, _ = self._find_route(pattern, find.get("ignore_case", False))
+                if route == "any":
+                    alt_lens = np.frombuffer(key[1], np.uint32)
+                    if len(set(alt_lens.tolist())) != 1:
+                        raise ValueError(f"the alternatives have lengths {sorted(set(alt_lens.tolist()))}, not one (where a match ends "
+                                         "is not reported): redact them with lines=True")
+                    mlen = int(alt_lens[0])
+                else:
+                    mlen = int(key[1])
+            pos, totals = self.find_pattern(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
+                                            max_positions=max_matches, relaxed=relaxed, **find)[:2]
+            written = torch.arange(max_matches, device=self.tdev) < totals[1]
+            pos = torch.where(written, pos, raw_size)
+            lengths = mlen
+        res = self.scatter(stream, stream_len, offsets, nblocks, pos, lengths, fill=fill, raw_size=raw_size, blocksize=blocksize,
+                           sub_index=sub_index, max_len=mlen, touched_cap=touched_cap, out=out, want_sub_index=want_sub_index,
+                           relaxed=relaxed)
+        return res + (totals,)
+
     # -- append and truncate: an indexed stream made longer or shorter in place ----------------------
     def append(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, raw_size: int, blocksize: int,
                data: torch.Tensor, sub_index: torch.Tensor | None = None, new_sub_index: bool = False,

@@ -157,6 +157,10 @@ struct hufgpu_ctx {
     uint32_t *d_urow_of, *d_urow_blk, *d_upiece;
     uint64_t *d_upairs, *d_unew;
     unsigned long long *d_ucount;             /* (fixed) */
+
+    /* hufgpu_scatter (kernels/scatter.hpp): what its kernels hand to its last one; everything else it uses is the
+     * workspaces of hufgpu_gather and hufgpu_update_ranges */
+    unsigned long long *d_scount;             /* (fixed) */
 };
 
 static char g_err[512] = "";
@@ -230,6 +234,7 @@ static const ws_buf WS_FIXED[] = {
     DEV(d_zipf, 255 * sizeof(uint64_t)), DEV(d_big_offs, (SPEC_WORDS + 2) * sizeof(uint64_t)),
     DEV(d_rcounters, 8 * sizeof(unsigned long long)), DEV(d_gtotal, sizeof(uint64_t)),
     DEV(d_ucount, UPD_WORDS * sizeof(unsigned long long)), DEV(d_sb_unbuilt, sizeof(unsigned long long)),
+    DEV(d_scount, SCAT_WORDS * sizeof(unsigned long long)),
 };
 static const ws_buf WS_ENCODE[] = {
     DEV(d_hist, n * HUF_NSYM * sizeof(uint64_t)),   /* (64-bit counts for chunked blocks) */

@@ -47,5 +47,6 @@ using namespace hufgpu;
 #include "host/gather.hpp"      /* hufgpu_gather */
 #include "host/find.hpp"        /* hufgpu_find_bytes */
 #include "host/update.hpp"      /* hufgpu_update_ranges, the row encoders */
+#include "host/scatter.hpp"     /* hufgpu_scatter */
 #include "host/append.hpp"      /* hufgpu_append, hufgpu_truncate */
 #include "host/sub_build.hpp"   /* hufgpu_sub_index_from_raw, hufgpu_decode_build_sub, hufgpu_build_sub_index */

@@ -15,6 +15,9 @@
  *            sub_tile_add_kernel for blocks of 2 MiB and more)
  *   overwrite of byte ranges: decode_prepare_kernel -> drange_plan / drange_mark -> upd_class -> the indexed decoders on
  *            the staged blocks -> upd_overlay -> hist_*_pairs -> upd_index -> pack_pairs, update_copy_kernel
+ *   overwrite of records at device-resident positions, enqueue-only (hufgpu_scatter): decode_prepare_kernel, scat_mark ->
+ *            gather_scan / gather_place -> scat_class -> the indexed decoders on the staged blocks -> scat_overlay ->
+ *            scat_hist_* -> upd_index -> scat_pack, update_copy_kernel -> scat_result
  *   served straight from stream, block index and sub-index, tile by tile (sub_tile.hpp: the one checked tile item):
  *            drange_tiles_kernel, gather_serve_kernel, find_sub_kernel, find_pat_sub_kernel, find_rec_sub_kernel
  *   byte values looked for (hufgpu_find_bytes): find_sub -> find_scan -> find_finish (-> find_emit), no decoded byte stored
@@ -56,4 +59,5 @@
 #include "kernels/find.hpp"
 #include "kernels/sub_build.hpp"
 #include "kernels/update.hpp"
+#include "kernels/scatter.hpp"
 #include "kernels/append.hpp"
