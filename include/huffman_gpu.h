@@ -843,7 +843,7 @@ int hufgpu_find_records_terms(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t 
  *
  * OUT OF SCOPE: anchors together with optional positions; optional positions inside hufgpu_find_records_terms();
  * unbounded repeats ('*', '+', '{m,}': they need state carried from tile to tile) and groups ('(ab)?'); and which form
- * matched, so where a match ends.
+ * matched, so where a match ends (hufgpu_find_any_spans() reports the longest form's end).
  */
 int hufgpu_find_any_quant(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
                           const uint64_t *d_block_offsets, uint64_t nblocks,
@@ -926,7 +926,8 @@ int hufgpu_find_records_quant(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t 
  *
  * OUT OF SCOPE: anchors with HUFGPU_TERMS_ALL of several terms (which term would they bind?); optional positions in a term
  * in front of another in an ordered call (its earliest end is not to be had from a mask of starts); anchors per alternative;
- * \b INSIDE a pattern; unbounded repeats; groups; and which form matched.
+ * \b INSIDE a pattern; unbounded repeats; groups; and which form matched (hufgpu_find_any_spans() reports the longest
+ * form's length for the positions call).
  */
 int hufgpu_find_any_expr(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
                          const uint64_t *d_block_offsets, uint64_t nblocks,
@@ -947,6 +948,50 @@ int hufgpu_find_records_expr(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t s
                              uint64_t *d_rec_pos, uint32_t *d_rec_len, uint64_t *d_rec_no, uint8_t *d_rec_sel, uint64_t rec_cap, uint32_t max_len,
                              uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
                              uint32_t flags, void *stream);
+
+/*
+ * FIND, MATCH SPANS: where each occurrence ENDS.  grep -o and redaction of exactly what matched need, next to every start,
+ * the length of what lies there: an IP address, 'took [0-9]{1,5}ms', 'req-[0-9a-f]{1,8}', 'colou?r'.
+ * hufgpu_find_any_spans() is hufgpu_find_any_expr() with d_len and d_open directly behind d_pos, and that call's contract
+ * holds word for word: d_sub_index (the caller vouches for NOTHING), the same starts in the same order, d_totals[0..2],
+ * d_block_counts and d_block_errs, one-symbol blocks served, flags, batch geometry, nblocks = 0, enqueue-only without a host
+ * write or a wait, capturable - with every buffer of the caller's made outside the capture - once a call of the same sizes has
+ * made the workspaces.  A span call and an expr call with the
+ * same arguments write bit-identical d_pos, d_totals[0..2], d_block_counts and d_block_errs.  There is no CPU path.
+ *
+ *   d_len         : for every rank r < d_totals[1] - nothing else is written - the length in bytes of the LONGEST form of any
+ *                   alternative that lies at d_pos[r], QUALIFIES under `anchors` form by form as hufgpu_find_any_expr()
+ *                   defines it, and has its tested span in served blocks and inside raw_size: [p, p + len), widened by the
+ *                   right neighbour where HUFGPU_ANCHOR_EOL or HUFGPU_ANCHOR_WORD tests it.  A boundary byte is not part of
+ *                   the length.  1 <= d_len[r] <= HUFGPU_FIND_PATTERN_MAX always: a start is reported only if a qualifying
+ *                   form lies there in served blocks.  A plain number: hufgpu_gather() and hufgpu_scatter() take the array
+ *                   as it is, with max_len = HUFGPU_FIND_PATTERN_MAX.  Required when pos_cap > 0.
+ *   d_open        : optional (NULL is fine), a byte a rank: 1 when a LONGER form could not be ruled out because a byte it
+ *                   needs - one of its own or its tested right neighbour - lies in a block that is not served, else 0.
+ *   d_totals[3]   : how many of the written spans are open, whether or not d_open is given; 0 when d_totals[2] is 0.
+ *
+ * Found on the host as hufgpu_find_any_expr()'s errors are, worded "find_any_spans: ...", in that call's order; new, with
+ * the required pointers (its group 8): pos_cap > 0 with a NULL d_len, HUF_ERROR_INVALID_ARGUMENT.
+ *
+ * What runs: the expr call's chain as it is, then ONE kernel over the walk's grid that decodes the tiles holding a start
+ * below pos_cap a second time - into LDS, no decoded byte reaches memory - and runs a forward automaton from every start,
+ * reading on into the edge bytes that the walk kept of the following tiles.  Without an optional position and with one
+ * length for all alternatives nothing is decoded twice: the kernel that writes d_pos writes the constant.  The seventeen
+ * older calls launch what they always did.  The worst case - every byte a start of 64 steps - and the measurements are in
+ * DESIGN.md 5.26.
+ *
+ * OUT OF SCOPE: the non-overlapping leftmost-longest selection that grep -o prints (EVERY start is reported, overlapping
+ * ones included, as the family always has); spans for the records calls; the ends of a quantified middle term of an ordered
+ * call; unbounded repeats; groups.
+ */
+int hufgpu_find_any_spans(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
+                          const uint64_t *d_block_offsets, uint64_t nblocks,
+                          const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                          const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts, const uint8_t *optional,
+                          const uint8_t delim_set[32], const uint8_t word_set[32], uint32_t anchors,
+                          uint64_t *d_pos, uint32_t *d_len, uint8_t *d_open, uint64_t pos_cap,
+                          uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
+                          uint32_t flags, void *stream);
 
 /*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from

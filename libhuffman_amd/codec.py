@@ -1116,6 +1116,90 @@ class GpuCodec:
                                                word=word, word_bytes=word_bytes, delimiters=delimiters)
         return totals, errs
 
+    SPAN_MAX = _native.FIND_PATTERN_MAX     # no reported length is above it: the max_len of gather / scatter behind find_spans
+
+    @staticmethod
+    def _span_key(pattern, ignore_case, bol, eol, whole_line, word, word_bytes, delimiters):
+        """(key, fixed): `pattern` - whatever find_pattern takes - as hufgpu_find_any_spans' part of the C argument list, classes
+        to anchors, and the one length of all its forms (None when there are several).  Raises what find_pattern raises."""
+        if isinstance(pattern, GpuCodec._Terms) or (isinstance(pattern, GpuCodec.Expr) and len(pattern) > 1):
+            raise TypeError(f"{type(pattern).__name__} selects records: find_records, count_records and grep take it, a search for "
+                            "positions does not")
+        if isinstance(pattern, GpuCodec.Expr):
+            GpuCodec._expr_alone(pattern, bol, eol, whole_line, word, word_bytes)
+            x = GpuCodec.expr_arrays(pattern, ignore_case, None)
+            classes, alt_lens, optional = x["classes"].tobytes(), x["alt_lens"], x["optional"]
+            anchors, ws = x["anchors"], x["word_set"]
+        else:
+            route, key, _, (anchors, ws) = GpuCodec._find_route(pattern, ignore_case, anchors=(bol, eol, whole_line, word, word_bytes))
+            optional = None
+            if route == "literal":
+                classes, alt_lens = GpuCodec.byte_classes(key[0]).tobytes(), np.array([key[1]], np.uint32)
+            elif route == "classes":
+                classes, alt_lens = key[0], np.array([key[1]], np.uint32)
+            else:
+                classes, alt_lens = key[0], np.frombuffer(key[1], np.uint32)
+                optional = np.frombuffer(key[3], np.uint8) if route == "quant" else None
+        lens = set(alt_lens.tolist())
+        fixed = lens.pop() if len(lens) == 1 and (optional is None or not optional.any()) else None
+        key = (classes, alt_lens.tobytes(), len(alt_lens), None if optional is None else optional.tobytes(),
+               GpuCodec.byte_set(delimiters), ws, anchors)
+        return key, fixed
+
+    def find_spans(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
+                   sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, max_positions: int = 0,
+                   block_counts: bool = False, relaxed: bool = False, out=None, want_open: bool = True,
+                   ignore_case: bool = False, bol: bool = False, eol: bool = False, whole_line: bool = False,
+                   word: bool = False, word_bytes=None, delimiters=b"\n"):
+        """find_pattern with the LENGTH of what lies at every start (hufgpu_find_any_spans): the same patterns - a literal,
+        classes, an AnyOf, Opt / Rep items, regex(), a one-term Expr / egrep() - and keywords, the same starts in the same order.
+        Returns CUDA tensors (positions int64, lengths int32, totals, block_errs, block_counts, open): lengths[r], for
+        r < totals[1], is the length of the LONGEST form of any alternative that lies at positions[r], qualifies under the
+        anchors and has its tested span in served blocks - 1 to SPAN_MAX, a boundary byte not counted -, so gather() and
+        scatter() take the tensor as it is with max_len = SPAN_MAX.  open[r] (uint8; None with `want_open=False`) is 1 when a
+        longer form could not be ruled out because a byte it needs lies in a block that is not served; totals[3] counts those.
+        `out`: (positions, lengths) or (positions, lengths, open), contiguous [max_positions] buffers; made when not given.
+        Every start is reported, overlapping ones included: the leftmost-longest selection of grep -o is the caller's.
+        Raises what find_pattern raises."""
+        key, _ = self._span_key(pattern, ignore_case, bol, eol, whole_line, word, word_bytes, delimiters)
+        max_positions = int(max_positions)
+        given = tuple(out) if out is not None else ()
+        if out is not None and len(given) not in (2, 3):
+            raise ValueError("`out` is (positions, lengths) or (positions, lengths, open)")
+        pos = self._find_buffer(given[0] if given else None, max_positions, torch.int64)
+        lens = self._find_buffer(given[1] if given else None, max_positions, torch.int32)
+        opn = self._find_buffer(given[2] if len(given) == 3 else None, max_positions, torch.uint8) if want_open else None
+        head, tail, totals, errs, counts = self._find_args(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize,
+                                                           block_counts, relaxed)
+        err = self.lib.hufgpu_find_any_spans(*head, *key, pos.data_ptr() if max_positions else None,
+                                             lens.data_ptr() if max_positions else None,
+                                             opn.data_ptr() if want_open and max_positions else None, max_positions, *tail)
+        self._check(err, "Failed to enqueue the search")
+        return pos, lens, totals, errs, counts, opn
+
+    def _spans_for(self, stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern, max_matches, relaxed, find):
+        """find_spans for the pipelines: (positions, lengths, totals) with the entries behind totals[1] made harmless on the
+        device - a record at raw_size of length 0 reads and writes nothing"""
+        pos, lens, totals = self.find_spans(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
+                                            max_positions=max_matches, relaxed=relaxed, want_open=False, **find)[:3]
+        written = torch.arange(max_matches, device=self.tdev) < totals[1]
+        return torch.where(written, pos, raw_size), torch.where(written, lens, 0), totals
+
+    def extract(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, sub_index: torch.Tensor,
+                raw_size: int, blocksize: int, pattern, max_matches: int, *, out: torch.Tensor | None = None,
+                relaxed: bool = False, **find):
+        """What a search finds, byte for byte: find_spans followed by gather(), on torch's current stream with no host wait
+        in between - grep -o without its selection of non-overlapping matches: EVERY start is a row.  `max_matches` is the
+        search's cap, `**find` are its keywords (`ignore_case`, `bol`, `word`, ...).  Returns CUDA tensors (slots uint8
+        [max_matches, >= SPAN_MAX] - row r holds lengths[r] bytes -, positions, lengths, statuses, totals): statuses are
+        gather()'s per row, and the rows behind totals[1] are made harmless on the device (position raw_size, length 0)."""
+        max_matches = int(max_matches)
+        pos, lens, totals = self._spans_for(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
+                                            max_matches, relaxed, find)
+        slots, statuses, _ = self.gather(stream, stream_len, offsets, nblocks, pos, lens, sub_index=sub_index, raw_size=raw_size,
+                                         blocksize=blocksize, max_len=self.SPAN_MAX, out=out, relaxed=relaxed)
+        return slots, pos, lens, statuses, totals
+
     def find_records(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, delimiters=b"\n",
                      max_records: int = 0, max_len: int = 0, block_counts: bool = False, relaxed: bool = False, out=None,
@@ -1452,7 +1536,7 @@ class GpuCodec:
     def redact(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, sub_index: torch.Tensor,
                raw_size: int, blocksize: int, pattern, fill=b"*", *, max_matches: int, lines: bool = False, max_len: int = 0,
                touched_cap: int | None = None, out: torch.Tensor | None = None, want_sub_index: bool = False,
-               relaxed: bool = False, **find):
+               relaxed: bool = False, spans: bool = False, **find):
         """Blank what a search finds: find_pattern (or, with `lines=True`, find_records) followed by scatter(fill=...), on
         torch's current stream with no host wait in between.  Every byte of every occurrence of `pattern` becomes `fill`;
         with `lines=True` the first `max_len` bytes of every selected record do (the delimiter stays).  `max_matches` is
@@ -1461,7 +1545,10 @@ class GpuCodec:
         `invert`, ...).
         A search for positions reports where a match STARTS; where it ends is known only for a pattern of one length - a
         literal, a list / tuple of classes, an AnyOf whose alternatives all have that length.  Opt / Rep items, an Expr
-        and an AnyOf of unequal lengths raise ValueError without `lines=True`.
+        and an AnyOf of unequal lengths raise ValueError without `lines=True` - or `spans=True`: then the search is
+        find_spans, which takes every positions pattern, and the LONGEST form at every start is blanked (scatter with the
+        lengths tensor, max_len = SPAN_MAX).  Every start counts, overlapping ones included: what is blanked is the union of
+        the spans.  `spans=True` with `lines=True` is a ValueError.
         The scatter is given the search's cap as its number of records, not the found count, which is on the device.  The
         entries behind the found count are made harmless on the device before it runs: positions from totals[1] on are
         replaced by raw_size (and lengths by 0) - a record that starts at raw_size writes nothing.
@@ -1473,7 +1560,13 @@ class GpuCodec:
         `result`, and nothing written outside the buffers, if more blocks are touched) and may pass `out=`.
         Returns (out, new_offsets, result, new sub-index or None, totals): scatter()'s, and the search's totals."""
         max_matches = int(max_matches)
-        if lines:
+        if spans and lines:
+            raise ValueError("redact(spans=True) blanks what matched, redact(lines=True) the records that hold it: give one")
+        if spans:
+            pos, lengths, totals = self._spans_for(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
+                                                   max_matches, relaxed, find)
+            mlen = self.SPAN_MAX
+        elif lines:
             if int(max_len) < 1:
                 raise ValueError("redact(lines=True) needs max_len, the bytes of a record that are blanked at most")
             found = self.find_records(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,

@@ -6,7 +6,8 @@
    the context call for the matches that begin or end at a record's or a word's edge; hufgpu_find_any_quant and
    hufgpu_find_records_quant are those two for patterns with optional positions; hufgpu_find_records_terms is the
    context call for the records that hold all of several terms, or all of them in order; hufgpu_find_any_expr and
-   hufgpu_find_records_expr take anchors, terms and optional positions together.  All enqueue-only.  A
+   hufgpu_find_records_expr take anchors, terms and optional positions together; hufgpu_find_any_spans is the expr positions
+   call with the length of the longest form at every start.  All enqueue-only.  A
    wrapper describes its call in three structs; find_call checks them (find_check, no HIP call), fills the kernels'
    arguments and grows the workspace (find_fill) and enqueues the chain of kernels/find.hpp (find_enqueue).
    Part of hufgpu_api.hip (one translation unit). */
@@ -76,6 +77,17 @@ struct FindTermCall {
     bool ordered;
 };
 
+/* what hufgpu_find_any_spans has beyond the expr positions call: where the lengths and the flags go, and - filled by
+ * find_span_tables once the call's own checks have passed - either the one length of all forms (`fixed`: find_emit_len_kernel in
+ * the place of find_emit_kernel) or find_span_kernel's forward table */
+struct FindSpanCall {
+    uint32_t *d_len;
+    uint8_t *d_open;                        /* optional */
+    bool fixed;
+    uint32_t value;
+    FindSpanArgs args;
+};
+
 /* What is looked for: `who` words the errors, `key` is the set (plen = 0) or the pattern of plen bytes, `key_name` its name;
  * rec is NULL but for the records' calls.  cls is NULL but for the class calls: then `key` is the caller's array of plen
  * classes, which find_call only checks for NULL and never reads - its wrapper has read it -, and cls is the table made
@@ -91,7 +103,8 @@ struct FindTermCall {
  * position count, and the walk and the seam kernel close the state over the optional positions (find_opt_masks).
  * expr is NULL but for the expr calls where they cross those three: optional positions with a tested byte behind a match,
  * and two terms or more with an optional position or an anchor.  Then opt is expr's (its masks 0 without an optional
- * position), and the walk and the seam kernel are the ones with the closure, the seam kernel's with the data's end. */
+ * position), and the walk and the seam kernel are the ones with the closure, the seam kernel's with the data's end.
+ * span is NULL but for the span call: the expr positions call with a length a start, written behind the whole chain. */
 struct FindKey {
     const char *who, *key_name;
     const uint8_t *key;
@@ -105,6 +118,7 @@ struct FindKey {
     FindTermCall *term;
     FindOptArgs *opt;
     FindExprArgs *expr;
+    FindSpanCall *span;
 };
 
 /* does the context call widen the answer: with both distances 0 it is the select call, maybe with flags */
@@ -142,6 +156,8 @@ static int find_check(hufgpu_ctx_t *ctx, const FindStream &in, const FindOut &ou
             return find_bad(ctx, "%s: rec_cap %llu needs d_rec_pos and d_rec_len", who, (unsigned long long)out.cap);
     } else if (out.cap > 0 && !out.d_pos) {
         return find_bad(ctx, "%s: pos_cap %llu needs d_pos", who, (unsigned long long)out.cap);
+    } else if (out.cap > 0 && k.span && !k.span->d_len) {
+        return find_bad(ctx, "%s: pos_cap %llu needs d_len", who, (unsigned long long)out.cap);
     }
     if (in.nblocks == 0) {
         if (in.raw_size != 0)
@@ -391,8 +407,19 @@ static int find_enqueue(hufgpu_ctx_t *ctx, const FindOut &out, const FindKey &k,
         find_rec_emit_no_kernel<<<tiles, et, 0, s>>>(sa);
     } else if (out.cap > 0 && k.rec) {
         find_rec_emit_kernel<<<tiles, et, 0, s>>>(ra);
+    } else if (out.cap > 0 && k.span && k.span->fixed) {
+        const FindEmitLenArgs ea = {fa, k.span->d_len, k.span->d_open, k.span->value};
+        find_emit_len_kernel<<<tiles, et, 0, s>>>(ea);
     } else if (out.cap > 0) {
         find_emit_kernel<<<tiles, et, 0, s>>>(fa);
+    }
+    if (out.cap > 0 && k.span && !k.span->fixed) {
+        /* the walk's grid once more: the tiles with a start below the cap are decoded again, the others cost a look */
+        FindSpanArgs &sa = k.span->args;
+        sa.qa.a.r = ra;
+        sa.len = k.span->d_len;
+        sa.open = k.span->d_open;
+        find_span_kernel<<<walk, dim3(FIND_THREADS), 0, s>>>(sa);
     }
     HIP_OK(ctx, hipGetLastError());
     return HUFE_OK;
@@ -638,11 +665,42 @@ static int find_opt_masks(hufgpu_ctx_t *ctx, const char *who, const uint32_t *al
     return HUFE_OK;
 }
 
+/* hufgpu_find_any_spans, behind the expr call's checks of the alternatives (so: 1 to 64 of them, lengths that sum to at most
+ * 64 - 63 with `behind` -, no empty class, no alternative that is all optional): without an optional position and with one
+ * length for all alternatives that length is the answer.  Else the forward table of kernels/find.hpp's FindSpanArgs:
+ * find_alt_table and find_opt_masks as they are, over every alternative's classes and `optional` bytes in reverse order, and
+ * with `behind` bit 0 of every entry that may stand behind a form. */
+static int find_span_tables(const char *who, const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts, const uint8_t *optional,
+                            bool quant, const uint8_t *behind, FindSpanCall *span)
+{
+    span->fixed = !quant;
+    span->value = alt_lens[0];
+    for (uint32_t j = 1; j < n_alts; j++) span->fixed &= alt_lens[j] == alt_lens[0];
+    if (span->fixed) return HUFE_OK;
+    uint8_t rcl[HUFGPU_FIND_PATTERN_MAX * 32], rop[HUFGPU_FIND_PATTERN_MAX];
+    for (uint32_t j = 0, at = 0; j < n_alts; at += alt_lens[j++]) {
+        for (uint32_t i = 0, len = alt_lens[j]; i < len; i++) {
+            memcpy(rcl + 32u * (at + i), classes + 32u * (at + len - 1u - i), 32);
+            rop[at + i] = optional ? optional[at + len - 1u - i] : 0;
+        }
+    }
+    FindSpanArgs &sa = span->args;
+    memset(&sa, 0, sizeof(sa));
+    uint32_t maxform = 0;
+    bool any = false;
+    if (find_alt_table(NULL, who, rcl, alt_lens, n_alts, NULL, &sa.qa.a, &maxform) ||
+        find_opt_masks(NULL, who, alt_lens, n_alts, rop, &sa.qa, &any))
+        return HUFE_ARGUMENT;                                       /* (cannot be: the call's own tables have been made of the same) */
+    sa.behind = behind != NULL;
+    for (uint32_t v = 0; behind && v < 256; v++) sa.qa.a.t.m[v][0] |= (uint32_t)((behind[v >> 3] >> (v & 7)) & 1);
+    return HUFE_OK;
+}
+
 /* the nine any-of wrappers' call: the table, when both arrays are there (find_check words a missing one), then find_call */
 static int find_alt_call(hufgpu_ctx_t *ctx, const char *who, const FindStream &in, const FindOut &out, const uint8_t *classes,
                          const uint32_t *alt_lens, uint32_t n_alts, const FindRecCall *rec, const FindSelCall *sel, const FindCtxCall *cx,
                          uint32_t flags, void *stream, const FindAncCall *anc = NULL, FindTermCall *term = NULL,
-                         const uint32_t *term_alts = NULL, const uint8_t *optional = NULL)
+                         const uint32_t *term_alts = NULL, const uint8_t *optional = NULL, FindSpanCall *span = NULL)
 {
     FindExprArgs x;                         /* (the older calls use its FindOptArgs, or that one's FindAltArgs, and nothing else) */
     FindOptArgs &q = x.qa;
@@ -676,8 +734,9 @@ static int find_alt_call(hufgpu_ctx_t *ctx, const char *who, const FindStream &i
         const uint32_t bit = (t.hl[j] & 63u) - alt_lens[j];
         x.bnd[bit >> 5] |= 1u << (bit & 31u);
     }
+    if (both && span && find_span_tables(who, classes, alt_lens, n_alts, optional, quant, behind, span)) return HUFE_ARGUMENT;
     const FindKey k = {who, "classes, alt_lens", both ? classes : NULL, maxlen, rec, &t.t, &t, sel, cx, anc, term,
-                       quant || cross ? &q : NULL, cross ? &x : NULL};
+                       quant || cross ? &q : NULL, cross ? &x : NULL, span};
     return find_call(ctx, in, out, k, flags, stream);
 }
 
@@ -893,6 +952,27 @@ extern "C" int hufgpu_find_any_expr(hufgpu_ctx_t *ctx, const void *d_stream, uin
     const FindOut out = {d_pos, pos_cap, d_block_counts, d_totals, d_block_errs};
     return find_alt_call(ctx, "find_any_expr", in, out, classes, alt_lens, n_alts, NULL, NULL, NULL, flags, stream, anchors ? &anc : NULL, NULL,
                          NULL, optional);
+}
+
+/* hufgpu_find_any_spans: hufgpu_find_any_expr with d_len and d_open behind d_pos */
+extern "C" int hufgpu_find_any_spans(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                     uint64_t nblocks, const void *d_sub_index, uint64_t raw_size, uint64_t blocksize,
+                                     const uint8_t *classes, const uint32_t *alt_lens, uint32_t n_alts, const uint8_t *optional,
+                                     const uint8_t delim_set[32], const uint8_t word_set[32], uint32_t anchors, uint64_t *d_pos,
+                                     uint32_t *d_len, uint8_t *d_open, uint64_t pos_cap, uint64_t *d_block_counts, uint64_t *d_totals,
+                                     int32_t *d_block_errs, uint32_t flags, void *stream)
+{
+    FindAncCall anc;
+    if (anchors && find_anc_sets(ctx, "find_any_spans", anchors, delim_set, word_set, false, &anc)) return HUFE_ARGUMENT;
+    const FindStream in = {d_stream, stream_len, d_block_offsets, nblocks, d_sub_index, raw_size, blocksize};
+    const FindOut out = {d_pos, pos_cap, d_block_counts, d_totals, d_block_errs};
+    FindSpanCall span;
+    span.d_len = d_len;
+    span.d_open = d_open;
+    span.fixed = true;
+    span.value = 0;
+    return find_alt_call(ctx, "find_any_spans", in, out, classes, alt_lens, n_alts, NULL, NULL, NULL, flags, stream, anchors ? &anc : NULL, NULL,
+                         NULL, optional, &span);
 }
 
 /* hufgpu_find_records_expr: the `select` check, the anchored calls' checks, the terms call's - an ordered call's last term

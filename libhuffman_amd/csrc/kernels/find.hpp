@@ -46,6 +46,9 @@
                                    2 to 4 terms without an optional position or an anchor: the terms call's chain.  Else
                                    find_rec_term_opt_sub -> find_term_opt_seam in the place of find_rec_term_sub -> find_term_seam,
                                    and - ORDERED with BOL / WORD - find_anchor over term 0's mask in front of dscan / mark
+   hufgpu_find_any_spans           the expr positions call's chain to its end, then find_span: the walk's grid once more, for the
+                                   tiles with a start below pos_cap.  No optional position and one length for all alternatives:
+                                   find_emit_len in the place of find_emit, and no find_span
    RECORDS = find_rec_dscan -> find_rec_mark -> find_scan -> find_finish [-> find_rec_emit]; no seam kernel for 1 byte
 
    The walk: find_sub_body, the nine *_sub kernels, find_rec_term_sub_kernel and find_rec_term_opt_sub_kernel
@@ -105,6 +108,14 @@
      find_finish_kernel    per-block counts as differences of the tiles' ranks, and d_totals[1];
      find_emit_kernel      one wave a tile, a lane a mask word: rank = the tile's + the wave's scan of popcounts, and
                            b B + 32 g + bit goes to d_pos[rank] for every set bit whose rank is below pos_cap.
+
+     find_span_kernel      hufgpu_find_any_spans: the length of the longest form at every reported start.  The walk's geometry; a
+                           chunk without a start below the cap leaves before it builds tables, a tile with one is decoded
+                           again into LDS (the checked item, as in the walk) and every set bit of the FINAL mask starts a
+                           forward Shift-And run - seeded once, find_opt_step over a table of the reversed positions - that
+                           remembers the last accepting step; bytes behind the tile come from the head edges of the tiles
+                           behind, by the seam kernels' layout walk.  d_len, d_open by the emit kernel's ranks; d_totals[3].
+     find_emit_len_kernel  find_emit_kernel with a constant length a start: the span call for patterns of one length.
 
    Records.  A record is [s, e) between two delimiters (or byte 0, or raw_size) and is reported once, when it holds a
    match and every block from the delimiter in front of it to the one that ends it is served.
@@ -1056,6 +1067,204 @@ __global__ __launch_bounds__(FIND_EMIT_THREADS) void find_emit_kernel(FindArgs a
     const uint64_t base = b * a.s.bsize + g * DSUB_SPL;
     while (m != 0u && r < a.pos_cap) {
         a.pos[r++] = base + (uint32_t)__builtin_ctz(m);
+        m &= m - 1u;
+    }
+}
+
+/* ---- hufgpu_find_any_spans: where the longest form at every reported start ends ------------------------------------- */
+
+/* Behind the expr call's whole chain.  The walk's automaton runs over the REVERSED pattern and sees a match at its start, so
+ * no end is in its state; this one runs FORWARD from a start.  qa holds the forward table: find_alt_table and find_opt_masks
+ * over every alternative's positions in REVERSE order, so that find_cls_step's shift moves from a position to the NEXT one
+ * and find_opt_close leaves out the optional positions that FOLLOW.  Its t.first are then the positions that may hold a
+ * form's FIRST byte - the seed, used once -, its `starts` the bit of every alternative's last position: set behind the
+ * closure, a form ends with this byte.  The table has no boundary position: with `behind` bit 0 of an entry's low half says
+ * "this byte may stand behind a form" (with EOL / WORD the positions sum to at most 63, so bit 63 ... 1 hold them), and a form
+ * that ends with the data has nothing behind it.  qa.a.r.p is the call's own: f as scan and finish left it (the final
+ * mask, the tile counts, the scan), the edges, and plen - the longest form's bytes, + 1 with `behind`: no start reads more. */
+struct FindSpanArgs {
+    FindOptArgs qa;
+    uint32_t behind;                        /* is the byte behind a form tested (EOL / WORD) */
+    uint32_t *len;                          /* [pos_cap] */
+    uint8_t *open;                          /* [pos_cap], optional */
+};
+static_assert(sizeof(FindSpanArgs) <= 4096, "a kernel's arguments end at 4 KiB");
+
+#define FIND_SPAN_END 256u                  /* find_span_next: the data ends here */
+#define FIND_SPAN_OPEN 257u                 /* ... or a block that is not served begins */
+
+/* the bytes behind a tile's end, one at a time: the head slots of the tiles behind it, by find_seam_candidate's walk over
+ * the layout's tile lengths.  A start reads at most plen - 1 of them, so never more than a head slot holds. */
+struct FindSpanTail {
+    uint64_t cb, ct, cblen;
+    const uint8_t *e;
+    uint32_t off, csym;                     /* the next byte is e[off]; csym bytes there belong to tile (cb, ct) */
+};
+__device__ __forceinline__ uint32_t find_span_next(const FindPatArgs &pa, FindSpanTail &w)
+{
+    const FindArgs &a = pa.f;
+    while (w.off == w.csym) {
+        if ((w.ct + 1) * HUF_SUB_TILE < w.cblen) {
+            w.ct++;
+        } else {
+            w.cb++;
+            w.ct = 0;
+            if (w.cb >= a.s.nblocks) return FIND_SPAN_END;
+            if (a.errs[w.cb] != HUFE_OK) return FIND_SPAN_OPEN;
+            w.cblen = find_block_len(a, w.cb);
+        }
+        w.e = pa.edges + (w.cb * a.tpb + w.ct) * FIND_EDGE_SLOT;
+        w.off = 0;
+        w.csym = find_tile_syms(w.cblen, w.ct);
+    }
+    return w.e[w.off++];
+}
+
+/* The longest qualifying form at start s of the wave's decoded tile (tsym bytes in `bytes`, tile t of block b), and whether a
+ * longer one could not be ruled out.  Seeded once; a step clears the last positions' bits first, so that no bit leaves its
+ * alternative for the one above (the walk's automaton sets that bit anyway, this one must not).  `pending`: a form ended
+ * with the byte before and waits for the byte behind it.  The loop ends when nothing is alive and nothing waits, at the end
+ * of the data - which qualifies what waits -, at a block that is not served - which leaves the span open when anything is
+ * alive or waits -, and after plen bytes at the latest. */
+__device__ __forceinline__ uint32_t find_span_one(const FindSpanArgs &sa, const uint32_t *s_m, const uint8_t *bytes, uint32_t tsym, uint64_t b,
+                                                  uint64_t t, uint64_t blen, uint32_t s, bool &open)
+{
+    const FindAltArgs &aa = sa.qa.a;
+    const FindPatArgs &pa = aa.r.p;
+    const uint32_t slo = aa.starts[0], shi = aa.starts[1];
+    FindSpanTail w = {b, t, blen, nullptr, 0u, 0u};
+    uint32_t lo = 0, hi = 0, flo = aa.t.first[0], fhi = aa.t.first[1], len = 0;
+    bool pending = false;
+    open = false;
+    for (uint32_t k = 0; k < pa.plen; k++) {
+        const uint32_t x = s + k < tsym ? (uint32_t)bytes[s + k] : find_span_next(pa, w);
+        if (x >= FIND_SPAN_END) {
+            if (x == FIND_SPAN_END) len = pending ? k : len;
+            else open = pending || ((lo & ~slo) | (hi & ~shi)) != 0u;
+            break;
+        }
+        if (pending && (s_m[2u * x] & 1u) != 0u) len = k;
+        lo &= ~slo;
+        hi &= ~shi;
+        find_opt_step(lo, hi, s_m, flo, fhi, x, sa.qa.q);
+        flo = fhi = 0u;
+        const bool acc = ((lo & slo) | (hi & shi)) != 0u;
+        if (acc && sa.behind == 0u) len = k + 1u;
+        pending = acc && sa.behind != 0u;
+        if (!pending && ((lo & ~slo) | (hi & ~shi)) == 0u) break;
+    }
+    return len;
+}
+
+/* The walk's geometry - a workgroup = one (block, chunk), a wave takes tiles - for the tiles that hold a start below pos_cap
+ * only: a chunk of a block that is not served, without a start or behind the cap leaves before it builds tables.  Such a tile
+ * is decoded once more into the wave's LDS slice with the checked item of sub_tile.hpp (the walk of this same call has passed
+ * it already; no bound of an access here rests on that), a block of one byte value is copies of its leaf.  Then a lane takes the set bits
+ * of its word of the FINAL start mask - behind the seam and anchor kernels -, one automaton run each: up to 32 starts of up to
+ * plen steps a lane ('a{1,64}' over a run of 'a').  Length and flag go to the tile's rank + the rank inside the tile, as
+ * find_emit_kernel numbers the starts; the open spans are counted into d_totals[3], one atomic a wave. */
+__global__ __launch_bounds__(FIND_THREADS) void find_span_kernel(FindSpanArgs sa)
+{
+    typedef DsubShared<FIND_THREADS> SH;
+    __shared__ SH sh;
+    __shared__ __attribute__((aligned(16))) uint32_t s_tile[FIND_WAVES][HUF_SUB_TILE / 4];
+    __shared__ alignas(8) uint32_t s_m[FIND_CLS_WORDS];
+    const FindPatArgs &pa = sa.qa.a.r.p;
+    const FindArgs &a = pa.f;
+    const uint32_t lane = (uint32_t)lane_id(), wave = uni32(threadIdx.x >> 6);
+    const uint64_t b = blockIdx.x / a.cpb;
+    const uint32_t c = blockIdx.x % a.cpb;
+    const uint64_t blen = find_block_len(a, b);
+    const uint64_t sym0 = (uint64_t)c * DSUB_CHUNK_SYMS;
+    if (sym0 >= blen || a.errs[b] != HUFE_OK) return;
+    const uint64_t sym1 = dmin<uint64_t>(blen, sym0 + DSUB_CHUNK_SYMS);
+    const uint64_t t0 = sym0 / HUF_SUB_TILE;
+    const uint32_t nt = (uint32_t)((sym1 - sym0 + HUF_SUB_TILE - 1) / HUF_SUB_TILE);
+    static_assert(DSUB_CHUNK_SYMS / HUF_SUB_TILE <= 64, "a lane a tile of the chunk");
+    /* (every wave asks for the whole chunk, so the answer is the workgroup's) */
+    if (__ballot(lane < nt && a.tcnt[b * a.tpb + t0 + lane] != 0u) == 0ull) return;
+    if (two_level_prefix(a.scan, b * a.tpb + t0) >= a.pos_cap) return;
+    static_assert(FIND_THREADS == FIND_CLS_WORDS, "a thread a word of the table");
+    s_m[threadIdx.x] = sa.qa.a.t.m[threadIdx.x >> 1][threadIdx.x & 1u];
+    __syncthreads();
+    BlockHeader h;
+    if (parse_block_header(a.s.stream, a.s.stream_len, a.s.offsets[b], a.s.offsets[b + 1], a.s.max_tree, h) != HUFE_OK || h.block_len != blen)
+        return;                                                     /* (the walk has seen it parse) */
+    const SubBlockView v = sub_block_view(h, a.s.sub, b);
+    const int leaf = h.tree_len == 5 ? single_leaf_symbol(h.tree) : -1;
+    uint32_t *tile_words = s_tile[wave];
+    uint32_t *top = nullptr;
+    if (leaf >= 0) {
+#pragma unroll
+        for (uint32_t j = 0; j < 8; j++) tile_words[8u * lane + j] = 0x01010101u * (uint32_t)leaf;
+    } else {
+        const DsubTreeWords tw = dsub_tree_request<FIND_THREADS>(h.tree, h.tree_len, a.s.sub.lens + b * HUF_NSYM);
+        if (!dsub_fast_tables<FIND_THREADS>(sh, h.tree_len, tw)) return;    /* (workgroup-uniform) */
+        top = DsubLds<FIND_THREADS>::slice(sh, (int)wave) + (SH::SLICE_WORDS - 1u);
+    }
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(tile_words);
+    uint32_t nopen = 0;
+    for (uint64_t t = t0 + wave; t * HUF_SUB_TILE < sym1; t += FIND_WAVES) {
+        const uint64_t i = b * a.tpb + t;
+        if (a.tcnt[i] == 0u) continue;                              /* (the wave's) */
+        const uint64_t rank0 = two_level_prefix(a.scan, i);
+        if (rank0 >= a.pos_cap) continue;
+        if (leaf < 0) {
+            uint32_t nsym;
+            /* (a tile that fails here has failed in the walk of this call, which read the same words: its block is not
+             * served and the exit above has taken it.  Memory safety rests on the checks; that every rank below
+             * d_totals[1] gets its length rests on the walk's verdict being this one) */
+            if (!sub_tile_checked<FIND_THREADS>(sh, top, v, t, reinterpret_cast<uint8_t *>(tile_words), nsym)) continue;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       /* the lanes' bytes are in LDS before other lanes read them */
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t tsym = find_tile_syms(blen, t);
+        const uint64_t g = t * 64u + lane;
+        uint32_t m = g * DSUB_SPL < blen ? a.bitmap[b * a.wpb + g] : 0u;
+        uint64_t r = rank0 + (wave_incl_scan_u32((uint32_t)__popc(m)) - (uint32_t)__popc(m));
+        while (m != 0u && r < a.pos_cap) {
+            bool open;
+            const uint32_t len = find_span_one(sa, s_m, bytes, tsym, b, t, blen, 32u * lane + (uint32_t)__builtin_ctz(m), open);
+            sa.len[r] = len;
+            if (sa.open) sa.open[r] = (uint8_t)open;
+            nopen += (uint32_t)open;
+            r++;
+            m &= m - 1u;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");       /* ... and read before the next tile overwrites them */
+        __builtin_amdgcn_wave_barrier();
+    }
+    nopen = wave_total_u32(nopen);
+    if (lane == 0 && nopen != 0u) atomicAdd((unsigned long long *)&a.totals[3], (unsigned long long)nopen);
+}
+
+/* No optional position and one length for all alternatives: nothing is decoded twice.  find_emit_kernel with that length
+ * for every start it writes; no span is open. */
+struct FindEmitLenArgs {
+    FindArgs f;
+    uint32_t *len;
+    uint8_t *open;                          /* optional */
+    uint32_t value;
+};
+__global__ __launch_bounds__(FIND_EMIT_THREADS) void find_emit_len_kernel(FindEmitLenArgs ea)
+{
+    const FindArgs &a = ea.f;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t i = find_tile_index<FIND_EMIT_THREADS>();
+    if (i >= a.ntiles) return;
+    const auto [b, t, blen] = find_tile(a, i);
+    if (t * HUF_SUB_TILE >= blen || a.errs[b] != HUFE_OK) return;
+    const uint64_t rank0 = two_level_prefix(a.scan, i);
+    if (rank0 >= a.pos_cap) return;
+    const uint64_t g = t * 64u + lane;
+    uint32_t m = g * DSUB_SPL < blen ? a.bitmap[b * a.wpb + g] : 0u;
+    uint64_t r = rank0 + (wave_incl_scan_u32((uint32_t)__popc(m)) - (uint32_t)__popc(m));
+    const uint64_t base = b * a.s.bsize + g * DSUB_SPL;
+    while (m != 0u && r < a.pos_cap) {
+        a.pos[r] = base + (uint32_t)__builtin_ctz(m);
+        ea.len[r] = ea.value;
+        if (ea.open) ea.open[r] = 0;
+        r++;
         m &= m - 1u;
     }
 }
