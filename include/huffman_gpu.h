@@ -981,7 +981,7 @@ int hufgpu_find_records_expr(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t s
  * DESIGN.md 5.26.
  *
  * OUT OF SCOPE: the non-overlapping leftmost-longest selection that grep -o prints (EVERY start is reported, overlapping
- * ones included, as the family always has); spans for the records calls; the ends of a quantified middle term of an ordered
+ * ones included, as the family always has: hufgpu_select_spans() selects from them); spans for the records calls; the ends of a quantified middle term of an ordered
  * call; unbounded repeats; groups.
  */
 int hufgpu_find_any_spans(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stream_len,
@@ -992,6 +992,63 @@ int hufgpu_find_any_spans(hufgpu_ctx_t *ctx, const void *d_stream, uint64_t stre
                           uint64_t *d_pos, uint32_t *d_len, uint8_t *d_open, uint64_t pos_cap,
                           uint64_t *d_block_counts, uint64_t *d_totals, int32_t *d_block_errs,
                           uint32_t flags, void *stream);
+
+/*
+ * SELECT SPANS: grep -o's non-overlapping leftmost-longest matches, chosen on the device from the spans that
+ * hufgpu_find_any_spans() reports.  That call reports EVERY start: '[0-9]{1,3}' on "1234" gives 0:3, 1:3, 2:2, 3:1, and
+ * grep -o prints 0:3 and 3:1.  The selection is a chain - the next match is the first start at or behind the end of the match
+ * just taken - whose lengths are known only on the device; hufgpu_select_spans() walks it there, enqueue-only, so that
+ * find_any_spans -> select_spans -> gather | scatter runs with no operation of the caller's in between and no host wait.
+ *
+ *   d_pos, d_len  : spans by rank, exactly as hufgpu_find_any_spans() leaves them: positions strictly ascending,
+ *                   1 <= len <= HUFGPU_FIND_PATTERN_MAX.  Required.
+ *   d_n, n_cap    : the number of spans is n = min(*d_n, n_cap).  d_n is a DEVICE word - &d_totals[1] of the span call can
+ *                   be passed as it is -; NULL means n = n_cap.  Nothing at or behind rank n is read for its value.  n_cap
+ *                   sizes the grids - rows beyond n do nothing - and is at most HUFGPU_SELECT_MAX.
+ *
+ * The selection: rank 0 is selected; after a selected rank s the next selected rank is the least r > s with
+ * pos[r] >= pos[s] + len[s].  When the span call served every block (d_totals[2] == 0) and was not cut
+ * (d_totals[0] == d_totals[1]), this is the set that grep -o -E prints.  Otherwise it is the greedy selection over what was
+ * reported.
+ *
+ *   d_sel_pos, d_sel_len : the selected spans, compacted and in ascending order: the first min(selected, sel_cap) are written
+ *                   and nothing behind them (but the pad rows).  Required when sel_cap > 0.
+ *   d_sel_rank    : optional (NULL is fine): the input rank of every written row, so that the caller can read d_open[rank].
+ *                   A pad row's rank is not written.
+ *   pad_pos, HUFGPU_SELECT_PAD : with the flag the rows from the written count to sel_cap get (pad_pos, 0).  A record of
+ *                   length 0 at raw_size reads and writes nothing in hufgpu_gather() / hufgpu_scatter(): with
+ *                   pad_pos = raw_size those calls take the arrays as they are, with nrecords = sel_cap.
+ *   d_sel_totals  : four words.  [0] the number selected, [1] the number written, [2] the status, [3] the lowest offending
+ *                   rank (0 with status 0).  Required.
+ *
+ * The status is HUF_ERROR_INVALID_ARGUMENT when, among the n spans, a rank r > 0 has pos[r] <= pos[r - 1] or a rank has a
+ * length outside 1 ... HUFGPU_FIND_PATTERN_MAX; r is the offending rank.  This is found on the device, as hufgpu_scatter()
+ * finds its errors: then [0] = [1] = 0 and no span row is written; pad rows are still written, all sel_cap of them.
+ *
+ * Found on the host, HUF_ERROR_INVALID_ARGUMENT, worded "select_spans: ...", in this order: a NULL d_pos, d_len or
+ * d_sel_totals; sel_cap > 0 with a NULL d_sel_pos or d_sel_len; n_cap above HUFGPU_SELECT_MAX; a flag bit other than
+ * HUFGPU_SELECT_PAD; an output array (d_sel_pos, d_sel_len, d_sel_rank, d_sel_totals) that starts at the address of an input
+ * array (d_pos, d_len, d_n); a NULL ctx (there is no CPU path).  n_cap == 0 is not an error: the totals are written as
+ * zeros, and the pads are written.
+ *
+ * Enqueue-only on `stream`: no host read of device memory, no wait.  Capturable - with every buffer of the caller's made
+ * outside the capture - once a call of the same n_cap and sel_cap has made the workspaces.  What runs (kernels/select.hpp,
+ * DESIGN.md 5.27): no length is above 64 and positions rise by at least 1 a rank, so the successor of rank i lies in
+ * (i, i + 64]; a tile of ranks is reduced to a map of 64 entry offsets to 64 exit offsets, the maps are composed in groups
+ * level by level, every tile then walks from its true entry, and a scan of the tiles' counts places the compacted rows.  The
+ * work is O(n_cap); the number of launches does not depend on n_cap up to 2^28.  hufgpu_select_geometry() reports the two
+ * constants: out[0] ranks a tile, out[1] tiles a composition group.
+ *
+ * OUT OF SCOPE: selection for the records calls (records never overlap); lengths above HUFGPU_FIND_PATTERN_MAX;
+ * leftmost-FIRST (Perl) semantics; replacement with text of another length; a fused search + select kernel.
+ */
+#define HUFGPU_SELECT_PAD 1u
+#define HUFGPU_SELECT_MAX (1ull << 30)
+int hufgpu_select_spans(hufgpu_ctx_t *ctx,
+                        const uint64_t *d_pos, const uint32_t *d_len, const uint64_t *d_n, uint64_t n_cap,
+                        uint64_t *d_sel_pos, uint32_t *d_sel_len, uint64_t *d_sel_rank, uint64_t sel_cap,
+                        uint64_t pad_pos, uint64_t *d_sel_totals, uint32_t flags, void *stream);
+void hufgpu_select_geometry(uint32_t out[2]);   /* ranks a tile, tiles a composition group */
 
 /*
  * The sub-index of a stream that came without one: read from a file, written by the reference on a CPU, received from

@@ -88,8 +88,11 @@ hufgpu_find_any_expr hufgpu_find_records_expr hufgpu_scatter hufgpu_scatter_touc
 
 # GPU symbols beyond the list above - declared, loaded and checked by build() as every one of them -, for calls that the closed
 # lists read off GPU_SYMBOLS do not cover: tests/test_gpu_streams.py takes GPU_SYMBOLS' hufgpu_find_* names as the set of search
-# calls that have a stream case each there.  hufgpu_find_any_spans is hufgpu_find_any_expr with a length a start.
-GPU_EXTRA_SYMBOLS = ["hufgpu_find_any_spans"]
+# calls that have a stream case each there.  hufgpu_find_any_spans is hufgpu_find_any_expr with a length a start;
+# hufgpu_select_spans chooses grep -o's non-overlapping matches from its answer.
+GPU_EXTRA_SYMBOLS = ["hufgpu_find_any_spans", "hufgpu_select_spans", "hufgpu_select_geometry"]
+SELECT_PAD = 1          # HUFGPU_SELECT_PAD
+SELECT_MAX = 1 << 30    # HUFGPU_SELECT_MAX
 
 
 def so_path() -> str:
@@ -242,6 +245,10 @@ def load() -> C.CDLL:
                                            L.hufgpu_find_records_context.argtypes[12:])
     L.hufgpu_find_any_spans.restype = C.c_int             # hufgpu_find_any_expr's with (d_len, d_open) behind d_pos
     L.hufgpu_find_any_spans.argtypes = L.hufgpu_find_any_expr.argtypes[:16] + [vp, vp] + L.hufgpu_find_any_expr.argtypes[16:]
+    L.hufgpu_select_spans.restype = C.c_int               # d_pos, d_len, d_n, n_cap; d_sel_pos, d_sel_len, d_sel_rank, sel_cap; pad_pos, d_sel_totals, flags, stream
+    L.hufgpu_select_spans.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, u64, vp, C.c_uint32, vp]
+    L.hufgpu_select_geometry.restype = None
+    L.hufgpu_select_geometry.argtypes = [C.POINTER(C.c_uint32)]
     L.hufgpu_scatter.restype = C.c_int                    # hufgpu_gather's up to max_len, then the new bytes, the cap, update_ranges' outputs
     L.hufgpu_scatter.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, u64, vp, vp, C.c_uint32, vp, u64, C.c_uint8, u64,
                                  vp, u64, vp, vp, vp, C.c_uint32, vp]

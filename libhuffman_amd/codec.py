@@ -1159,7 +1159,8 @@ class GpuCodec:
         scatter() take the tensor as it is with max_len = SPAN_MAX.  open[r] (uint8; None with `want_open=False`) is 1 when a
         longer form could not be ruled out because a byte it needs lies in a block that is not served; totals[3] counts those.
         `out`: (positions, lengths) or (positions, lengths, open), contiguous [max_positions] buffers; made when not given.
-        Every start is reported, overlapping ones included: the leftmost-longest selection of grep -o is the caller's.
+        Every start is reported, overlapping ones included: the leftmost-longest selection of grep -o is select_spans' - or
+        find_matches, which runs both.
         Raises what find_pattern raises."""
         key, _ = self._span_key(pattern, ignore_case, bol, eol, whole_line, word, word_bytes, delimiters)
         max_positions = int(max_positions)
@@ -1177,25 +1178,114 @@ class GpuCodec:
         self._check(err, "Failed to enqueue the search")
         return pos, lens, totals, errs, counts, opn
 
-    def _spans_for(self, stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern, max_matches, relaxed, find):
+    def _spans_for(self, stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern, max_matches, relaxed, find,
+                   nonoverlapping=False):
         """find_spans for the pipelines: (positions, lengths, totals) with the entries behind totals[1] made harmless on the
-        device - a record at raw_size of length 0 reads and writes nothing"""
+        device - a record at raw_size of length 0 reads and writes nothing.  With `nonoverlapping` select_spans stands behind
+        the search and makes them harmless itself (its pad rows); the totals are still the search's."""
         pos, lens, totals = self.find_spans(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
                                             max_positions=max_matches, relaxed=relaxed, want_open=False, **find)[:3]
+        if nonoverlapping:
+            pos, lens, _, _ = self.select_spans(pos, lens, totals[1:2], pad_pos=raw_size)
+            return pos, lens, totals
         written = torch.arange(max_matches, device=self.tdev) < totals[1]
         return torch.where(written, pos, raw_size), torch.where(written, lens, 0), totals
 
+    SELECT_MAX = _native.SELECT_MAX         # spans a select_spans call takes at most
+
+    def select_geometry(self):
+        """(ranks a tile, tiles a composition group) of select_spans' kernels (hufgpu_select_geometry)"""
+        out = (C.c_uint32 * 2)()
+        self.lib.hufgpu_select_geometry(out)
+        return int(out[0]), int(out[1])
+
+    def select_spans(self, positions: torch.Tensor, lengths: torch.Tensor, count: torch.Tensor | None = None, *,
+                     max_selected: int | None = None, pad_pos: int | None = None, want_ranks: bool = False, out=None):
+        """grep -o's non-overlapping leftmost-longest matches, chosen on the device from what find_spans reports
+        (hufgpu_select_spans), on torch's current stream and without a synchronisation.  `positions` (int64 / uint64) and
+        `lengths` (int32) are find_spans' tensors: positions strictly ascending, lengths 1 to SPAN_MAX.  `count` says how many
+        of their rows hold spans: a one-element CUDA int64 / uint64 tensor or a view such as find_spans' totals[1:2]; None:
+        all of them.  Rank 0 is selected, and behind a selected span the first one that starts at or behind its end.
+        `max_selected` (default: the number of rows) caps the rows written; with `pad_pos` - for gather() / scatter():
+        raw_size - the rows behind the written ones become (pad_pos, 0), records that read and write nothing.
+        `out`: (positions, lengths) or (positions, lengths, ranks), contiguous [max_selected] buffers; made when not given.
+        Returns CUDA tensors (positions int64, lengths int32, ranks int64 or None, totals int64 [4]): ranks[r] (with
+        `want_ranks`) is the input rank of row r, totals = [selected, written, status, lowest offending rank] -
+        select_result(totals) waits and reads them.  Eager only: the results are allocated inside the call."""
+        assert positions.is_cuda and positions.dtype in (torch.int64, torch.uint64) and positions.dim() == 1 and positions.is_contiguous()
+        n_cap = positions.numel()
+        assert lengths.is_cuda and lengths.dtype == torch.int32 and lengths.dim() == 1 and lengths.numel() == n_cap and lengths.is_contiguous()
+        if count is not None:
+            assert count.is_cuda and count.dtype in (torch.int64, torch.uint64) and count.numel() == 1
+        sel_cap = n_cap if max_selected is None else int(max_selected)
+        given = tuple(out) if out is not None else ()
+        if out is not None and len(given) not in (2, 3):
+            raise ValueError("`out` is (positions, lengths) or (positions, lengths, ranks)")
+        pos = self._find_buffer(given[0] if given else None, sel_cap, torch.int64)
+        lens = self._find_buffer(given[1] if given else None, sel_cap, torch.int32)
+        ranks = self._find_buffer(given[2] if len(given) == 3 else None, sel_cap, torch.int64) if want_ranks else None
+        totals = torch.empty(4, dtype=torch.int64, device=self.tdev)
+        if n_cap == 0:                                  # the C call wants the two arrays even when it reads nothing of them
+            positions, lengths = torch.empty(1, dtype=torch.int64, device=self.tdev), torch.empty(1, dtype=torch.int32, device=self.tdev)
+        err = self.lib.hufgpu_select_spans(self._ctx, positions.data_ptr(), lengths.data_ptr(),
+                                           count.data_ptr() if count is not None else None, n_cap,
+                                           pos.data_ptr() if sel_cap else None, lens.data_ptr() if sel_cap else None,
+                                           ranks.data_ptr() if want_ranks and sel_cap else None, sel_cap,
+                                           0 if pad_pos is None else int(pad_pos), totals.data_ptr(),
+                                           0 if pad_pos is None else _native.SELECT_PAD, self._stream())
+        self._check(err, "Failed to enqueue the selection")
+        return pos, lens, ranks, totals
+
+    def select_result(self, totals: torch.Tensor):
+        """The one wait behind select_spans / find_matches / count_matches: (selected, written) of their `totals`; raises
+        HuffmanGpuError on a status that is not 0 and names the offending rank."""
+        selected, written, status, rank = (int(v) for v in totals.cpu().tolist())
+        if status:
+            raise HuffmanGpuError(status, "The selection refused its input",
+                                  f"rank {rank}: positions are not strictly ascending there, or its length is not 1 to {self.SPAN_MAX}")
+        return selected, written
+
+    def find_matches(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
+                     sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, max_positions: int = 0,
+                     block_counts: bool = False, relaxed: bool = False, out=None, want_open: bool = True,
+                     ignore_case: bool = False, bol: bool = False, eol: bool = False, whole_line: bool = False,
+                     word: bool = False, word_bytes=None, delimiters=b"\n"):
+        """What grep -o -E prints: find_spans followed by select_spans, with no host wait in between.  The arguments are
+        find_spans' (`max_positions` caps the STARTS the search reports; `out` is the selection's).  Returns CUDA tensors
+        (positions, lengths, sel_totals, find_totals, block_errs, ranks): the selected matches, select_spans' totals, the
+        search's totals and block statuses, and for every selected row its rank among the search's starts (None with
+        `want_open=False`).  This is grep's set when find_totals[0] == find_totals[1] and find_totals[2] == 0; otherwise it
+        is the greedy selection over what the search reported."""
+        spos, slens, ftotals, errs, _, _ = self.find_spans(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
+                                                           max_positions=max_positions, block_counts=block_counts, relaxed=relaxed,
+                                                           want_open=False, ignore_case=ignore_case, bol=bol, eol=eol,
+                                                           whole_line=whole_line, word=word, word_bytes=word_bytes, delimiters=delimiters)
+        pos, lens, ranks, totals = self.select_spans(spos, slens, ftotals[1:2], want_ranks=want_open, out=out)
+        return pos, lens, totals, ftotals, errs, ranks
+
+    def count_matches(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int,
+                      sub_index: torch.Tensor, raw_size: int, blocksize: int, pattern, max_positions: int = 0,
+                      relaxed: bool = False, **find):
+        """grep -o -E | wc -l: find_matches without position buffers for the selection (the search still needs
+        `max_positions` rows: the lengths are its).  Returns CUDA tensors (sel_totals, find_totals, block_errs)."""
+        spos, slens, ftotals, errs, _, _ = self.find_spans(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
+                                                           max_positions=max_positions, relaxed=relaxed, want_open=False, **find)
+        totals = self.select_spans(spos, slens, ftotals[1:2], max_selected=0)[3]
+        return totals, ftotals, errs
+
     def extract(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, sub_index: torch.Tensor,
                 raw_size: int, blocksize: int, pattern, max_matches: int, *, out: torch.Tensor | None = None,
-                relaxed: bool = False, **find):
+                relaxed: bool = False, nonoverlapping: bool = False, **find):
         """What a search finds, byte for byte: find_spans followed by gather(), on torch's current stream with no host wait
-        in between - grep -o without its selection of non-overlapping matches: EVERY start is a row.  `max_matches` is the
+        in between - grep -o without its selection of non-overlapping matches: EVERY start is a row.  With
+        `nonoverlapping=True` select_spans stands between the two: grep -o, a row a match.  `max_matches` is the
         search's cap, `**find` are its keywords (`ignore_case`, `bol`, `word`, ...).  Returns CUDA tensors (slots uint8
         [max_matches, >= SPAN_MAX] - row r holds lengths[r] bytes -, positions, lengths, statuses, totals): statuses are
-        gather()'s per row, and the rows behind totals[1] are made harmless on the device (position raw_size, length 0)."""
+        gather()'s per row, totals the search's, and the rows behind totals[1] - behind the selected ones with
+        `nonoverlapping` - are made harmless on the device (position raw_size, length 0)."""
         max_matches = int(max_matches)
         pos, lens, totals = self._spans_for(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
-                                            max_matches, relaxed, find)
+                                            max_matches, relaxed, find, nonoverlapping)
         slots, statuses, _ = self.gather(stream, stream_len, offsets, nblocks, pos, lens, sub_index=sub_index, raw_size=raw_size,
                                          blocksize=blocksize, max_len=self.SPAN_MAX, out=out, relaxed=relaxed)
         return slots, pos, lens, statuses, totals
@@ -1536,7 +1626,7 @@ class GpuCodec:
     def redact(self, stream: torch.Tensor, stream_len: int, offsets: torch.Tensor, nblocks: int, sub_index: torch.Tensor,
                raw_size: int, blocksize: int, pattern, fill=b"*", *, max_matches: int, lines: bool = False, max_len: int = 0,
                touched_cap: int | None = None, out: torch.Tensor | None = None, want_sub_index: bool = False,
-               relaxed: bool = False, spans: bool = False, **find):
+               relaxed: bool = False, spans: bool = False, nonoverlapping: bool = False, **find):
         """Blank what a search finds: find_pattern (or, with `lines=True`, find_records) followed by scatter(fill=...), on
         torch's current stream with no host wait in between.  Every byte of every occurrence of `pattern` becomes `fill`;
         with `lines=True` the first `max_len` bytes of every selected record do (the delimiter stays).  `max_matches` is
@@ -1548,7 +1638,9 @@ class GpuCodec:
         and an AnyOf of unequal lengths raise ValueError without `lines=True` - or `spans=True`: then the search is
         find_spans, which takes every positions pattern, and the LONGEST form at every start is blanked (scatter with the
         lengths tensor, max_len = SPAN_MAX).  Every start counts, overlapping ones included: what is blanked is the union of
-        the spans.  `spans=True` with `lines=True` is a ValueError.
+        the spans.  `spans=True` with `lines=True` is a ValueError.  With `nonoverlapping=True` (which needs `spans=True`)
+        select_spans stands between the search and the scatter: grep -o's matches are blanked and no others, so with
+        scatter's `data=` in the place of a fill the records could not overlap.
         The scatter is given the search's cap as its number of records, not the found count, which is on the device.  The
         entries behind the found count are made harmless on the device before it runs: positions from totals[1] on are
         replaced by raw_size (and lengths by 0) - a record that starts at raw_size writes nothing.
@@ -1562,9 +1654,11 @@ class GpuCodec:
         max_matches = int(max_matches)
         if spans and lines:
             raise ValueError("redact(spans=True) blanks what matched, redact(lines=True) the records that hold it: give one")
+        if nonoverlapping and not spans:
+            raise ValueError("redact(nonoverlapping=True) selects among spans: give spans=True")
         if spans:
             pos, lengths, totals = self._spans_for(stream, stream_len, offsets, nblocks, sub_index, raw_size, blocksize, pattern,
-                                                   max_matches, relaxed, find)
+                                                   max_matches, relaxed, find, nonoverlapping)
             mlen = self.SPAN_MAX
         elif lines:
             if int(max_len) < 1:

@@ -161,6 +161,14 @@ struct hufgpu_ctx {
     /* hufgpu_scatter (kernels/scatter.hpp): what its kernels hand to its last one; everything else it uses is the
      * workspaces of hufgpu_gather and hufgpu_update_ranges */
     unsigned long long *d_scount;             /* (fixed) */
+
+    /* hufgpu_select_spans (kernels/select.hpp): the maps of the tiles and of every composition level, a mark a rank, the scan
+     * of the tiles' counts, and two words: the lowest offending rank, the selected count; no other call allocates them */
+    uint64_t sws_tiles;
+    uint8_t *d_smaps;
+    uint64_t *d_smarks;
+    unsigned long long *d_swords;
+    TwoLevel sel_scan;
 };
 
 static char g_err[512] = "";
@@ -299,15 +307,19 @@ static const ws_buf WS_UPD_BLOCKS[] = {
     DEV(d_unew, (n + 1) * sizeof(uint64_t)),
 };
 static const ws_buf WS_UPD_PIECES[] = {DEV(d_upiece, n * sizeof(uint32_t))};
+static const ws_buf WS_SELECT[] = {     /* n tiles: their maps and those of the levels above, a sixty-fourth each of the one below */
+    DEV(d_smaps, (n + n / 32 + 16) * SEL_WINDOW), DEV(d_smarks, n * SEL_MARK_WORDS * sizeof(uint64_t)),
+    DEV(d_swords, 2 * sizeof(unsigned long long)),
+};
 
-/* The groups.  Most grow by an eighth; the staging area by a quarter; gather and find double, since their bounds come
+/* The groups.  Most grow by an eighth; the staging area by a quarter; gather, find and select double, since their bounds come
  * from the host's arguments (records x parts, the layout of all blocks) and jump from call to call; the sub-index of a
  * block of many MiB and the range scratch take what they are asked for (grow_range_scratch adds its own eighth).
  * Soft groups report nothing: the caller has another way, or words the error itself. */
 enum { G_FIXED, G_ENCODE, G_CHUNK, G_DECODE, G_DISC_WGS, G_DISC_CANDS, G_BIG_LANES, G_BIG_SUB, G_BSTAGE, G_BATCH, G_RANGE,
        G_RSCRATCH, G_GATHER_BLOCKS, G_GATHER_PARTS, G_FIND_WORDS, G_FIND_TILES, G_FIND_EDGES, G_FIND_REC_WORDS, G_FIND_REC_TILES, G_FIND_SEL, G_FIND_CTX_WORDS, G_FIND_CTX_TILES, G_FIND_ANC_WORDS, G_FIND_ANC_TILES,
        G_FIND_TERM_WORDS, G_FIND_TERM_TILES, G_FIND_TERM_SCAN0, G_FIND_TERM_SCAN1, G_FIND_TERM_SCAN2, G_FIND_TERM_SCAN3, G_SB_BLOCKS, G_SB_CHUNKS, G_UPD_BLOCKS,
-       G_UPD_PIECES, G_COUNT };
+       G_UPD_PIECES, G_SELECT, G_COUNT };
 #define ROWS(a) a, (int)(sizeof(a) / sizeof(a[0]))
 #define CAP(member) {offsetof(hufgpu_ctx, member), WS_NO_CAP}
 #define CAPS(m0, m1) {offsetof(hufgpu_ctx, m0), offsetof(hufgpu_ctx, m1)}
@@ -348,6 +360,7 @@ static const ws_group WS[G_COUNT] = {
     {"sub-build chunks", ROWS(WS_SB_CHUNKS), CAP(sbws_chunks), WS_EIGHTH, false, NO_SCAN},
     {"update blocks", ROWS(WS_UPD_BLOCKS), CAP(uws_blocks), WS_EIGHTH, false, NO_SCAN},
     {"update pieces", ROWS(WS_UPD_PIECES), CAP(uws_pieces), WS_EIGHTH, false, NO_SCAN},
+    {"select tiles", ROWS(WS_SELECT), CAP(sws_tiles), WS_DOUBLE, false, SCAN_AT(sel_scan)},
 };
 
 /* Room in one group (ws_grow): HUFE_OK; HUFE_FATAL with the error text for a hard group; HUFE_MEMORY, silently, for a

@@ -46,6 +46,7 @@ using namespace hufgpu;
 #include "host/ranges.hpp"      /* hufgpu_decode_ranges */
 #include "host/gather.hpp"      /* hufgpu_gather */
 #include "host/find.hpp"        /* hufgpu_find_bytes */
+#include "host/select.hpp"      /* hufgpu_select_spans */
 #include "host/update.hpp"      /* hufgpu_update_ranges, the row encoders */
 #include "host/scatter.hpp"     /* hufgpu_scatter */
 #include "host/append.hpp"      /* hufgpu_append, hufgpu_truncate */

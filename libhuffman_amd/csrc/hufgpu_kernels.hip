@@ -25,6 +25,8 @@
  *            the tiles' edge bytes) -> find_scan -> find_finish (-> find_emit)
  *   the records that hold a pattern (hufgpu_find_records): find_rec_sub (match and delimiter masks of one walk) (-> find_seam)
  *            -> find_rec_dscan -> find_rec_mark -> find_scan -> find_finish (-> find_rec_emit)
+ *   grep -o's non-overlapping matches chosen from the spans of a search (hufgpu_select_spans): select_tile -> select_compose
+ *            (once a level) -> select_mark -> select_emit -> select_finish
  *   append / truncate in place: decode_prepare_kernel on the one block that is opened again -> app_plan -> the indexed
  *            decoders on it -> app_join -> hist_*_pairs -> app_index -> pack_pairs -> app_commit (-> app_sub_rows)
  *
@@ -57,6 +59,7 @@
 #include "kernels/range_tiles.hpp"
 #include "kernels/gather.hpp"
 #include "kernels/find.hpp"
+#include "kernels/select.hpp"
 #include "kernels/sub_build.hpp"
 #include "kernels/update.hpp"
 #include "kernels/scatter.hpp"
